@@ -3,13 +3,16 @@
 512x512 (latent 4x64x64), PLMS 50 steps = 51 UNet evaluations per image at CFG batch 2n.
 
   python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+  python bench.py ... --dump-outputs DIR                  (also write what the last timed step returned, DIR/<name>.npy)
 
 One "step" = one sampler step of the hot path on one batch of synthetic input: a UNet evaluation on
 the CFG-doubled batch (2n latents, context 77x768) through qdiff.QuantModel (HIP graph replay) +
 guidance combine + PLMS multistep update.  Weights are random-init (key-derived, qdiff/synthetic.py),
 quantisers are initialised from data exactly as the reference does on a first forward and converted to
 AdaRound with alpha ~ U(-1,1); no network, no checkpoints.  All inputs are resident in HBM before the
-timed region.  images/sec = N * n / (51 * seconds_per_step)   (51 evals per 50-step PLMS image batch).
+timed region.  ms_per_step = wall time of one timed step; images/sec = N * n / (51 * seconds_per_step)
+(51 evals per 50-step PLMS image batch), the step time charged with 1/51 of the one-off context preparation.
+With the same arguments the inputs (weights, quantisers, latents, conditioning, per-step noise) are the same on every run.
 
 Extra objects on the JSON line:
   roofline     — the dominant kernel class (igemm int8 MFMA contraction): algorithmic int ops of every
@@ -537,10 +540,44 @@ def _committed(suffix):
     return None
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, world, rank, dist):
+    """--dump-outputs: what the last timed step handed its caller, gathered over the ranks in rank order, written by rank 0
+    as <path>/<name>.npy in float32.  Above DUMP_CAP_BYTES in all, every array keeps the same fixed, seeded sample of its
+    batch rows (a function of the batch size only, listed on the JSON line).  Collective when world > 1."""
+    import numpy as np
+    full = {}
+    for name, t in arrays.items():
+        t = t.detach().float().contiguous()
+        if world > 1:
+            parts = [torch.empty_like(t) for _ in range(world)]
+            dist.all_gather(parts, t)
+            t = torch.cat(parts)
+        full[name] = t.cpu()
+    if rank != 0:
+        return None
+    total = sum(t.numel() * 4 for t in full.values())
+    batch = min(t.shape[0] for t in full.values())
+    rows = None
+    if total > DUMP_CAP_BYTES:
+        keep = max(1, batch * DUMP_CAP_BYTES // total)
+        rows = torch.randperm(batch, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+    os.makedirs(path, exist_ok=True)
+    shapes = {}
+    for name, t in full.items():
+        if rows is not None:
+            t = t[rows]
+        np.save(os.path.join(path, name + ".npy"), t.numpy())
+        shapes[name] = list(t.shape)
+    return {"arrays": shapes, "dtype": "float32", "rows": None if rows is None else rows.tolist()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="ranks (one per GPU); default: WORLD_SIZE when launched by torch.distributed.run, else 1")
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed sampler steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--images-per-gpu", type=int, default=8, help="n images per GPU (UNet batch 2n with CFG)")
     ap.add_argument("--model", default="sd", choices=["sd", "ldm", "cifar", "churches"])
@@ -560,7 +597,12 @@ def main():
                          "per step, no enable_hip_graphs / prepare_context calls; prints its own JSON line")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous only (gloo, no GPU): prove that `python bench.py --gpus N` becomes N ranks; used by tests")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned (x_prev = the next latent, pred_x0, eps = the "
+                         "guided noise prediction; whole batch over all ranks) as DIR/<name>.npy, float32, at most 64 MB in all")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.gpus is None:                                  # `torchrun --nproc-per-node N bench.py` without --gpus: N ranks
         a.gpus = int(os.environ.get("WORLD_SIZE", "1"))
 
@@ -582,15 +624,18 @@ def main():
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become N ranks of one node, one process per GPU (the driver's own command line,
-        # SURVEY.md §8e); the children see WORLD_SIZE and fall through to the code below
+        # SURVEY.md §8e); the children see WORLD_SIZE and fall through to the code below.  A fresh child process, not an exec
+        # of this one.
         import socket
+        import subprocess
         s = socket.socket()
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
         s.close()
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={a.gpus}",
-                                  "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={a.gpus}",
+                            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        raise SystemExit(r.returncode)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != a.gpus:
         raise SystemExit(f"bench.py: --gpus {a.gpus} but WORLD_SIZE={world}; launch with --nproc-per-node {a.gpus}")
@@ -696,7 +741,8 @@ def main():
         else:
             e_prime = e
         noise = state["noise"]() if state["noise"] is not None else None      # eta > 0: the whole batch's draw, this rank's slice
-        state["x"], _ = table.update(state["x"], e_prime, index, noise)
+        state["x"], state["pred_x0"] = table.update(state["x"], e_prime, index, noise)
+        state["eps"] = e
         old.append(e)
         if len(old) >= 4:
             old.pop(0)
@@ -721,9 +767,15 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     assert torch.isfinite(state["x"]).all(), "sampler state diverged"
+    dumped = None
+    if a.dump_outputs:                                 # before anything below runs the model again
+        dumped = dump_outputs(a.dump_outputs, {"x_prev": state["x"], "pred_x0": state["pred_x0"], "eps": state["eps"]}, world, rank, dist)
 
-    ms_per_step = 1000.0 * elapsed / a.steps + prepare_ms / evals
-    images_per_s = gb / (evals * ms_per_step / 1000.0)
+    # ms_per_step = wall time of one timed step; charged_ms adds the one-off context preparation of an image batch, spread
+    # over its evaluations: images/s and the figures derived from the step time use it
+    ms_per_step = 1000.0 * elapsed / a.steps
+    charged_ms = ms_per_step + prepare_ms / evals
+    images_per_s = gb / (evals * charged_ms / 1000.0)
 
     def retime(warm=4):
         """The timed loop again (same model, whatever stream type / batch is now in force): ms per step, rank-local."""
@@ -746,10 +798,12 @@ def main():
                                f"W{qspec['w_bits']}A8 sm_abit={qspec['sm_abit']}{'' if kind == 'churches' else ' split'}, hip-graph={'off' if a.no_graph else 'on'}"
                                + (f", cross-attention K/V of the run's context prepared once per image batch ({prepare_ms:.2f} ms, charged as /{evals} per step)"
                                   if ctx_prepared else (", cross-attention K/V recomputed per evaluation" if ctx_shape else "")),
-                   "images_per_gpu": n, "global_batch": gb, "single_unet_step_ms": round(ms_per_step, 4), "eta": eta,
+                   "images_per_gpu": n, "global_batch": gb, "single_unet_step_ms": round(charged_ms, 4), "eta": eta,
                    "context_prepare_ms": round(prepare_ms, 3), "context_prepared": ctx_prepared,
                    "parallelism": f"batch-sharded x{world}, quant-state broadcast {nbytes} B"},
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if kind == "cifar" and rank == 0:
         # BASELINE configs[1] as a whole-sampler-step graph (generalized_steps captured like DevicePLMS): the pixel-space UNet
         # is launch-latency-bound (~0.04 of the MFMA peak), so the per-step host work a graph of the evaluation alone leaves
@@ -805,7 +859,7 @@ def main():
         # whole-step view: every integer op of the evaluation (contractions + attention, SURVEY.md §8d per-sample figures)
         # against the wall clock of the timed sampler step
         per_sample_gop = {"sd": 803.0, "ldm": 202.0, "cifar": 12.5, "churches": 41.8}[kind]
-        step_top = per_sample_gop * 1e9 * (xb.shape[0] * (2 if guide != 1.0 else 1)) / (ms_per_step * 1e-3) / 1e12
+        step_top = per_sample_gop * 1e9 * (xb.shape[0] * (2 if guide != 1.0 else 1)) / (charged_ms * 1e-3) / 1e12
         out["roofline"] = {"bound": "mfma", "achieved": round(ach, 2), "peak": I8_MFMA_PEAK_TOPS, "unit": "TOP/s",
                            "frac": round(ach / I8_MFMA_PEAK_TOPS, 4), "traffic": traffic, "traffic_source": traffic_src,
                            "frac_of_ubench_ceiling_4404": round(ach / I8_MFMA_UBENCH_TOPS, 4),
@@ -824,7 +878,7 @@ def main():
                            # guidance / sampler update glue)
                            "by_class": r["by_class"], "eval_ms_eager": r["eval_ms"], "library_launches_per_eval": r["library_launches"],
                            "graph_replay_eval_ms": replay_ms,
-                           "sampler_glue_ms": (round(ms_per_step - prepare_ms / evals - replay_ms, 4) if replay_ms is not None else None),
+                           "sampler_glue_ms": (round(ms_per_step - replay_ms, 4) if replay_ms is not None else None),
                            "attention_calls": r["attention_calls"], "producer_entries": r["producer_entries"],
                            "frac_of_box_ubench": (round(ach / box["mfma_ubench_tops"], 4) if box.get("mfma_ubench_tops") else None),
                            "whole_step_frac_of_box_ubench": (round(step_top / box["mfma_ubench_tops"], 4) if box.get("mfma_ubench_tops") else None)}
@@ -833,8 +887,8 @@ def main():
             # same UNet, same batch, same GPU, same run: the denominators of north_star's ">= 4x the reference fp32
             # PyTorch-ROCm UNet" target
             den = gpu_denominators(qnn, margs)
-            den["speedup_vs_fp32_unet"] = round(den["fp32_unet_ms"] / ms_per_step, 2)
-            den["speedup_vs_fake_quant_sim"] = round(den["fake_quant_sim_ms"] / ms_per_step, 2)
+            den["speedup_vs_fp32_unet"] = round(den["fp32_unet_ms"] / charged_ms, 2)
+            den["speedup_vs_fake_quant_sim"] = round(den["fake_quant_sim_ms"] / charged_ms, 2)
             den["note"] = ("ms per UNet evaluation at the bench batch; fp32_unet = quantisation off (org_weight path, MIOpen/rocBLAS "
                            "fp32); fake_quant_sim = the reference's fp32 simulation arithmetic on the GPU (fake-quantised weights cached)")
             out["gpu_denominators"] = den
@@ -874,11 +928,12 @@ def main():
                             prep_b = 1000.0 * (time.perf_counter() - t1) / 3
                 if eta > 0.0:
                     state["noise"] = sampling.ShardedStepNoise(nb, shape, 4321, 1, 0, dev)
-                ms_b = retime() + prep_b / evals
+                ms_b = retime()
+                charged_b = ms_b + prep_b / evals
                 nsamp = nb * (2 if guide != 1.0 else 1)
                 out["config"]["extra_batch"] = {"images_per_gpu": nb, "eval_batch": nsamp, "ms_per_step": round(ms_b, 4),
-                                                "images_per_s": round(nb / (evals * ms_b / 1000.0), 4),
-                                                "whole_step_frac": round(per_sample_gop * 1e9 * nsamp / (ms_b * 1e-3) / 1e12 / I8_MFMA_PEAK_TOPS, 4)}
+                                                "images_per_s": round(nb / (evals * charged_b / 1000.0), 4),
+                                                "whole_step_frac": round(per_sample_gop * 1e9 * nsamp / (charged_b * 1e-3) / 1e12 / I8_MFMA_PEAK_TOPS, 4)}
             except Exception as exc:  # noqa: BLE001 - never lose the line over an extra
                 out["config"]["extra_batch"] = {"error": repr(exc)[:200]}
             finally:
@@ -896,11 +951,11 @@ def main():
                     with torch.no_grad():
                         qnn(torch.cat([state["x"]] * 2), torch.full((2 * state["x"].shape[0],), 500, device=dev, dtype=torch.long), ctx2)
                         qnn.prepare_context(ctx2)
-                    ms16 = retime() + prepare_ms / evals
+                    ms16 = retime()
                     measure_igemm(qnn, margs)
                     r16 = measure_igemm(qnn, margs)
                     ach16 = r16["ops"] / (r16["total_ms"] * 1e-3) / 1e12
-                    other["sd_fp16_stream"] = {"ms_per_step": round(ms16, 4), "value": round(gb / (evals * ms16 / 1000.0), 4), "unit": "images/s",
+                    other["sd_fp16_stream"] = {"ms_per_step": round(ms16, 4), "value": round(gb / (evals * (ms16 + prepare_ms / evals) / 1000.0), 4), "unit": "images/s",
                                                "dtype": "int8xint4->int32 (fp16 residual stream)", "vs_fp32_stream_ms": round(ms16 - ms_per_step, 4),
                                                "igemm_ms_per_eval": round(r16["total_ms"], 3), "igemm_frac": round(ach16 / I8_MFMA_PEAK_TOPS, 4),
                                                "by_launch_class": r16["classes"], "envelope": _committed("_fp16_envelope.json")}
