@@ -1409,7 +1409,8 @@ static int& kgroups_knob() {
 constexpr int kgroups_min_steps() { return 8; }
 
 // qd_conv2d_i8_group runs every member through run() — all its checks, its tile choice — with this set: dispatch() then
-// records the finished kernel descriptor and the tile it would have launched instead of launching.
+// records the finished kernel descriptor and the tile it would have launched instead of launching, and run() returns right
+// after it (no split-K finalise pass, no launch check).
 struct GroupCapture { ConvD k; int out, tile; bool split; };
 thread_local GroupCapture* g_capture = nullptr;
 constexpr int tile_code(int MT, int NT, int WM, int WN, int WB) { return (((MT * 16 + NT) * 8 + WM) * 8 + WN) * 32 + WB; }
@@ -1596,7 +1597,9 @@ int run(const qd_conv_desc* d, int32_t* iout, void* stream) {
             case 4:  rc = dispatch<1, 4, 4, 1>(k, false, O_PART, st, nsplit); break;
             default: rc = dispatch<1, 2, 4, 1>(k, false, O_PART, st, nsplit); break;
         }
-        if (rc) return rc;
+        // a grouped launch's probe (g_capture set) launches nothing: the finalise pass would read stale partials, write `out`
+        // and, with out == residual, corrupt the residual the member's real launch reads next
+        if (rc || g_capture) return rc;
         const SegD& sg = k.seg[0];
         const long MN = M * N;
         dim3 grid((unsigned)((MN + 255) / 256)), block(256);
@@ -1651,7 +1654,7 @@ int run(const qd_conv_desc* d, int32_t* iout, void* stream) {
     } else {
         rc = dispatch<1, 2, 4, 1>(k, split, out, st);
     }
-    if (rc) return rc;
+    if (rc || g_capture) return rc;
     QD_LAUNCH_CHECK("qd_conv2d_i8");
     return 0;
 }
