@@ -442,6 +442,38 @@ int qd_groupnorm_silu_h16(const float* x, int64_t B, int64_t S, int C, int64_t l
                           const float* gamma, const float* beta, int apply_silu, int out_dtype, void* out, int64_t ldo, void* ws,
                           const float* part_in, int nchunk_in, int64_t part_ld, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Weights-only layers (additive in ABI 20).  Replaces the (weight_quant, act_quant) = (True, False) state of
+ *     QuantModule.forward (qdiff/quant_layer.py:620-631: fwd_func on the fake-quantised fp32 weight, i.e.
+ *     F.conv2d / F.conv1d / F.linear of quant_layer.py:276 with UniformAffineQuantizer / AdaRoundQuantizer applied to the
+ *     weight only, quant_layer.py:82-88, adaptive_rounding.py:49-61) by a contraction of the PACKED weight codes with fp16 or
+ *     bf16 activations and fp32 accumulation (v_mfma_f32_32x32x16_f16 / _bf16):
+ *        out[m][n] = sum_seg delta_s[n] * sum_k x[m][k] * (q_s[k][n] - z_s[n]) + bias[n] (+ residual[m][n])
+ *     The zero point is subtracted from the code in registers (no activation row sums), so every product is exact in fp32.
+ *
+ *     qd_conv2d_wq_h16: the descriptor of qd_conv2d_i8 with
+ *         x          fp16 (act_dtype = QD_F16) or bf16 (QD_BF16) channels-last rows [B*H*W][ldx] of qd_rows_to_h16;
+ *                    ldx, seg.c0, seg.clen count ELEMENTS (multiples of 8); channels of a segment past its real width
+ *                    must be zero (qd_rows_to_h16 writes them so)
+ *         w          the tile-ordered codes of qd_pack_weights_t4 (wbits = 4) / _t8 (wbits = 8), w_tiled = 1, seg.kstep0
+ *                    as for qd_conv2d_i8: the packs of the integer path serve this mode unchanged
+ *         seg.scale  [Cout] delta_w[n] of the segment's weight quantiser;  seg.zw: [Cout] its RAW zero point z[n]
+ *                    in [-128, 255] (not zw - 128);  seg.zc / zfill / fill16 must be NULL
+ *         nseg 1 or 2 (split shortcut, quant_layer.py:257-269: each segment its own delta / z), epilogue = QD_EPI_LINEAR,
+ *         out_dtype QD_F32 or QD_F16 (the residual has the type of the output), kh/kw/stride/pad_t/pad_l as for
+ *         qd_conv2d_i8; out-of-image taps, K tails and M tails read zeros.  rowbias, gn_part, upsample2x must be unset;
+ *         split-K, oq_* / hd_* are ignored.
+ *         bf16 operands carry q - z exactly only while |q - z| <= 256 for every stored code: the caller checks (8-bit
+ *         codes with z < -1 can exceed it); fp16 is exact for every zero point in [-128, 255].
+ *     qd_rows_to_h16: the producer of those rows.  x is a logical [B][C][S] fp32 / fp16 / bf16 tensor addressed by element
+ *         strides (sb, sc, ss) as in qd_quantize_act; channels [c0, c0+clen) are rounded to out_dtype (QD_F16 / QD_BF16,
+ *         nearest even) and written to out[(b*S+s)*ldo + oc0 + (c-c0)], channels up to clen_pad are set to zero.
+ *         One call per segment; clen_pad, oc0 and ldo are multiples of 8.
+ * ------------------------------------------------------------------------------------------ */
+int qd_conv2d_wq_h16(const qd_conv_desc* d, int act_dtype, void* stream);
+int qd_rows_to_h16(const void* x, int x_dtype, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc, int64_t ss,
+                   int c0, int clen, int clen_pad, void* out, int out_dtype, int64_t ldo, int oc0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -460,6 +460,118 @@ def conv_forward_geglu(plan, xq, M, next_plan):
 
 
 # ------------------------------------------------------------------------------------------------
+# weights-only layers: state (weight_quant, act_quant) = (True, False) on the packed codes (qd_conv2d_wq_h16)
+# ------------------------------------------------------------------------------------------------
+def _parse_weight_only(v):
+    v = (v or "").strip().lower()
+    if v in ("", "0", "off", "none", "fp32", "float32"):
+        return None
+    if v in ("fp16", "half", "float16"):
+        return torch.float16
+    if v in ("bf16", "bfloat16"):
+        return torch.bfloat16
+    raise ValueError(f"QDIFF_WEIGHT_ONLY={v!r}: expected fp16, bf16 or off")
+
+
+# Weights-only kernel: None (default) = a weights-only QuantModule runs the reference's floating-point path (the fake-quantised
+# fp32 weight through the library convolution, quant_layer.py:620-631); torch.float16 / torch.bfloat16 = it contracts its
+# packed int4 / int8 codes with activations rounded to that type (qd_conv2d_wq_h16), and layers the kernel does not cover keep
+# the library path.  QDIFF_WEIGHT_ONLY=fp16|bf16, or engine.set_weight_only_kernel().
+WEIGHT_ONLY_KERNEL = _parse_weight_only(os.environ.get("QDIFF_WEIGHT_ONLY"))
+
+
+def set_weight_only_kernel(dtype):
+    """None, torch.float16 or torch.bfloat16 (or the strings QDIFF_WEIGHT_ONLY accepts)."""
+    global WEIGHT_ONLY_KERNEL
+    if isinstance(dtype, str):
+        dtype = _parse_weight_only(dtype)
+    if dtype not in (None, torch.float16, torch.bfloat16):
+        raise ValueError("weight-only kernel dtype must be None, torch.float16 or torch.bfloat16")
+    WEIGHT_ONLY_KERNEL = dtype
+
+
+def wonly_device_ok(t):
+    """The weights-only kernel runs on GPU tensors only; anything else keeps the library path."""
+    return t.is_cuda
+
+
+class WonlyPlan:
+    """Frozen launch state of one weights-only QuantModule: the pack of the integer path, per segment delta_w and the RAW
+    weight zero point, the activation row layout (the same segment offsets as the int8 rows)."""
+    __slots__ = ("pack", "kh", "kw", "stride", "pad", "bias", "segs", "Cout", "Cin", "ldx", "act_dtype")
+
+
+def wonly_code_span(pack):
+    """max |q - z| over the stored codes of every channel (one host read; 4-bit codes are bounded by 255 without looking)."""
+    if pack.mode == 4:
+        return 255
+    ntiles = (pack.Cout + 31) // 32
+    q = pack.wq.view(torch.int8).view(-1, ntiles, 4, 32, 16).to(torch.int32) + 128      # [kstep][jt][kh4][nn][16] codes
+    q = q.permute(1, 3, 0, 2, 4).reshape(ntiles * 32, -1)[:pack.Cout]
+    span = 0
+    for sg in pack.segs:
+        k0, k1 = sg["kstep0"] * 64, (sg["kstep0"] + pack.taps * ((sg["clen_pad"] + 63) // 64)) * 64
+        z = (sg["zw"].to(torch.int32) + 128).view(-1, 1)
+        d = (q[:, k0:k1] - z).abs().max()
+        span = max(span, int(d.item()))
+    return span
+
+
+def build_wonly_plan(pack, kh, kw, stride, pad, bias, act_dtype):
+    """WonlyPlan for `pack` (engine.pack_module_weights or a packed checkpoint's frozen pack), or None when the kernel does
+    not take it: a row-permuted pack, or bf16 operands and a stored code with |q - z| > 256 (not exact in bf16)."""
+    if not pack.tiled or pack.row_perm is not None or pack.mode not in (4, 8):
+        return None
+    if act_dtype == torch.bfloat16 and wonly_code_span(pack) > 256:
+        return None
+    plan = WonlyPlan()
+    plan.pack, plan.kh, plan.kw, plan.stride, plan.pad = pack, kh, kw, stride, pad
+    plan.bias = bias.detach().float().contiguous() if bias is not None else None
+    plan.Cout, plan.Cin, plan.act_dtype = pack.Cout, pack.Cin, act_dtype
+    plan.segs = []
+    for sg in pack.segs:
+        zraw = (sg["zw"].to(torch.int32) + (128 if pack.mode == 8 else 0)).contiguous()
+        plan.segs.append(dict(c0=sg["kofs"], clen=sg["clen_pad"], kofs=sg["kofs"], kstep0=sg.get("kstep0", 0),
+                              scale=sg["delta_w"].float().contiguous(), zw=zraw, zc=None, zfill=None, fill16=None, wzp=None))
+    plan.ldx = pad16(sum(s["clen_pad"] for s in pack.segs))
+    return plan
+
+
+def wonly_rows(x, plan, B, C, S, strides):
+    """Logical [B][C][S] float tensor -> the plan's fp16 / bf16 rows [B*S][ldx] (pad channels zero)."""
+    out = torch.empty((B * S, plan.ldx), dtype=plan.act_dtype, device=x.device)
+    for sg, d in zip(plan.pack.segs, plan.segs):
+        hip.rows_to_h16(x, B, C, S, strides, out, plan.ldx, sg["c0w"], sg["clen"], sg["clen_pad"], d["c0"])
+    return out
+
+
+def wonly_out_dtype(device_type="cuda"):
+    """(kernel output dtype, final cast or None): fp32 outside autocast; under autocast the type the library convolution
+    returns there (fp16 is written by the kernel; a bf16 autocast gets the fp32 rows cast)."""
+    try:
+        on, dt = torch.is_autocast_enabled(device_type), torch.get_autocast_dtype(device_type)
+    except (TypeError, AttributeError):
+        on, dt = torch.is_autocast_enabled(), torch.get_autocast_gpu_dtype()
+    if not on or dt == torch.float32:
+        return torch.float32, None
+    return (torch.float16, None) if dt == torch.float16 else (torch.float32, dt)
+
+
+def wonly_forward(plan, xh, B, H, W, Ho, Wo, out_dtype=torch.float32, residual=None):
+    """qd_conv2d_wq_h16 on the rows of wonly_rows: returns out [B*Ho*Wo][Cout] (row-major)."""
+    M = B * Ho * Wo
+    out = torch.empty((M, plan.Cout), dtype=out_dtype, device=xh.device)
+    if residual is not None and residual.dtype != out_dtype:
+        residual = residual.to(out_dtype)
+    call = hip.ConvCall(x=xh, w=plan.pack.wq, out=out, bias=plan.bias, residual=residual, ldx=plan.ldx, ldk=plan.pack.ldk,
+                        ldo=out.stride(0), ldr=(residual.stride(0) if residual is not None else 0), ld_rowbias=0,
+                        B=B, H=H, W=W, Ho=Ho, Wo=Wo, Cout=plan.Cout, kh=plan.kh, kw=plan.kw, stride=plan.stride,
+                        pad_t=plan.pad, pad_l=plan.pad, wbits=plan.pack.wbits, w_tiled=True, segs=plan.segs)
+    hip.conv2d_wq_h16(call, plan.act_dtype)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # producers (K5, K9)
 # ------------------------------------------------------------------------------------------------
 _ws_cache = {}

@@ -67,7 +67,7 @@ EXPORTS = ["qd_abi_version", "qd_last_error", "qd_device_ok", "qd_box_probe", "q
            "qd_geglu_quant", "qd_quantize_heads", "qd_attn_i8", "qd_attn_keyterm", "qd_attn_uses_keyterm", "qd_attn_config", "qd_attn_ws_bytes", "qd_bmm_qk_i8", "qd_bmm_pv_i8", "qd_temb_mlp",
            "qd_fakequant_blocks", "qd_fakequant_fwd", "qd_fakequant_bwd",
            "qd_conv2d_bf16", "qd_pack_weights_bf16_bytes", "qd_pack_weights_bf16", "qd_groupnorm_silu_bf16",
-           "qd_pack_weights_h16", "qd_groupnorm_silu_h16"]
+           "qd_pack_weights_h16", "qd_groupnorm_silu_h16", "qd_conv2d_wq_h16", "qd_rows_to_h16"]
 
 _lib = None
 
@@ -127,6 +127,8 @@ def load():
     lib.qd_groupnorm_silu_bf16.argtypes = [vp, i64, i64, i32, i64, i32, f32, vp, vp, i32, vp, i64, vp, vp, i32, i64, vp]
     lib.qd_pack_weights_h16.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp]
     lib.qd_groupnorm_silu_h16.argtypes = [vp, i64, i64, i32, i64, i32, f32, vp, vp, i32, i32, vp, i64, vp, vp, i32, i64, vp]
+    lib.qd_conv2d_wq_h16.argtypes = [ctypes.POINTER(ConvDesc), i32, vp]
+    lib.qd_rows_to_h16.argtypes = [vp, i32, i64, i64, i64, i64, i64, i64, i32, i32, i32, vp, i32, i64, i32, vp]
     lib.qd_box_probe.argtypes = [i32, i32, i32, vp, vp, vp]
     lib.qd_attn_ws_bytes.argtypes = [i32, i32, i32, i32]
     lib.qd_attn_ws_bytes.restype = ctypes.c_int64
@@ -366,6 +368,28 @@ def conv2d_bf16(x, wt, bias, out, B, H, W, Cin_pad, Cout, k=3, pad=1, residual=N
     d.nseg = 1
     d.seg[0].c0, d.seg[0].clen = 0, Cin_pad
     _check(load().qd_conv2d_bf16(ctypes.byref(d), _stream()), "qd_conv2d_bf16")
+
+
+# ---- weights-only layers: fp16 / bf16 activations x packed weight codes (include/qdiff_hip.h, "Weights-only layers") ----
+_H16 = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
+
+
+def rows_to_h16(x, B, C, S, strides, out, ldo, c0, clen, clen_pad, oc0):
+    """Logical [B][C][S] fp32 / fp16 / bf16 tensor (element strides) -> fp16 / bf16 rows (the dtype of `out`): channels
+    [c0, c0+clen) at row offset oc0, zeros up to clen_pad (qd_rows_to_h16)."""
+    if x.dtype not in _H16 or out.dtype not in (torch.float16, torch.bfloat16):
+        raise HipEngineError(f"rows_to_h16: unsupported dtypes {x.dtype} -> {out.dtype}")
+    sb, sc, ss = strides
+    _check(load().qd_rows_to_h16(_ptr(x, "x"), _H16[x.dtype], B, C, S, sb, sc, ss, c0, clen, clen_pad, _ptr(out, "out"),
+                                 _H16[out.dtype], ldo, oc0, _stream()), "qd_rows_to_h16")
+
+
+def conv2d_wq_h16(c, act_dtype):
+    """ConvCall whose x are fp16 / bf16 rows and whose segs carry scale = delta_w, zw = raw zero points (qd_conv2d_wq_h16)."""
+    if act_dtype not in (torch.float16, torch.bfloat16):
+        raise HipEngineError("conv2d_wq_h16: activations must be float16 or bfloat16")
+    d = _conv_desc(c)
+    _check(load().qd_conv2d_wq_h16(ctypes.byref(d), _H16[act_dtype], _stream()), "qd_conv2d_wq_h16")
 
 
 def groupnorm_silu_bf16(x, B, S, C, groups, eps, gamma, beta, silu, out, ws, part=None):

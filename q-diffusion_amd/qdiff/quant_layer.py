@@ -447,6 +447,7 @@ class QuantModule(nn.Module):
         tracking, so call this (or QuantModel.invalidate_plans()) after such an edit."""
         engine.bump_state()
         self._pack_key = self._plan_key = self._wdq_key = None
+        self.__dict__.pop('_wonly_cache', None)
         self.__dict__.pop('_geglu_cache', None)
         self.__dict__.pop('_heads_cache', None)
         self.__dict__.pop('_frozen_pack', None)
@@ -460,6 +461,7 @@ class QuantModule(nn.Module):
         self.__dict__['_frozen_pack'] = pack
         self.__dict__['_frozen_geglu_pack'] = geglu_pack
         self._pack_key = self._plan_key = None
+        self.__dict__.pop('_wonly_cache', None)
         self.__dict__.pop('_geglu_cache', None)
         self.__dict__.pop('_heads_cache', None)
 
@@ -542,6 +544,85 @@ class QuantModule(nn.Module):
         out = engine.conv_forward(plan, xq, 1, 1, M, 1, M)
         return out.view(*lead, plan.Cout)
 
+    # -- weights-only kernel (engine.WEIGHT_ONLY_KERNEL) ---------------------------------------------
+    def _wonly_state(self):
+        """Weights quantised, activations not (state (True, False) or disable_act_quant), no autograd, no simulation, knob set."""
+        return (engine.WEIGHT_ONLY_KERNEL is not None and not engine.SIMULATE and self.use_weight_quant
+                and not (self.use_act_quant and not self.disable_act_quant and self.act_quant_mode == 'qdiff')
+                and not torch.is_grad_enabled())
+
+    def wonly_plan(self):
+        """engine.WonlyPlan of the current weight quantisers for engine.WEIGHT_ONLY_KERNEL, or None when the kernel does not
+        take this layer (grouped / dilated convolution, a weight quantiser the packer refuses — symmetric, per-tensor, AdaRound
+        soft targets — or bf16 operands with |q - z| > 256): the layer then keeps the library path.  Built from the pack of
+        the integer path (or a packed checkpoint's frozen pack) without touching the activation quantisers; cached under the
+        weight part of plan_keys() and dropped by invalidate()."""
+        dt = engine.WEIGHT_ONLY_KERNEL
+        if dt is None:
+            return None
+        geo = self._geometry()
+        cache = self.__dict__.setdefault('_wonly_cache', [None, None])
+        if geo is None:
+            cache[0], cache[1] = None, None
+            return None
+        wkey, akey = self.plan_keys()
+        key = (wkey, akey[2], dt)
+        if cache[0] == key:
+            return cache[1]
+        frozen = self.__dict__.get('_frozen_pack')
+        pack = None
+        if frozen is not None:
+            pack = frozen
+        elif self._pack_key == wkey:
+            pack = self._pack
+        else:
+            try:
+                pack = engine.pack_module_weights(self.weight, self._weight_quantizers(), self.split)
+            except hip.HipEngineError:
+                pack = None
+            else:
+                self._pack, self._pack_key, self._plan_key = pack, wkey, None
+        kh, kw, stride, pad = geo
+        plan = engine.build_wonly_plan(pack, kh, kw, stride, pad, self.bias, dt) if pack is not None else None
+        cache[0], cache[1] = key, plan
+        return plan
+
+    def wonly_ready(self):
+        """True when the next forward of this module runs the weights-only kernel (kept apart from int_ready(): the blocks'
+        fused integer routes must not engage in this state)."""
+        return self._wonly_state() and self.wonly_plan() is not None
+
+    def _weights_freed(self):
+        return self.__dict__.get('_frozen_pack') is not None and self.weight.numel() == 0
+
+    def _forward_wonly(self, x, plan):
+        out_dtype, cast = engine.wonly_out_dtype(x.device.type)
+        if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            x = x.float()
+        if self.kind == 'conv2d':
+            B, C, H, W = x.shape
+            sb, sc, sh, sw = x.stride()
+            if sh != W * sw:
+                x = x.contiguous(memory_format=torch.channels_last)
+                sb, sc, sh, sw = x.stride()
+            xh = engine.wonly_rows(x, plan, B, C, H * W, (sb, sc, sw))
+            Ho, Wo = engine.conv_out_hw(H, W, plan)
+            y = engine.wonly_forward(plan, xh, B, H, W, Ho, Wo, out_dtype).view(B, Ho, Wo, plan.Cout).permute(0, 3, 1, 2)
+        elif self.kind == 'conv1d':
+            B, C, T = x.shape
+            xh = engine.wonly_rows(x, plan, B, C, T, x.stride())
+            To = (T + 2 * plan.pad - plan.kw) // plan.stride + 1
+            y = engine.wonly_forward(plan, xh, B, 1, T, 1, To, out_dtype).view(B, To, plan.Cout).permute(0, 2, 1)
+        else:
+            lead, K = x.shape[:-1], x.shape[-1]
+            rows = x.reshape(-1, K)
+            if rows.stride(1) != 1:
+                rows = rows.contiguous()
+            M = rows.shape[0]
+            xh = engine.wonly_rows(rows, plan, 1, K, M, (0, 1, rows.stride(0)))
+            y = engine.wonly_forward(plan, xh, 1, 1, M, 1, M, out_dtype).view(*lead, plan.Cout)
+        return y if cast is None else y.to(cast)
+
     def geglu_plan(self):
         """Second plan of a GEGLU projection: rows packed (value tile, gate tile) interleaved for the fused
         value*gelu(gate)->quantise epilogue (engine.conv_forward_geglu).  None if the layer does not
@@ -620,7 +701,16 @@ class QuantModule(nn.Module):
         self._note_split(split)
         if not torch.is_grad_enabled() and self.int_ready():
             return self.activation_function(self._forward_int(input, out_slot))
+        if self._wonly_state() and engine.wonly_device_ok(input):
+            plan = self.wonly_plan()
+            if plan is not None:
+                return self.activation_function(self._forward_wonly(input, plan))
         # simulated / floating-point states: (False, *), weights-only, or calibration under autograd
+        if self._weights_freed():
+            raise hip.HipEngineError(
+                f"QuantModule({self.kind}): the fp32 weights were released by load_packed_ckpt(free_weights=True), so only the "
+                "packed kernels can run it: the integer state (True, True), or the weights-only state with the weights-only "
+                "kernel on (qdiff.engine.set_weight_only_kernel(torch.float16 | torch.bfloat16) or QDIFF_WEIGHT_ONLY=fp16|bf16)")
         if not self.disable_act_quant and self.use_act_quant and self.act_quant_mode == 'qdiff':
             parts = [q(xs) for q, xs in zip(self._act_quantizers(), self._input_slices(input))]
             input = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
