@@ -4,6 +4,11 @@
 
   python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
   python bench.py ... --dump-outputs DIR                  (also write what the last timed step returned, DIR/<name>.npy)
+  python bench.py ... --full                              (also every measurement beyond the headline, listed below)
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the headline line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, config).  --full adds, after the headline numbers are taken, the extra objects below
+(and, for cifar, config.whole_step_graph_*); --decode and --extra-batch are additions to such a run and imply --full.
 
 One "step" = one sampler step of the hot path on one batch of synthetic input: a UNet evaluation on
 the CFG-doubled batch (2n latents, context 77x768) through qdiff.QuantModel (HIP graph replay) +
@@ -14,7 +19,7 @@ timed region.  ms_per_step = wall time of one timed step; images/sec = N * n / (
 (51 evals per 50-step PLMS image batch), the step time charged with 1/51 of the one-off context preparation.
 With the same arguments the inputs (weights, quantisers, latents, conditioning, per-step noise) are the same on every run.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line of a --full run:
   roofline     — the dominant kernel class (igemm int8 MFMA contraction): algorithmic int ops of every
                  launch of one UNet evaluation / their HIP-event durations on the launch stream; fractions against
                  the nominal 5.0 POP/s and the 4.404 POP/s micro-benchmark ceiling; whole_step_* = all integer ops of
@@ -27,6 +32,9 @@ Extra objects on the JSON line:
                  the reference's fp32 fake-quant simulation (rank 0, N=1 only).
   cpu_baseline — the oracle (CPU port of the reference fake-quant forward, oracle/unet_ref.py) timed on
                  this box's host cores: one warm-up + two timed UNet evaluations of one sample (rank 0, N=1 only).
+  other_configs — (sd, N=1) the same workload on the fp16 activation stream, then child runs: the CIFAR-10 and LDM-4 lines,
+                 the unmodified sampler's call pattern (--as-script) and the first-stage decode; config.extra_batch = the
+                 loop at 5 images per GPU.
 """
 import argparse
 import json
@@ -501,7 +509,7 @@ def extra_lines(a):
     extra keys of the headline line: short runs in child processes with a time cap, started AFTER the headline numbers are
     computed, so that nothing here can lose them."""
     out = {}
-    common = ["--no-cpu-baseline", "--no-denominators", "--no-extras", "--steps", "10", "--warmup", "2"]
+    common = ["--full", "--no-cpu-baseline", "--no-denominators", "--no-extras", "--steps", "10", "--warmup", "2"]
     for kind, n in (("cifar", 64), ("ldm", 64)):
         # BASELINE configs[2] (LDM-4) is quoted at `-n 10 -e 1.0` (README.md:47-49): batch 10 is that line's headline, batch 64 the
         # throughput point; both from one child (same model, same process)
@@ -582,16 +590,21 @@ def main():
     ap.add_argument("--images-per-gpu", type=int, default=8, help="n images per GPU (UNet batch 2n with CFG)")
     ap.add_argument("--model", default="sd", choices=["sd", "ldm", "cifar", "churches"])
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-denominators", action="store_true", help="skip the fp32 / fake-quant GPU denominators")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline numbers, also measure everything else: roofline and per-class kernel times, box probe, "
+                         "GPU denominators, CPU baseline, other batches / precisions / configurations (off: the headline line only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-denominators", action="store_true", help="(--full) skip the fp32 / fake-quant GPU denominators")
     ap.add_argument("--decode", action="store_true", help="also time the first-stage decode of the image batch, all three engines, "
-                    "each in its own child process (sd / ldm / churches; extra field)")
+                    "each in its own child process (sd / ldm / churches; extra field); implies --full")
     ap.add_argument("--decode-leg", default=None, choices=sorted(DECODE_LEGS), help="(child mode) time ONE decode engine and print its JSON line")
-    ap.add_argument("--no-extras", action="store_true", help="skip the cifar / ldm / first-stage-decode child runs of the default SD line")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the fp16-stream, batch-5, cifar / ldm / first-stage-decode "
+                    "runs of the SD line")
     ap.add_argument("--stream", default=None, choices=["fp32", "fp16"],
                     help="storage type of the inter-kernel activations (default: QDIFF_STREAM or fp32); fp16 = the precision the "
                          "reference scripts run at (--precision autocast); compute stays int8 MFMA / fp32 epilogues")
-    ap.add_argument("--extra-batch", type=int, default=0, help="also time the same loop at this (smaller) number of images per GPU; extra key of config")
+    ap.add_argument("--extra-batch", type=int, default=0, help="also time the same loop at this (smaller) number of images per GPU; extra key of "
+                    "config; implies --full")
     ap.add_argument("--as-script", action="store_true",
                     help="(child mode) SD driven exactly as the reference's unmodified PLMS sampler drives it: fresh torch.cat of x / t / context "
                          "per step, no enable_hip_graphs / prepare_context calls; prints its own JSON line")
@@ -603,6 +616,7 @@ def main():
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    a.full = a.full or a.decode or a.extra_batch > 0
     if a.gpus is None:                                  # `torchrun --nproc-per-node N bench.py` without --gpus: N ranks
         a.gpus = int(os.environ.get("WORLD_SIZE", "1"))
 
@@ -668,7 +682,7 @@ def main():
     stream_name = "fp16" if engine.STREAM_DTYPE == torch.float16 else "fp32"
 
     kind, n = a.model, a.images_per_gpu
-    if kind == "sd" and not a.no_extras and a.extra_batch == 0 and n > 5:
+    if a.full and kind == "sd" and not a.no_extras and a.extra_batch == 0 and n > 5:
         a.extra_batch = 5                              # BASELINE configs[3]: `--n_samples 5` (README.md:59-61) = evaluation batch 10, next to the headline
     # rank 0 owns the calibrated model (synthetic here: data-dependent init + AdaRound conversion); every other rank
     # builds the bare architecture with unrelated weights and receives the packed state — the ONLY collective of the run
@@ -804,7 +818,7 @@ def main():
     }
     if dumped is not None:
         out["dump_outputs"] = dumped
-    if kind == "cifar" and rank == 0:
+    if a.full and kind == "cifar" and rank == 0:
         # BASELINE configs[1] as a whole-sampler-step graph (generalized_steps captured like DevicePLMS): the pixel-space UNet
         # is launch-latency-bound (~0.04 of the MFMA peak), so the per-step host work a graph of the evaluation alone leaves
         # is visible; extra key, the headline above stays the evaluation-graph number
@@ -822,7 +836,7 @@ def main():
         ws_ms = 1000.0 * (time.perf_counter() - t0) / a.steps
         out["config"]["whole_step_graph_ms"] = round(ws_ms, 4)
         out["config"]["whole_step_graph_images_per_s"] = round(gb / (evals * ws_ms / 1000.0), 3)
-    if rank == 0:
+    if rank == 0 and a.full:
         # ---- roofline of the dominant kernel class (live HIP events, eager launches) ----------------
         xb = state["x"]
         tb = torch.full((xb.shape[0],), 500, device=dev, dtype=torch.long)
@@ -965,6 +979,7 @@ def main():
                     engine.set_stream_dtype(torch.float32)
             other.update(extra_lines(a))
             out["other_configs"] = other
+    if rank == 0:
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

@@ -3,13 +3,13 @@
 tag="$1"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/$tag; mkdir -p $out
-timeout 600 python bench.py > $out/bench.json 2> $out/bench.err
+timeout 600 python bench.py --full > $out/bench.json 2> $out/bench.err
 tail -1 $out/bench.json
-CMD="python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-graph"
+CMD="python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-graph"
 rocprofv3 --kernel-trace -d $out -o kt -- $CMD > $out/kt.log 2>&1
 python tools/rocpd_stats.py $out/kt_results.db --md > $out/kernel_stats.md
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out -o pmc_$c -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-graph > $out/pmc_$c.log 2>&1
+  rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out -o pmc_$c -- python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-graph > $out/pmc_$c.log 2>&1
 done
 python - $out <<'PY'
 import csv, sys, glob, collections, json
