@@ -474,6 +474,27 @@ int qd_conv2d_wq_h16(const qd_conv_desc* d, int act_dtype, void* stream);
 int qd_rows_to_h16(const void* x, int x_dtype, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc, int64_t ss,
                    int c0, int clen, int clen_pad, void* out, int out_dtype, int64_t ldo, int oc0, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Weights-only attention (state (weight_quant, act_quant) = (True, False))
+ *
+ *     qd_attn_h16: out = softmax(q k^T * scale) v per (b, h), one fused sweep (online softmax, the T x S score matrix is never
+ *         written).  Replaces the floating-point attention of reference qdiff/quant_block.py:190-221 (use_act_quant False:
+ *         einsum, * scale, softmax, einsum) and the legacy attention ldm/modules/diffusionmodules/openaimodel.py:373-406.
+ *         q          logical [B][T][H][d], k and v [B][S][H][d], all of type in_dtype (QD_F32 / QD_F16 / QD_BF16), addressed by
+ *                    element strides (sb, s_token, sh, sd); sd must be 1 and every run of 8 channels 16-byte aligned
+ *                    (16-byte aligned bases, the other strides multiples of 16 bytes' worth of elements).  Values are rounded
+ *                    to op_dtype (QD_F16 / QD_BF16, nearest even) when a tile is staged.
+ *         d          a multiple of 8 in [8, 160]; any T >= 1, S >= 1; no mask.  scale > 0.
+ *         out        merged-head rows out[b*T + t][h*d + c], out_dtype QD_F32 or QD_F16, row stride ldo (>= H*d, a multiple
+ *                    of 4 elements, out aligned to 4 elements).
+ *         Scores accumulate in fp32 (v_mfma_f32_32x32x16_{f16,bf16}), the softmax runs in fp32 (exp2 with scale*log2 e
+ *         folded in), P is rounded to op_dtype for the P.V product.
+ * ------------------------------------------------------------------------------------------ */
+int qd_attn_h16(const void* q, const void* k, const void* v, int in_dtype, int B, int T, int S, int H, int d,
+                int64_t qsb, int64_t qst, int64_t qsh, int64_t qsd, int64_t ksb, int64_t kst, int64_t ksh, int64_t ksd,
+                int64_t vsb, int64_t vst, int64_t vsh, int64_t vsd, float scale, int op_dtype, void* out, int out_dtype,
+                int64_t ldo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -572,6 +572,71 @@ def wonly_forward(plan, xh, B, H, W, Ho, Wo, out_dtype=torch.float32, residual=N
 
 
 # ------------------------------------------------------------------------------------------------
+# weights-only attention: softmax(q k^T * scale) v of the (True, False) state in one fused kernel (qd_attn_h16)
+# ------------------------------------------------------------------------------------------------
+def _parse_weight_only_attn(v):
+    try:
+        return _parse_weight_only(v)
+    except ValueError:
+        raise ValueError(f"QDIFF_WEIGHT_ONLY_ATTN={v!r}: expected fp16, bf16 or off") from None
+
+
+# Weights-only attention: None (default) = the attention of a weights-only block runs the reference's fp32 library passes
+# (einsum, * scale, softmax, einsum); torch.float16 / torch.bfloat16 = it runs qd_attn_h16 with operands of that type (a
+# precision choice against the reference's fp32, hence a knob of its own, independent of WEIGHT_ONLY_KERNEL).
+# QDIFF_WEIGHT_ONLY_ATTN=fp16|bf16, or engine.set_weight_only_attention().
+WEIGHT_ONLY_ATTN = _parse_weight_only_attn(os.environ.get("QDIFF_WEIGHT_ONLY_ATTN"))
+
+# qd_attn_h16 launches issued by attention_h16 (tests read it to see that the kernel ran)
+ATTN_H16_LAUNCHES = 0
+
+# head dims the kernel takes
+WONLY_ATTN_DMIN, WONLY_ATTN_DMAX = 8, 160
+
+
+def set_weight_only_attention(dtype):
+    """None, torch.float16 or torch.bfloat16 (or the strings QDIFF_WEIGHT_ONLY_ATTN accepts)."""
+    global WEIGHT_ONLY_ATTN
+    if isinstance(dtype, str):
+        dtype = _parse_weight_only_attn(dtype)
+    if dtype not in (None, torch.float16, torch.bfloat16):
+        raise ValueError("weight-only attention dtype must be None, torch.float16 or torch.bfloat16")
+    WEIGHT_ONLY_ATTN = dtype
+
+
+def wonly_attn_shape_ok(d):
+    """qd_attn_h16 covers head dims that are multiples of 8 in [8, 160] (any token counts)."""
+    return d % 8 == 0 and WONLY_ATTN_DMIN <= d <= WONLY_ATTN_DMAX
+
+
+def _attn_h16_operand(x, B, N, H, d, strides, dtype):
+    """(tensor, strides) that qd_attn_h16 can read for the logical [B][N][H][d] view of x: x itself when its channel stride is 1
+    and every run of 8 channels is 16-byte aligned, else a contiguous copy of that view (in `dtype`)."""
+    sb, st, sh, sd = strides
+    m = 4 if dtype == torch.float32 else 8
+    if x.dtype == dtype and sd == 1 and x.data_ptr() % 16 == 0 and sb % m == 0 and st % m == 0 and sh % m == 0:
+        return x, strides
+    y = torch.as_strided(x, (B, N, H, d), strides).to(dtype).contiguous()
+    return y, y.stride()
+
+
+def attention_h16(q, k, v, B, T, S, H, d, q_strides, k_strides, v_strides, scale, out_dtype=torch.float32):
+    """softmax(q k^T * scale) v with engine.WEIGHT_ONLY_ATTN operands (qd_attn_h16).  q: logical [B][T][H][d], k, v: [B][S][H][d]
+    addressed by element strides (sb, s_token, sh, sd).  Returns merged-head rows [B*T][H*d] of out_dtype (fp32 / fp16)."""
+    global ATTN_H16_LAUNCHES
+    op = WEIGHT_ONLY_ATTN or torch.float16
+    dt = q.dtype if (q.dtype in (torch.float32, torch.float16, torch.bfloat16) and k.dtype == q.dtype and v.dtype == q.dtype) \
+        else torch.float32
+    q, q_strides = _attn_h16_operand(q, B, T, H, d, q_strides, dt)
+    k, k_strides = _attn_h16_operand(k, B, S, H, d, k_strides, dt)
+    v, v_strides = _attn_h16_operand(v, B, S, H, d, v_strides, dt)
+    out = torch.empty((B * T, H * d), dtype=out_dtype, device=q.device)
+    hip.attn_h16(q, k, v, B, T, S, H, d, q_strides, k_strides, v_strides, scale, op, out)
+    ATTN_H16_LAUNCHES += 1
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # producers (K5, K9)
 # ------------------------------------------------------------------------------------------------
 _ws_cache = {}

@@ -67,7 +67,8 @@ EXPORTS = ["qd_abi_version", "qd_last_error", "qd_device_ok", "qd_box_probe", "q
            "qd_geglu_quant", "qd_quantize_heads", "qd_attn_i8", "qd_attn_keyterm", "qd_attn_uses_keyterm", "qd_attn_config", "qd_attn_ws_bytes", "qd_bmm_qk_i8", "qd_bmm_pv_i8", "qd_temb_mlp",
            "qd_fakequant_blocks", "qd_fakequant_fwd", "qd_fakequant_bwd",
            "qd_conv2d_bf16", "qd_pack_weights_bf16_bytes", "qd_pack_weights_bf16", "qd_groupnorm_silu_bf16",
-           "qd_pack_weights_h16", "qd_groupnorm_silu_h16", "qd_conv2d_wq_h16", "qd_rows_to_h16"]
+           "qd_pack_weights_h16", "qd_groupnorm_silu_h16", "qd_conv2d_wq_h16", "qd_rows_to_h16",
+           "qd_attn_h16"]
 
 _lib = None
 
@@ -129,6 +130,7 @@ def load():
     lib.qd_groupnorm_silu_h16.argtypes = [vp, i64, i64, i32, i64, i32, f32, vp, vp, i32, i32, vp, i64, vp, vp, i32, i64, vp]
     lib.qd_conv2d_wq_h16.argtypes = [ctypes.POINTER(ConvDesc), i32, vp]
     lib.qd_rows_to_h16.argtypes = [vp, i32, i64, i64, i64, i64, i64, i64, i32, i32, i32, vp, i32, i64, i32, vp]
+    lib.qd_attn_h16.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32] + [i64] * 12 + [f32, i32, vp, i32, i64, vp]
     lib.qd_box_probe.argtypes = [i32, i32, i32, vp, vp, vp]
     lib.qd_attn_ws_bytes.argtypes = [i32, i32, i32, i32]
     lib.qd_attn_ws_bytes.restype = ctypes.c_int64
@@ -390,6 +392,18 @@ def conv2d_wq_h16(c, act_dtype):
         raise HipEngineError("conv2d_wq_h16: activations must be float16 or bfloat16")
     d = _conv_desc(c)
     _check(load().qd_conv2d_wq_h16(ctypes.byref(d), _H16[act_dtype], _stream()), "qd_conv2d_wq_h16")
+
+
+def attn_h16(q, k, v, B, T, S, H, d, q_strides, k_strides, v_strides, scale, op_dtype, out):
+    """Fused fp16 / bf16 attention of the weights-only state (qd_attn_h16).  q: logical [B][T][H][d], k, v: [B][S][H][d], one
+    float dtype, element strides (sb, s_token, sh, sd) with sd == 1; out: fp32 / fp16 merged-head rows [B*T][>= H*d]."""
+    if op_dtype not in (torch.float16, torch.bfloat16):
+        raise HipEngineError("attn_h16: operands must be float16 or bfloat16")
+    if q.dtype not in _H16 or k.dtype != q.dtype or v.dtype != q.dtype or out.dtype not in (torch.float32, torch.float16):
+        raise HipEngineError(f"attn_h16: unsupported dtypes q {q.dtype} k {k.dtype} v {v.dtype} out {out.dtype}")
+    _check(load().qd_attn_h16(_ptr(q, "q"), _ptr(k, "k"), _ptr(v, "v"), _H16[q.dtype], B, T, S, H, d, *q_strides, *k_strides,
+                              *v_strides, float(scale), _H16[op_dtype], _ptr(out, "out"), _H16[out.dtype], out.stride(0), _stream()),
+           "qd_attn_h16")
 
 
 def groupnorm_silu_bf16(x, B, S, C, groups, eps, gamma, beta, silu, out, ws, part=None):

@@ -11,6 +11,7 @@ Each block has two forwards:
     q/k/softmax/v quantisation + both attention contractions are one fused kernel (K7/K8).
 """
 import logging
+import math
 import os
 from types import MethodType
 
@@ -126,6 +127,25 @@ def _dropout_live(block):
 def _aq_ready(*quantizers):
     """Initialised and not in EMA range-tracking mode (a tracking quantiser must see its float input: simulation path)."""
     return all(q.inited and not q.running_stat for q in quantizers)
+
+
+def _wonly_proj(m):
+    """A projection in the weights-only state: weights quantised, activations not (QuantModule._wonly_state without the layer
+    knob, which is independent of the attention knob)."""
+    return (isinstance(m, QuantModule) and m.use_weight_quant
+            and not (m.use_act_quant and not m.disable_act_quant and m.act_quant_mode == 'qdiff'))
+
+
+def _wonly_attn_gate(projections, tensors, d):
+    """The fused weights-only attention (engine.attention_h16) takes this call: the knob is set, no simulation, no autograd,
+    GPU tensors, a head dim the kernel covers, and every projection of the attention in the state (True, False).  Anything
+    else keeps the library path unchanged — (False, False) in particular, where calibration takes its fp targets."""
+    return (engine.WEIGHT_ONLY_ATTN is not None and not engine.SIMULATE and not torch.is_grad_enabled()
+            and all(engine.wonly_device_ok(t) for t in tensors) and engine.wonly_attn_shape_ok(d) and all(_wonly_proj(m) for m in projections))
+
+
+def _no_hooks(*modules):
+    return all(not m._forward_hooks and not m._forward_pre_hooks for m in modules)
 
 
 def _gn_silu_to(conv, rows, B, S, C, gn, silu=True, raw_plan=None, mod=None):
@@ -812,8 +832,50 @@ class QuantAttentionBlock(BaseQuantBlock, _AttnQuant):
                 return self._forward_heads(x, plans, out_slot)
             return self._forward_int(x, out_slot)
         xf = x.reshape(b, c, -1)
-        h = self.proj_out(self.attention(self.qkv(self.norm(xf))))
+        qkv = self.qkv(self.norm(xf))
+        if self._wonly_attention_ok(qkv):
+            h = self.proj_out(self._attention_h16(qkv))
+        else:
+            h = self.proj_out(self.attention(qkv))
         return (xf + h).reshape(b, c, *spatial)
+
+    def _wonly_attention_ok(self, qkv):
+        """engine.attention_h16 replaces self.attention(qkv): the repo's (or the reference's) QKVAttentionLegacy whose two
+        matmuls compute in floating point — QKMatMul / SMVMatMul, or their Quant* counterparts with activation quantisation off
+        (the same einsums) — no hooks on any of the three, a qkv layout of whole heads, and the weights-only gate."""
+        att = self.attention
+        qk, smv = getattr(att, "qkv_matmul", None), getattr(att, "smv_matmul", None)
+        plain_qk = type(qk).__name__ == "QKMatMul" or (isinstance(qk, QuantQKMatMul) and not qk.use_act_quant)
+        plain_smv = type(smv).__name__ == "SMVMatMul" or (isinstance(smv, QuantSMVMatMul) and not smv.use_act_quant)
+        if (self.use_act_quant or type(att).__name__ != "QKVAttentionLegacy" or not plain_qk or not plain_smv
+                or not _no_hooks(att, qk, smv)):
+            return False
+        if qkv.dim() != 3 or qkv.shape[1] % (3 * att.n_heads) != 0:
+            return False
+        ch = qkv.shape[1] // (3 * att.n_heads)
+        if qk.scale is not None and qk.scale != 1 / math.sqrt(math.sqrt(ch)):
+            return False                               # the library path asserts on it
+        return _wonly_attn_gate((self.qkv, self.proj_out), (qkv,), ch)
+
+    def _attention_h16(self, qkv):
+        """QKVAttentionLegacy.forward on the fused kernel: channel = head*3d + {q,k,v}*d + i of qkv [B, 3C, T], read by strides
+        (the layer kernel's channels-last rows as they are; a library output [B, 3C, T] is made channels-last once).
+        Returns the [B, C, T] view of the merged-head rows that proj_out receives from the library path."""
+        att = self.attention
+        B, width, T = qkv.shape
+        nh = att.n_heads
+        ch = width // (3 * nh)
+        if att.qkv_matmul.scale is None:
+            att.qkv_matmul.scale = 1 / math.sqrt(math.sqrt(ch))        # what QKVAttentionLegacy.forward leaves behind
+        if qkv.stride(1) != 1:
+            qkv = qkv.transpose(1, 2).contiguous().transpose(1, 2)
+        sb, sc, st = qkv.stride()
+        strides = (sb, st, 3 * ch * sc, sc)
+        out_dtype, cast = engine.wonly_out_dtype(qkv.device.type)
+        rows = engine.attention_h16(qkv, qkv[:, ch:], qkv[:, 2 * ch:], B, T, T, nh, ch, strides, strides, strides,
+                                    ch ** -0.5, out_dtype)
+        y = rows.view(B, T, nh * ch).permute(0, 2, 1)
+        return y if cast is None else y.to(cast)
 
     def _forward_int(self, x, out_slot=None):
         B, C, H, W = x.shape
@@ -881,6 +943,15 @@ def cross_attn_forward(self, x, context=None, mask=None):
     h = self.heads
     context = x if context is None else context
     q, k, v = self.to_q(x), self.to_k(context), self.to_v(context)
+    if (not self.use_act_quant and mask is None and q.dim() == 3 and k.dim() == 3 and q.shape[-1] % h == 0
+            and _wonly_attn_gate((self.to_q, self.to_k, self.to_v, self.to_out[0]), (q, k, v), q.shape[-1] // h)):
+        # weights-only state: q / k / v by strides into the fused kernel, merged-head rows [B, T, H*d] into to_out
+        B, T, C = q.shape
+        S, d = k.shape[1], C // h
+        out_dtype, cast = engine.wonly_out_dtype(q.device.type)
+        st = lambda t: (t.stride(0), t.stride(1), d * t.stride(2), t.stride(2))
+        rows = engine.attention_h16(q, k, v, B, T, S, h, d, st(q), st(k), st(v), self.scale, out_dtype).view(B, T, C)
+        return self.to_out(rows if cast is None else rows.to(cast))
     q, k, v = (ldm_unet._split_heads(t, h) for t in (q, k, v))
     if self.use_act_quant:
         q, k = self.act_quantizer_q(q), self.act_quantizer_k(k)

@@ -5,6 +5,15 @@ class alone under HIP events and its share of the ~2.5 PF dense fp16 MFMA rate. 
 bench.py (SD-v1.4 at batch 16 by default).  One JSON line per model.
 
     python tools/bench_weight_only.py [--models sd,ldm,cifar] [--batch 16] [--evals 3]
+
+--attn adds the attention-knob column (engine.WEIGHT_ONLY_ATTN, qd_attn_h16) with the layer kernel at fp16: evaluation time
+with the fused attention off and on (alternated A/B in one process), the attention class (HIP events around every
+engine.attention_h16 call; with the knob off, the library's fp32 attention core — einsum, * scale, softmax, einsum — timed in
+isolation at the shapes the evaluation hits), torch.cuda.max_memory_allocated of one evaluation, and --attn-shapes a per-shape
+table at SD's shapes (kernel us, TFLOP/s, share of the fp16 peak at 4*BH*T*S*d FLOP, F.scaled_dot_product_attention in fp16
+and the library core in fp32 as yardsticks).
+
+    python tools/bench_weight_only.py --attn [--models sd,ldm,churches] [--attn-shapes]
 """
 import argparse
 import json
@@ -83,18 +92,140 @@ def run(kind, batch, k, dev):
     return res
 
 
+def _events_ms(fn, k=10):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    with torch.no_grad():
+        fn()
+        torch.cuda.synchronize()
+        a.record()
+        for _ in range(k):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+    return a.elapsed_time(b) / k
+
+
+def _library_core(BH, T, S, d, dev):
+    """The reference's fp32 attention core at one shape (cross_attn_forward's einsum, * scale, softmax, einsum)."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    q, k, v = (torch.randn(BH, n, d, device=dev, generator=g) for n in (T, S, S))
+    scale = d ** -0.5
+
+    def core():
+        sim = torch.einsum("b i d, b j d -> b i j", q, k) * scale
+        return torch.einsum("b i j, b j d -> b i d", sim.softmax(dim=-1), v)
+    return core
+
+
+def _attention_class(one):
+    """(ms, launches, shapes) of the engine.attention_h16 calls of one evaluation, each bracketed by HIP events."""
+    from qdiff import engine
+    orig, marks = engine.attention_h16, []
+
+    def timed(q, k, v, B, T, S, H, d, *rest, **kw):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = orig(q, k, v, B, T, S, H, d, *rest, **kw)
+        b.record()
+        marks.append((a, b, (B * H, T, S, d)))
+        return out
+    engine.attention_h16 = timed
+    try:
+        with torch.no_grad():
+            one()
+        torch.cuda.synchronize()
+    finally:
+        engine.attention_h16 = orig
+    return sum(a.elapsed_time(b) for a, b, _ in marks), len(marks), [s for _, _, s in marks]
+
+
+def run_attn(kind, batch, k, dev):
+    import bench
+    from qdiff import engine, synthetic
+    qnn, _ = bench.build_quantised_unet(kind, dev)
+    x, t, c = synthetic.synthetic_inputs(kind, batch, seed=0)
+    args = [a.to(dev) for a in (x, t, c) if a is not None]
+    qnn.set_quant_state(True, False)
+    one = lambda: qnn(*args)
+    res = {"model": kind, "batch": batch, "layer_knob": "fp16", "evals_timed": k}
+    prev_k, prev_a = engine.WEIGHT_ONLY_KERNEL, engine.WEIGHT_ONLY_ATTN
+    try:
+        engine.set_weight_only_kernel(torch.float16)
+        off, on = [], []
+        for _ in range(3):                                       # alternated A/B
+            engine.set_weight_only_attention(None)
+            off.append(_timed(one, k))
+            engine.set_weight_only_attention(torch.float16)
+            on.append(_timed(one, k))
+        res["attn_off_ms"], res["attn_on_ms"] = round(min(off), 3), round(min(on), 3)
+        res["attn_off_ms_all"], res["attn_on_ms_all"] = [round(v, 3) for v in off], [round(v, 3) for v in on]
+        ms, n, shapes = _attention_class(one)
+        res["attn_on_class_ms"], res["attn_launches"] = round(ms, 3), n
+        lib = sum(_events_ms(_library_core(BH, T, S, d, dev), 3) for BH, T, S, d in shapes)
+        res["attn_off_class_ms"] = round(lib, 3)
+        res["attn_off_class_share"] = round(lib / res["attn_off_ms"], 3)
+        for name, dt in (("off", None), ("on", torch.float16)):
+            engine.set_weight_only_attention(dt)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats(dev)
+            with torch.no_grad():
+                one()
+            torch.cuda.synchronize()
+            res[f"attn_{name}_max_mem_mib"] = round(torch.cuda.max_memory_allocated(dev) / 2 ** 20, 1)
+        res["shapes"] = sorted(set(shapes))
+    finally:
+        engine.set_weight_only_kernel(prev_k)
+        engine.set_weight_only_attention(prev_a)
+    return res
+
+
+# SD-v1.4 at batch 16 (B*H = 128): self-attention at the four latent levels, cross-attention over 77 tokens
+SD_SHAPES = [(128, 4096, 4096, 40), (128, 1024, 1024, 80), (128, 256, 256, 160), (128, 64, 64, 160),
+             (128, 4096, 77, 40), (128, 1024, 77, 80), (128, 256, 77, 160), (128, 64, 77, 160)]
+# the LDM-4 (LSUN-Bedrooms) and LDM-8 (LSUN-Churches) attention shapes at batch 16
+LDM_SHAPES = [(224, 1024, 1024, 32), (336, 256, 256, 32), (448, 64, 64, 32),
+              (128, 1024, 1024, 24), (128, 256, 256, 48), (128, 64, 64, 48), (128, 16, 16, 96), (128, 4, 4, 96)]
+
+
+def attn_shape_table(dev, shapes=SD_SHAPES):
+    import torch.nn.functional as F
+    from qdiff import engine
+    prev = engine.WEIGHT_ONLY_ATTN
+    engine.set_weight_only_attention(torch.float16)
+    g = torch.Generator(device=dev).manual_seed(0)
+    try:
+        for BH, T, S, d in shapes:
+            q, k, v = (torch.randn(1, n, BH, d, device=dev, generator=g) for n in (T, S, S))
+            st = lambda n: (n * BH * d, BH * d, d, 1)
+            us = 1000 * _events_ms(lambda: engine.attention_h16(q, k, v, 1, T, S, BH, d, st(T), st(S), st(S), d ** -0.5))
+            qh, kh, vh = (t.permute(0, 2, 1, 3).reshape(BH, -1, d).half().contiguous() for t in (q, k, v))
+            sdpa = 1000 * _events_ms(lambda: F.scaled_dot_product_attention(qh, kh, vh))
+            lib = 1000 * _events_ms(_library_core(BH, T, S, d, dev))
+            flop = 4.0 * BH * T * S * d
+            print(json.dumps({"BH": BH, "T": T, "S": S, "d": d, "kernel_us": round(us, 1),
+                              "tflops": round(flop / us / 1e6, 1), "frac_of_peak": round(flop / us / 1e6 / F16_MFMA_PEAK_TFLOPS, 4),
+                              "sdpa_fp16_us": round(sdpa, 1), "library_fp32_us": round(lib, 1),
+                              "speedup_vs_library": round(lib / us, 2)}), flush=True)
+    finally:
+        engine.set_weight_only_attention(prev)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="sd,ldm,cifar")
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--evals", type=int, default=3)
+    ap.add_argument("--attn", action="store_true", help="the attention-knob column (layer kernel at fp16)")
+    ap.add_argument("--attn-shapes", action="store_true", help="the per-shape attention table at SD's shapes")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     from qdiff import hip
     hip.load()
     dev = torch.device("cuda:0")
+    if a.attn_shapes:
+        attn_shape_table(dev, SD_SHAPES + LDM_SHAPES)
     for kind in a.models.split(","):
-        print(json.dumps(run(kind, a.batch, a.evals, dev)), flush=True)
+        print(json.dumps((run_attn if a.attn else run)(kind, a.batch, a.evals, dev)), flush=True)
         torch.cuda.empty_cache()
 
 
