@@ -461,8 +461,11 @@ int qd_groupnorm_silu_h16(const float* x, int64_t B, int64_t S, int C, int64_t l
  *                    in [-128, 255] (not zw - 128);  seg.zc / zfill / fill16 must be NULL
  *         nseg 1 or 2 (split shortcut, quant_layer.py:257-269: each segment its own delta / z), epilogue = QD_EPI_LINEAR,
  *         out_dtype QD_F32 or QD_F16 (the residual has the type of the output), kh/kw/stride/pad_t/pad_l as for
- *         qd_conv2d_i8; out-of-image taps, K tails and M tails read zeros.  rowbias, gn_part, upsample2x must be unset;
+ *         qd_conv2d_i8; out-of-image taps, K tails and M tails read zeros.  gn_part, upsample2x must be unset;
  *         split-K, oq_* / hd_* are ignored.
+ *         rowbias    optional fp32 [B][ld_rowbias] (ld_rowbias >= Cout): row b is added to every output row of sample b
+ *                    after the bias and before the residual, as in qd_conv2d_i8 (the timestep-embedding add
+ *                    `h + emb_out` of qdiff/quant_block.py:92-98).  NULL leaves the output bytes as they were.
  *         bf16 operands carry q - z exactly only while |q - z| <= 256 for every stored code: the caller checks (8-bit
  *         codes with z < -1 can exceed it); fp16 is exact for every zero point in [-128, 255].
  *     qd_rows_to_h16: the producer of those rows.  x is a logical [B][C][S] fp32 / fp16 / bf16 tensor addressed by element
@@ -494,6 +497,31 @@ int qd_attn_h16(const void* q, const void* k, const void* v, int in_dtype, int B
                 int64_t qsb, int64_t qst, int64_t qsh, int64_t qsd, int64_t ksb, int64_t kst, int64_t ksh, int64_t ksd,
                 int64_t vsb, int64_t vst, int64_t vsh, int64_t vsd, float scale, int op_dtype, void* out, int out_dtype,
                 int64_t ldo, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Weights-only producers (additive in ABI 20): the floating-point glue between the kernels of a
+ *     weights-only block written straight as the fp16 / bf16 operand rows [M][ldo] that qd_conv2d_wq_h16 reads.  Input rows
+ *     are fp32 or fp16 (x_dtype QD_F32 / QD_F16), 16-byte aligned with a row stride of a multiple of 16 bytes; arithmetic is
+ *     fp32; the result is rounded ONCE (nearest even) to out_dtype (QD_F16 / QD_BF16); channels [C, ldo) of every row are
+ *     written as zeros; ldo is a multiple of 8 and out is 16-byte aligned.  Rows outside [0, M) are not touched.
+ *
+ *     qd_layernorm_h16: nn.LayerNorm over the last axis of rows [M][C] (ldm/modules/attention.py:229-231, norm1 / norm2 /
+ *         norm3 of BasicTransformerBlock) -> ONE row buffer, shared by every consumer (to_q / to_k / to_v): there is no
+ *         per-consumer quantiser in this state.  C a multiple of 8, at most 2048; gamma / beta fp32, 16-byte aligned.
+ *     qd_geglu_h16: h[:, :F] * gelu(h[:, F:2F]) with the erf GELU (attention.py:37-44 GEGLU.forward) of rows [M][ldh >= 2F]
+ *         -> the operand rows of the feed-forward output Linear.  F a multiple of 8.
+ *     qd_groupnorm_h16: GroupNorm (+ SiLU when apply_silu) of channels-last rows [B*S][C] -> operand rows: `in_layers` /
+ *         `out_layers` norm + SiLU of ResBlock (ldm/modules/diffusionmodules/openaimodel.py:201-232, qdiff/quant_block.py:
+ *         83-111); apply_silu = 0 is the plain Normalize in front of an attention block or a SpatialTransformer's proj_in.
+ *         gamma / beta may be NULL.  C a multiple of 8 and of groups.  ws: qd_groupnorm_ws_bytes(B, C, S) bytes.
+ * ------------------------------------------------------------------------------------------ */
+int qd_layernorm_h16(const void* x, int x_dtype, int64_t M, int C, int64_t ldx, float eps, const float* gamma,
+                     const float* beta, void* out, int out_dtype, int64_t ldo, void* stream);
+int qd_geglu_h16(const void* h, int h_dtype, int64_t M, int F, int64_t ldh, void* out, int out_dtype, int64_t ldo,
+                 void* stream);
+int qd_groupnorm_h16(const void* x, int x_dtype, int64_t B, int64_t S, int C, int64_t ldx, int groups, float eps,
+                     const float* gamma, const float* beta, int apply_silu, void* out, int out_dtype, int64_t ldo,
+                     void* ws, void* stream);
 
 #ifdef __cplusplus
 }

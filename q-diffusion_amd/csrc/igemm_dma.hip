@@ -1901,7 +1901,8 @@ struct WqD {
     void* out;
     const void* residual;
     const float* bias;
-    long ldx, ldo, ldr;
+    const float* rowbias;                 // [B][ldrb] fp32, one row per sample (the timestep-embedding projection), or NULL
+    long ldx, ldo, ldr, ldrb;
     int H, W, Ho, Wo, Cout, kw, stride, pad_t, pad_l, taps;
     int M, nseg, ntiles, nblk_n;
     WqSeg seg[2];
@@ -2125,6 +2126,7 @@ __global__ __launch_bounds__(256, 2) void wq_h16_kernel(const WqD p) {
                 const long m = m0 + wm * 64 + i * 32 + crow(r) + 4 * fhalf;
                 if (m >= p.M) continue;
                 float v = __builtin_fmaf(acc[i][j][r], d, SPLIT ? facc[SPLIT ? i : 0][SPLIT ? j : 0][r] : 0.f) + bias;
+                if (p.rowbias) v += p.rowbias[((int)m / HoWo) * p.ldrb + n];
                 if constexpr (OUT == O_F32) {
                     if (p.residual) v += reinterpret_cast<const float*>(p.residual)[m * p.ldr + n];
                     reinterpret_cast<float*>(p.out)[m * p.ldo + n] = v;
@@ -2174,8 +2176,9 @@ int run_wq_h16(const qd_conv_desc* d, int act_dtype, void* stream) {
     QD_REQUIRE(d->w_tiled && (d->wbits == 4 || d->wbits == 8), "qd_conv2d_wq_h16: weights must be tile-ordered codes of qd_pack_weights_t4 / _t8 (w_tiled = 1, wbits 4 / 8)");
     QD_REQUIRE(d->out_dtype == QD_F32 || d->out_dtype == QD_F16, "qd_conv2d_wq_h16: out_dtype must be f32/f16");
     QD_REQUIRE(d->nseg == 1 || d->nseg == 2, "qd_conv2d_wq_h16: nseg must be 1 or 2");
-    QD_REQUIRE(d->epilogue == QD_EPI_LINEAR && !d->rowbias && !d->gn_part && !d->upsample2x,
-               "qd_conv2d_wq_h16: linear epilogue only (no row bias, GroupNorm statistics or up-sampling)");
+    QD_REQUIRE(d->epilogue == QD_EPI_LINEAR && !d->gn_part && !d->upsample2x,
+               "qd_conv2d_wq_h16: linear epilogue only (no GroupNorm statistics or up-sampling)");
+    QD_REQUIRE(!d->rowbias || d->ld_rowbias >= d->Cout, "qd_conv2d_wq_h16: ld_rowbias shorter than Cout");
     QD_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0 && d->Cout > 0, "qd_conv2d_wq_h16: bad shape");
     QD_REQUIRE(d->kh > 0 && d->kw > 0 && d->stride > 0 && d->kh * d->kw <= 32, "qd_conv2d_wq_h16: bad kernel/stride (at most 32 taps)");
     QD_REQUIRE(d->pad_t >= 0 && d->pad_l >= 0 && d->pad_t < 64 && d->pad_l < 64, "qd_conv2d_wq_h16: bad padding");
@@ -2184,6 +2187,7 @@ int run_wq_h16(const qd_conv_desc* d, int act_dtype, void* stream) {
     QD_REQUIRE(d->ldo >= d->Cout && (!d->residual || d->ldr >= d->Cout), "qd_conv2d_wq_h16: ldo / ldr shorter than Cout");
     WqD k{};
     k.x = reinterpret_cast<const unsigned short*>(d->x); k.wt = d->w; k.out = d->out; k.residual = d->residual; k.bias = d->bias;
+    k.rowbias = d->rowbias; k.ldrb = d->ld_rowbias;
     k.ldx = d->ldx; k.ldo = d->ldo; k.ldr = d->ldr;
     k.H = d->H; k.W = d->W; k.Ho = d->Ho; k.Wo = d->Wo; k.Cout = d->Cout;
     k.kw = d->kw; k.stride = d->stride; k.pad_t = d->pad_t; k.pad_l = d->pad_l; k.taps = d->kh * d->kw;

@@ -871,3 +871,249 @@ extern "C" int qd_layernorm_quant(const void* x, int x_dtype, int64_t M, int C, 
     QD_LAUNCH_CHECK("qd_layernorm_quant");
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Weights-only producers (state (weight_quant, act_quant) = (True, False)): LayerNorm, GroupNorm(+SiLU)
+// and GEGLU written straight as the fp16 / bf16 operand rows [M][ldo] of qd_conv2d_wq_h16 — no fp32 intermediate and no
+// qd_rows_to_h16 pass.  HBM-bound streams: a lane owns 8 consecutive channels (16-byte stores; fp16 input one 16-byte load,
+// fp32 input two), fp32 arithmetic, ONE round-to-nearest-even at the store, pad channels [C, ldo) written as zeros.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+template <typename T>
+__device__ __forceinline__ void h16_ld8(const T* p, float (&v)[8]) {
+    if constexpr (sizeof(T) == 4) {
+        const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    } else {
+        qd_ld8h(p, v);
+    }
+}
+__device__ __forceinline__ v4i h16_pack8(const float (&y)[8], int fh) {
+    v4i pk;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pk[j] = fh ? (int)qd_pack2h(y[2 * j], y[2 * j + 1]) : (int)qd_pack2bf(y[2 * j], y[2 * j + 1]);
+    return pk;
+}
+
+// LayerNorm: a wave owns RPW rows at a time (their loads and reduction chains interleave, as in ln_quant_kernel), lane =
+// 8-channel chunks lane + 64 k (k < NV); mean, then the centred sum of squares, both from registers.  Grid-stride over rows.
+template <typename T, int NV, int RPW>
+__global__ __launch_bounds__(256) void ln_h16_kernel(const T* __restrict__ x, long M, int C, long ldx, float eps,
+                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                     unsigned short* __restrict__ out, long ldo, int fh) {
+    const int lane = threadIdx.x & 63;
+    const int nch = C >> 3, nout = (int)(ldo >> 3);
+    for (long row0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW; row0 < M; row0 += (long)gridDim.x * 4 * RPW) {
+        float v[RPW][NV][8];
+#pragma unroll
+        for (int r = 0; r < RPW; ++r) {
+            const long row = row0 + r < M ? row0 + r : M - 1;      // clamp: loads stay in bounds, stores are predicated
+#pragma unroll
+            for (int k = 0; k < NV; ++k)
+                if (lane + 64 * k < nch) h16_ld8(x + row * ldx + (lane + 64 * k) * 8, v[r][k]);
+        }
+        float s[RPW], q[RPW];
+#pragma unroll
+        for (int r = 0; r < RPW; ++r) {
+            s[r] = 0.f;
+#pragma unroll
+            for (int k = 0; k < NV; ++k)
+                if (lane + 64 * k < nch) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) s[r] += v[r][k][j];
+                }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+            for (int r = 0; r < RPW; ++r) s[r] += __shfl_xor(s[r], o);
+        float mean[RPW];
+#pragma unroll
+        for (int r = 0; r < RPW; ++r) {
+            mean[r] = s[r] / (float)C;
+            q[r] = 0.f;
+#pragma unroll
+            for (int k = 0; k < NV; ++k)
+                if (lane + 64 * k < nch) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) { const float d = v[r][k][j] - mean[r]; q[r] += d * d; }
+                }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+            for (int r = 0; r < RPW; ++r) q[r] += __shfl_xor(q[r], o);
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+            const int c8 = lane + 64 * k;
+            if (c8 >= nch) continue;
+            float g[8], b[8];
+            h16_ld8(gamma + c8 * 8, g);
+            h16_ld8(beta + c8 * 8, b);
+#pragma unroll
+            for (int r = 0; r < RPW; ++r) {
+                if (row0 + r >= M) continue;
+                const float rstd = 1.0f / sqrtf(q[r] / (float)C + eps);
+                float y[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) y[j] = (v[r][k][j] - mean[r]) * rstd * g[j] + b[j];
+                *reinterpret_cast<v4i*>(out + (row0 + r) * ldo + c8 * 8) = h16_pack8(y, fh);
+            }
+        }
+        for (int c8 = nch + lane; c8 < nout; c8 += 64)
+#pragma unroll
+            for (int r = 0; r < RPW; ++r)
+                if (row0 + r < M) *reinterpret_cast<v4i*>(out + (row0 + r) * ldo + c8 * 8) = v4i{0, 0, 0, 0};
+    }
+}
+
+template <typename T, int NV>
+void launch_ln_h16(hipStream_t st, const void* x, long M, int C, long ldx, float eps, const float* gamma, const float* beta,
+                   unsigned short* out, long ldo, int fh) {
+    constexpr int RPW = 2;
+    const long nblk = (M + 4 * RPW - 1) / (4 * RPW);
+    hipLaunchKernelGGL((ln_h16_kernel<T, NV, RPW>), dim3((unsigned)(nblk < 4096 ? nblk : 4096)), dim3(256), 0, st, (const T*)x, M, C, ldx, eps,
+                       gamma, beta, out, ldo, fh);
+}
+
+template <typename T>
+void dispatch_ln_h16(hipStream_t st, const void* x, long M, int C, long ldx, float eps, const float* gamma, const float* beta,
+                     unsigned short* out, long ldo, int fh) {
+    switch ((C / 8 + 63) / 64) {
+        case 1:  launch_ln_h16<T, 1>(st, x, M, C, ldx, eps, gamma, beta, out, ldo, fh); break;
+        case 2:  launch_ln_h16<T, 2>(st, x, M, C, ldx, eps, gamma, beta, out, ldo, fh); break;
+        case 3:  launch_ln_h16<T, 3>(st, x, M, C, ldx, eps, gamma, beta, out, ldo, fh); break;
+        default: launch_ln_h16<T, 4>(st, x, M, C, ldx, eps, gamma, beta, out, ldo, fh); break;
+    }
+}
+
+// GEGLU: thread = (row, 8-channel chunk of the ldo-wide output row); value h[row][c], gate h[row][F + c].  The erf is
+// qd_erff (common.h, < 1 ulp), the operations are those of geglu_quant_kernel up to the store.  Grid-stride.
+template <typename T>
+__global__ __launch_bounds__(256) void geglu_h16_kernel(const T* __restrict__ h, long total, int F, long ldh,
+                                                        unsigned short* __restrict__ out, long ldo, int fh) {
+    const int nch = F >> 3, nout = (int)(ldo >> 3);
+    for (long gid = (long)blockIdx.x * 256 + threadIdx.x; gid < total; gid += (long)gridDim.x * 256) {
+        const long row = gid / nout;
+        const int c8 = (int)(gid - row * nout);
+        v4i pk = {0, 0, 0, 0};
+        if (c8 < nch) {
+            float a[8], g[8], y[8];
+            h16_ld8(h + row * ldh + c8 * 8, a);
+            h16_ld8(h + row * ldh + F + c8 * 8, g);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) y[j] = a[j] * (0.5f * g[j] * (1.0f + qd_erff(g[j] * 0.70710678118654752440f)));
+            pk = h16_pack8(y, fh);
+        }
+        *reinterpret_cast<v4i*>(out + row * ldo + c8 * 8) = pk;
+    }
+}
+
+// GroupNorm apply: thread = (row, 8-channel chunk of the output row), y = x * a + sh with the per-(sample, channel) affine of
+// gn_finalize_kernel, optional SiLU (the expression of gn_apply_bf16_kernel).  Grid-stride.
+template <typename T>
+__global__ __launch_bounds__(256) void gn_apply_h16_kernel(const T* __restrict__ x, long total, long S, int C, long ldx,
+                                                           const float* __restrict__ ab, int apply_silu,
+                                                           unsigned short* __restrict__ out, long ldo, int fh) {
+    const int nch = C >> 3, nout = (int)(ldo >> 3);
+    for (long gid = (long)blockIdx.x * 256 + threadIdx.x; gid < total; gid += (long)gridDim.x * 256) {
+        const long row = gid / nout;
+        const int c8 = (int)(gid - row * nout);
+        v4i pk = {0, 0, 0, 0};
+        if (c8 < nch) {
+            float v[8], y[8];
+            h16_ld8(x + row * ldx + c8 * 8, v);
+            const float* abp = ab + ((row / S) * C + c8 * 8) * 2;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float4 t = *reinterpret_cast<const float4*>(abp + 4 * j);
+                y[2 * j] = v[2 * j] * t.x + t.y;
+                y[2 * j + 1] = v[2 * j + 1] * t.z + t.w;
+            }
+            if (apply_silu) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) y[j] = y[j] * (1.0f / (1.0f + expf(-y[j])));
+            }
+            pk = h16_pack8(y, fh);
+        }
+        *reinterpret_cast<v4i*>(out + row * ldo + c8 * 8) = pk;
+    }
+}
+
+inline unsigned h16_stream_grid(long total) {
+    const long nblk = (total + 255) / 256;
+    return (unsigned)(nblk < 8192 ? nblk : 8192);
+}
+
+}  // namespace
+
+extern "C" int qd_layernorm_h16(const void* x, int x_dtype, int64_t M, int C, int64_t ldx, float eps, const float* gamma,
+                                const float* beta, void* out, int out_dtype, int64_t ldo, void* stream) {
+    QD_REQUIRE(x && gamma && beta && out, "qd_layernorm_h16: null pointer");
+    QD_REQUIRE(x_dtype == QD_F32 || x_dtype == QD_F16, "qd_layernorm_h16: x_dtype must be f32/f16");
+    QD_REQUIRE(out_dtype == QD_F16 || out_dtype == QD_BF16, "qd_layernorm_h16: out_dtype must be f16/bf16");
+    QD_REQUIRE(M > 0 && C > 0 && C % 8 == 0 && C <= 2048, "qd_layernorm_h16: C=%d unsupported (multiple of 8, <= 2048)", C);
+    QD_REQUIRE(ldx >= C && ldx % (x_dtype == QD_F32 ? 4 : 8) == 0 && qd_aligned(x, 16), "qd_layernorm_h16: input rows must be 16-byte aligned");
+    QD_REQUIRE(ldo >= C && ldo % 8 == 0 && qd_aligned(out, 16), "qd_layernorm_h16: output rows must be 16-byte aligned (ldo %% 8 == 0)");
+    QD_REQUIRE(qd_aligned(gamma, 16) && qd_aligned(beta, 16), "qd_layernorm_h16: gamma/beta must be 16-byte aligned");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int fh = out_dtype == QD_F16 ? 1 : 0;
+    if (x_dtype == QD_F32) dispatch_ln_h16<float>(st, x, (long)M, C, (long)ldx, eps, gamma, beta, reinterpret_cast<unsigned short*>(out), (long)ldo, fh);
+    else dispatch_ln_h16<__half>(st, x, (long)M, C, (long)ldx, eps, gamma, beta, reinterpret_cast<unsigned short*>(out), (long)ldo, fh);
+    QD_LAUNCH_CHECK("qd_layernorm_h16");
+    return 0;
+}
+
+extern "C" int qd_geglu_h16(const void* h, int h_dtype, int64_t M, int F, int64_t ldh, void* out, int out_dtype, int64_t ldo,
+                            void* stream) {
+    QD_REQUIRE(h && out, "qd_geglu_h16: null pointer");
+    QD_REQUIRE(h_dtype == QD_F32 || h_dtype == QD_F16, "qd_geglu_h16: h_dtype must be f32/f16");
+    QD_REQUIRE(out_dtype == QD_F16 || out_dtype == QD_BF16, "qd_geglu_h16: out_dtype must be f16/bf16");
+    QD_REQUIRE(M > 0 && F > 0 && F % 8 == 0 && ldh >= 2 * (int64_t)F, "qd_geglu_h16: bad shape (F=%d must be a multiple of 8, ldh >= 2 F)", F);
+    QD_REQUIRE(ldh % (h_dtype == QD_F32 ? 4 : 8) == 0 && qd_aligned(h, 16), "qd_geglu_h16: input rows must be 16-byte aligned");
+    QD_REQUIRE(ldo >= F && ldo % 8 == 0 && qd_aligned(out, 16), "qd_geglu_h16: output rows must be 16-byte aligned (ldo %% 8 == 0)");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const long total = (long)M * (ldo / 8);
+    const int fh = out_dtype == QD_F16 ? 1 : 0;
+    if (h_dtype == QD_F32)
+        hipLaunchKernelGGL(geglu_h16_kernel<float>, dim3(h16_stream_grid(total)), dim3(256), 0, st, (const float*)h, total, F, (long)ldh, reinterpret_cast<unsigned short*>(out), (long)ldo, fh);
+    else
+        hipLaunchKernelGGL(geglu_h16_kernel<__half>, dim3(h16_stream_grid(total)), dim3(256), 0, st, (const __half*)h, total, F, (long)ldh, reinterpret_cast<unsigned short*>(out), (long)ldo, fh);
+    QD_LAUNCH_CHECK("qd_geglu_h16");
+    return 0;
+}
+
+extern "C" int qd_groupnorm_h16(const void* x, int x_dtype, int64_t B, int64_t S, int C, int64_t ldx, int groups, float eps,
+                                const float* gamma, const float* beta, int apply_silu, void* out, int out_dtype, int64_t ldo,
+                                void* ws, void* stream) {
+    QD_REQUIRE(x && out && ws, "qd_groupnorm_h16: null pointer");
+    QD_REQUIRE(x_dtype == QD_F32 || x_dtype == QD_F16, "qd_groupnorm_h16: x_dtype must be f32/f16");
+    QD_REQUIRE(out_dtype == QD_F16 || out_dtype == QD_BF16, "qd_groupnorm_h16: out_dtype must be f16/bf16");
+    QD_REQUIRE(B > 0 && B < 65536 && S > 0 && C > 0 && groups > 0 && C % groups == 0 && C % 8 == 0,
+               "qd_groupnorm_h16: C=%d must be a multiple of 8 and of groups=%d", C, groups);
+    QD_REQUIRE(ldx >= C && ldx % (x_dtype == QD_F32 ? 4 : 8) == 0 && qd_aligned(x, 16), "qd_groupnorm_h16: input rows must be 16-byte aligned");
+    QD_REQUIRE(ldo >= C && ldo % 8 == 0 && qd_aligned(out, 16), "qd_groupnorm_h16: output rows must be 16-byte aligned (ldo %% 8 == 0)");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int nchunk = (int)((S + gn_rows(S) - 1) / gn_rows(S));
+    float* part = reinterpret_cast<float*>(ws);
+    float* ab = part + (size_t)B * nchunk * C * 2;
+    if (x_dtype == QD_F32)
+        hipLaunchKernelGGL(gn_partial_kernel<float>, dim3(nchunk, (unsigned)B), dim3(256), 0, st, (const float*)x, (long)S, C, (long)ldx, part, nchunk, 1);
+    else
+        hipLaunchKernelGGL(gn_partial_h8_kernel, dim3(nchunk, (unsigned)B), dim3(256), 0, st, (const __half*)x, (long)S, C, (long)ldx, part, nchunk);
+    if ((long)nchunk * (C / groups) >= 2048)
+        hipLaunchKernelGGL(gn_finalize_wide_kernel, dim3(groups, (unsigned)B), dim3(256), 0, st, part, nchunk, (long)C, (long)S, C, groups, eps, gamma, beta, ab);
+    else
+        hipLaunchKernelGGL(gn_finalize_kernel, dim3(groups, (unsigned)B), dim3(64), 0, st, part, nchunk, (long)C, (long)S, C, groups, eps, gamma, beta, ab);
+    const long total = (long)B * S * (ldo / 8);
+    const int fh = out_dtype == QD_F16 ? 1 : 0;
+    if (x_dtype == QD_F32)
+        hipLaunchKernelGGL(gn_apply_h16_kernel<float>, dim3(h16_stream_grid(total)), dim3(256), 0, st, (const float*)x, total, (long)S, C, (long)ldx, ab, apply_silu,
+                           reinterpret_cast<unsigned short*>(out), (long)ldo, fh);
+    else
+        hipLaunchKernelGGL(gn_apply_h16_kernel<__half>, dim3(h16_stream_grid(total)), dim3(256), 0, st, (const __half*)x, total, (long)S, C, (long)ldx, ab, apply_silu,
+                           reinterpret_cast<unsigned short*>(out), (long)ldo, fh);
+    QD_LAUNCH_CHECK("qd_groupnorm_h16");
+    return 0;
+}

@@ -557,17 +557,113 @@ def wonly_out_dtype(device_type="cuda"):
     return (torch.float16, None) if dt == torch.float16 else (torch.float32, dt)
 
 
-def wonly_forward(plan, xh, B, H, W, Ho, Wo, out_dtype=torch.float32, residual=None):
-    """qd_conv2d_wq_h16 on the rows of wonly_rows: returns out [B*Ho*Wo][Cout] (row-major)."""
+def wonly_forward(plan, xh, B, H, W, Ho, Wo, out_dtype=torch.float32, residual=None, rowbias=None):
+    """qd_conv2d_wq_h16 on the rows of wonly_rows: returns out [B*Ho*Wo][Cout] (row-major).
+    rowbias: fp32 [B][>= Cout] rows, row b added to every output row of sample b (the timestep-embedding projection)."""
     M = B * Ho * Wo
     out = torch.empty((M, plan.Cout), dtype=out_dtype, device=xh.device)
     if residual is not None and residual.dtype != out_dtype:
         residual = residual.to(out_dtype)
-    call = hip.ConvCall(x=xh, w=plan.pack.wq, out=out, bias=plan.bias, residual=residual, ldx=plan.ldx, ldk=plan.pack.ldk,
-                        ldo=out.stride(0), ldr=(residual.stride(0) if residual is not None else 0), ld_rowbias=0,
+    if rowbias is not None and (rowbias.dtype != torch.float32 or rowbias.dim() != 2 or rowbias.shape[0] != B
+                                or rowbias.shape[1] < plan.Cout or rowbias.stride(1) != 1):
+        raise hip.HipEngineError("wonly_forward: rowbias must be fp32 rows [B][>= Cout] with unit column stride")
+    call = hip.ConvCall(x=xh, w=plan.pack.wq, out=out, bias=plan.bias, residual=residual, rowbias=rowbias, ldx=plan.ldx,
+                        ldk=plan.pack.ldk, ldo=out.stride(0), ldr=(residual.stride(0) if residual is not None else 0),
+                        ld_rowbias=(rowbias.stride(0) if rowbias is not None else 0),
                         B=B, H=H, W=W, Ho=Ho, Wo=Wo, Cout=plan.Cout, kh=plan.kh, kw=plan.kw, stride=plan.stride,
                         pad_t=plan.pad, pad_l=plan.pad, wbits=plan.pack.wbits, w_tiled=True, segs=plan.segs)
     hip.conv2d_wq_h16(call, plan.act_dtype)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# weights-only block fusion: the norms, GEGLU, the embedding add and the residual adds of a weights-only block as producers
+# and epilogues of the kernels above (qd_groupnorm_h16, qd_layernorm_h16, qd_geglu_h16, rowbias / residual of qd_conv2d_wq_h16)
+# ------------------------------------------------------------------------------------------------
+def _parse_flag(v, name):
+    v = (v or "").strip().lower()
+    if v in ("", "0", "off", "false", "no"):
+        return False
+    if v in ("1", "on", "true", "yes"):
+        return True
+    raise ValueError(f"{name}={v!r}: expected 1 or 0")
+
+
+# Weights-only fusion: False (default) = a weights-only block runs the reference's composition, every QuantModule entered
+# through its own forward (library norms, qd_rows_to_h16 per consumer, separate adds); True = the plain residual blocks and
+# the transformer blocks run QuantResBlock._forward_wonly / QuantBasicTransformerBlock._forward_wonly.  Effective only while
+# WEIGHT_ONLY_KERNEL is set; the operand type is that knob's.  QDIFF_WEIGHT_ONLY_FUSE=1, or engine.set_weight_only_fusion().
+WEIGHT_ONLY_FUSE = _parse_flag(os.environ.get("QDIFF_WEIGHT_ONLY_FUSE"), "QDIFF_WEIGHT_ONLY_FUSE")
+
+# block forwards that took the fused route (tests read it to see that it ran)
+WONLY_FUSED = {"resblock": 0, "transformer": 0}
+
+# widest LayerNorm row of qd_layernorm_h16
+WONLY_LN_CMAX = 2048
+
+
+def set_weight_only_fusion(on):
+    """True / False (or the strings QDIFF_WEIGHT_ONLY_FUSE accepts)."""
+    global WEIGHT_ONLY_FUSE
+    if isinstance(on, str):
+        on = _parse_flag(on, "QDIFF_WEIGHT_ONLY_FUSE")
+    if not isinstance(on, bool):
+        raise ValueError("weight-only fusion must be True or False")
+    WEIGHT_ONLY_FUSE = on
+
+
+def _autocast_on():
+    try:
+        return torch.is_autocast_enabled("cuda") or torch.is_autocast_enabled("cpu")
+    except TypeError:
+        return torch.is_autocast_enabled() or torch.is_autocast_cpu_enabled()
+
+
+def wonly_fuse_state():
+    """The block-level conditions of the fused weights-only route that do not depend on the block: both knobs, no simulation,
+    no autograd, and no autocast (under torch.autocast the route does not engage: today's composition decides the dtypes)."""
+    return (WEIGHT_ONLY_FUSE and WEIGHT_ONLY_KERNEL is not None and not SIMULATE and not torch.is_grad_enabled()
+            and not _autocast_on())
+
+
+def wonly_plain_plan(plan, C):
+    """`plan` reads ONE segment that is the C channels of its input in order (no split shortcut), C a multiple of 8: the
+    layout a producer can write without knowing the consumer."""
+    if plan is None or len(plan.segs) != 1 or C % 8:
+        return False
+    sg = plan.pack.segs[0]
+    return sg["c0w"] == 0 and sg["clen"] == C and plan.segs[0]["c0"] == 0 and plan.ldx >= C
+
+
+def _h16_input_rows(rows):
+    """fp32 rows a producer can read with 16-byte loads (copied when a column range of wider rows is not aligned)."""
+    if rows.stride(1) != 1 or rows.stride(0) % 4 or rows.data_ptr() % 16:
+        rows = rows.contiguous()
+    return rows
+
+
+def wonly_groupnorm_rows(x_rows, B, S, C, gn, silu, plan):
+    """GroupNorm (+ SiLU) of channels-last fp32 rows [B*S][>= C] -> the operand rows [B*S][plan.ldx] of `plan`."""
+    x_rows = _h16_input_rows(x_rows)
+    out = torch.empty((B * S, plan.ldx), dtype=plan.act_dtype, device=x_rows.device)
+    ws = _workspace(hip.groupnorm_ws_bytes(B, C, S), x_rows.device)
+    hip.groupnorm_h16(x_rows, B, S, C, x_rows.stride(0), gn.num_groups, gn.eps, gn.weight, gn.bias, silu, out, plan.ldx, ws)
+    return out
+
+
+def wonly_layernorm_rows(x_rows, M, C, ln, plan):
+    """LayerNorm of fp32 rows [M][C] -> ONE buffer of operand rows [M][plan.ldx], shared by every consumer with that layout."""
+    x_rows = _h16_input_rows(x_rows)
+    out = torch.empty((M, plan.ldx), dtype=plan.act_dtype, device=x_rows.device)
+    hip.layernorm_h16(x_rows, M, C, x_rows.stride(0), ln.eps, ln.weight, ln.bias, out, plan.ldx)
+    return out
+
+
+def wonly_geglu_rows(h_rows, M, F, plan):
+    """value * gelu(gate) of rows [M][2F] -> the operand rows [M][plan.ldx] of `plan` (the feed-forward output Linear)."""
+    h_rows = _h16_input_rows(h_rows)
+    out = torch.empty((M, plan.ldx), dtype=plan.act_dtype, device=h_rows.device)
+    hip.geglu_h16(h_rows, M, F, h_rows.stride(0), out, plan.ldx)
     return out
 
 

@@ -68,7 +68,7 @@ EXPORTS = ["qd_abi_version", "qd_last_error", "qd_device_ok", "qd_box_probe", "q
            "qd_fakequant_blocks", "qd_fakequant_fwd", "qd_fakequant_bwd",
            "qd_conv2d_bf16", "qd_pack_weights_bf16_bytes", "qd_pack_weights_bf16", "qd_groupnorm_silu_bf16",
            "qd_pack_weights_h16", "qd_groupnorm_silu_h16", "qd_conv2d_wq_h16", "qd_rows_to_h16",
-           "qd_attn_h16"]
+           "qd_attn_h16", "qd_layernorm_h16", "qd_geglu_h16", "qd_groupnorm_h16"]
 
 _lib = None
 
@@ -131,6 +131,9 @@ def load():
     lib.qd_conv2d_wq_h16.argtypes = [ctypes.POINTER(ConvDesc), i32, vp]
     lib.qd_rows_to_h16.argtypes = [vp, i32, i64, i64, i64, i64, i64, i64, i32, i32, i32, vp, i32, i64, i32, vp]
     lib.qd_attn_h16.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32] + [i64] * 12 + [f32, i32, vp, i32, i64, vp]
+    lib.qd_layernorm_h16.argtypes = [vp, i32, i64, i32, i64, f32, vp, vp, vp, i32, i64, vp]
+    lib.qd_geglu_h16.argtypes = [vp, i32, i64, i32, i64, vp, i32, i64, vp]
+    lib.qd_groupnorm_h16.argtypes = [vp, i32, i64, i64, i32, i64, i32, f32, vp, vp, i32, vp, i32, i64, vp, vp]
     lib.qd_box_probe.argtypes = [i32, i32, i32, vp, vp, vp]
     lib.qd_attn_ws_bytes.argtypes = [i32, i32, i32, i32]
     lib.qd_attn_ws_bytes.restype = ctypes.c_int64
@@ -404,6 +407,47 @@ def attn_h16(q, k, v, B, T, S, H, d, q_strides, k_strides, v_strides, scale, op_
     _check(load().qd_attn_h16(_ptr(q, "q"), _ptr(k, "k"), _ptr(v, "v"), _H16[q.dtype], B, T, S, H, d, *q_strides, *k_strides,
                               *v_strides, float(scale), _H16[op_dtype], _ptr(out, "out"), _H16[out.dtype], out.stride(0), _stream()),
            "qd_attn_h16")
+
+
+def _h16_rows_check(what, x, ldx, Cin, out, ldo, Cout):
+    """Argument checks shared by the weights-only producers, before any launch: dtypes, 16-byte rows, ldo % 8."""
+    if x.dtype not in (torch.float32, torch.float16) or out.dtype not in (torch.float16, torch.bfloat16):
+        raise HipEngineError(f"{what}: unsupported dtypes {x.dtype} -> {out.dtype} (fp32 / fp16 rows -> fp16 / bf16 rows)")
+    m = 4 if x.dtype == torch.float32 else 8
+    if ldx < Cin or ldx % m or x.data_ptr() % 16:
+        raise HipEngineError(f"{what}: input rows must be 16-byte aligned (row stride {ldx}, a multiple of {m} elements)")
+    if ldo < Cout or ldo % 8 or out.data_ptr() % 16:
+        raise HipEngineError(f"{what}: output rows must be 16-byte aligned with ldo % 8 == 0 and ldo >= {Cout} (ldo {ldo})")
+
+
+def layernorm_h16(x, M, C, ldx, eps, gamma, beta, out, ldo):
+    """fp32 / fp16 rows [M][ldx] -> LayerNorm -> fp16 / bf16 operand rows [M][ldo] (the type of `out`), pad channels zero
+    (qd_layernorm_h16)."""
+    _h16_rows_check("layernorm_h16", x, ldx, C, out, ldo, C)
+    if C % 8 or C > 2048:
+        raise HipEngineError(f"layernorm_h16: C={C} unsupported (a multiple of 8, at most 2048)")
+    _check(load().qd_layernorm_h16(_ptr(x, "x"), _H16[x.dtype], M, C, ldx, float(eps), _ptr(gamma, "gamma"), _ptr(beta, "beta"),
+                                   _ptr(out, "out"), _H16[out.dtype], ldo, _stream()), "qd_layernorm_h16")
+
+
+def geglu_h16(h, M, F, ldh, out, ldo):
+    """fp32 / fp16 rows [M][ldh >= 2F] -> h[:, :F] * gelu(h[:, F:2F]) -> fp16 / bf16 operand rows [M][ldo] (qd_geglu_h16)."""
+    _h16_rows_check("geglu_h16", h, ldh, 2 * F, out, ldo, F)
+    if F % 8:
+        raise HipEngineError(f"geglu_h16: F={F} must be a multiple of 8")
+    _check(load().qd_geglu_h16(_ptr(h, "h"), _H16[h.dtype], M, F, ldh, _ptr(out, "out"), _H16[out.dtype], ldo, _stream()),
+           "qd_geglu_h16")
+
+
+def groupnorm_h16(x, B, S, C, ldx, groups, eps, gamma, beta, silu, out, ldo, ws):
+    """fp32 / fp16 channels-last rows [B*S][ldx] -> GroupNorm (+ SiLU) -> fp16 / bf16 operand rows [B*S][ldo], pad channels
+    zero (qd_groupnorm_h16).  ws: groupnorm_ws_bytes(B, C, S) bytes."""
+    _h16_rows_check("groupnorm_h16", x, ldx, C, out, ldo, C)
+    if C % 8 or C % groups:
+        raise HipEngineError(f"groupnorm_h16: C={C} must be a multiple of 8 and of groups={groups}")
+    _check(load().qd_groupnorm_h16(_ptr(x, "x"), _H16[x.dtype], B, S, C, ldx, groups, float(eps), _ptr(gamma), _ptr(beta),
+                                   1 if silu else 0, _ptr(out, "out"), _H16[out.dtype], ldo, _ptr(ws, "ws"), _stream()),
+           "qd_groupnorm_h16")
 
 
 def groupnorm_silu_bf16(x, B, S, C, groups, eps, gamma, beta, silu, out, ws, part=None):

@@ -148,6 +148,16 @@ def _no_hooks(*modules):
     return all(not m._forward_hooks and not m._forward_pre_hooks for m in modules)
 
 
+def _wonly_fuse_gate(block, layers, tensors):
+    """The fused weights-only route (engine.WEIGHT_ONLY_FUSE) takes this block call: knobs, no simulation / autograd /
+    autocast (engine.wonly_fuse_state), fp32 GPU tensors, no live dropout, every listed QuantModule on the weights-only kernel
+    without a split input, and no forward / pre-forward hook on any module below the block — the route bypasses their
+    forwards, and a hooked model must keep seeing every module call."""
+    return (engine.wonly_fuse_state() and all(torch.is_tensor(t) and t.dtype == torch.float32 and engine.wonly_device_ok(t) for t in tensors)
+            and not _dropout_live(block) and all(isinstance(m, QuantModule) and m.split == 0 and m.wonly_ready() for m in layers)
+            and _no_hooks(*list(block.modules())[1:]))
+
+
 def _gn_silu_to(conv, rows, B, S, C, gn, silu=True, raw_plan=None, mod=None):
     """GroupNorm(+SiLU) -> int8 rows for `conv`; initialises conv's act quantiser on first use.
     raw_plan: also return the int8 rows of a 1x1 consumer of the un-normalised `rows` (the skip connection), quantised
@@ -630,7 +640,46 @@ class QuantResBlock(BaseQuantBlock, ldm_unet.TimestepBlock):
         if (_int_mode(conv1, conv2, self.emb_layers[-1]) and conv1.split == 0 and conv2.split == 0 and not _dropout_live(self)
                 and (not self.updown or (H_ % 2 == 0 and not getattr(self.h_upd, "use_conv", False)))):
             return self._forward_int(x, emb, split, conv1, conv2, out_slot)
+        if self._wonly_fusable(x, emb, conv1, conv2):
+            return self._forward_wonly(x, emb, split, conv1, conv2)
         return self._forward_sim(x, emb, split)
+
+    def _wonly_fusable(self, x, emb, conv1, conv2):
+        """Plain blocks only (no `updown`, no `use_scale_shift_norm`) with the reference's layer lists (norm, SiLU, conv /
+        norm, SiLU, dropout, conv), both convolutions reading all their channels as one segment."""
+        if not engine.WEIGHT_ONLY_FUSE or self.updown or self.use_scale_shift_norm or x.dim() != 4:
+            return False
+        if not (len(self.in_layers) == 3 and len(self.out_layers) == 4 and isinstance(self.in_layers[0], nn.GroupNorm)
+                and isinstance(self.out_layers[0], nn.GroupNorm) and isinstance(self.in_layers[1], nn.SiLU)
+                and isinstance(self.out_layers[1], nn.SiLU) and isinstance(self.out_layers[2], nn.Dropout)):
+            return False
+        if not _wonly_fuse_gate(self, (conv1, conv2), (x, emb)):
+            return False
+        return (conv1.kind == 'conv2d' and conv2.kind == 'conv2d' and engine.wonly_plain_plan(conv1.wonly_plan(), x.shape[1])
+                and engine.wonly_plain_plan(conv2.wonly_plan(), self.out_channels) and conv2.wonly_plan().Cout == self.out_channels
+                and engine.conv_out_hw(x.shape[2], x.shape[3], conv1.wonly_plan()) == (x.shape[2], x.shape[3])
+                and engine.conv_out_hw(x.shape[2], x.shape[3], conv2.wonly_plan()) == (x.shape[2], x.shape[3]))
+
+    def _forward_wonly(self, x, emb, split, conv1, conv2):
+        """Reference :83-111 in the weights-only state: GN.SiLU -> operand rows (qd_groupnorm_h16), conv1 with the embedding
+        projection as a row bias, GN.SiLU -> operand rows, conv2 with the skip rows as the residual of its epilogue.  The
+        embedding projection and the skip connection keep their own module calls."""
+        B, C, H, W = x.shape
+        S = H * W
+        rows = _nhwc_rows(x)
+        xh = engine.wonly_groupnorm_rows(rows, B, S, C, self.in_layers[0], True, conv1.wonly_plan())
+        e = self.emb_layers(emb).float()
+        if e.stride(1) != 1:
+            e = e.contiguous()
+        h = conv1.forward_rows(xh, B, H, W, rowbias=e)
+        hh = engine.wonly_groupnorm_rows(h, B, S, self.out_channels, self.out_layers[0], True, conv2.wonly_plan())
+        if isinstance(self.skip_connection, nn.Identity):
+            res = rows
+        else:
+            res = _nhwc_rows(self.skip_connection(x, split=split) if split != 0 else self.skip_connection(x))
+        out = conv2.forward_rows(hh, B, H, W, residual=res)
+        engine.WONLY_FUSED["resblock"] += 1
+        return _rows_to_nchw(out, B, H, W)
 
     def _forward_sim(self, x, emb, split=0):
         if self.updown:
@@ -1006,9 +1055,92 @@ class QuantBasicTransformerBlock(BaseQuantBlock, _AttnQuant):
         if (glu and a1.use_act_quant and a2.use_act_quant and not _dropout_live(self) and _int_mode(*mods, self.ff.net[0].proj)
                 and self._attn_inited(a1) and self._attn_inited(a2)):
             return self._forward_int(x, context, out_plan)
+        if glu and self._wonly_fusable(x, context):
+            return self._forward_wonly(x, context)
         x = self.attn1(self.norm1(x)) + x
         x = self.attn2(self.norm2(x), context=context) + x
         return self.ff(self.norm3(x)) + x
+
+    def _wonly_fusable(self, x, context):
+        """Token rows [B, T, C] of a width qd_layernorm_h16 covers, three nn.LayerNorms, a GEGLU feed-forward whose halves are
+        multiples of 8, and every projection that reads a LayerNorm (or the GEGLU) taking all its channels as one segment."""
+        if not engine.WEIGHT_ONLY_FUSE or x.dim() != 3 or (context is not None and (not torch.is_tensor(context) or context.dim() != 3)):
+            return False
+        a1, a2, ff = self.attn1, self.attn2, self.ff
+        C = x.shape[2]
+        if C % 8 or C > engine.WONLY_LN_CMAX or not all(isinstance(n, nn.LayerNorm) and n.elementwise_affine and tuple(n.normalized_shape) == (C,)
+                                                       for n in (self.norm1, self.norm2, self.norm3)):
+            return False
+        proj, ff_out = ff.net[0].proj, ff.net[-1]
+        layers = [a1.to_q, a1.to_k, a1.to_v, a1.to_out[0], a2.to_q, a2.to_k, a2.to_v, a2.to_out[0], proj, ff_out]
+        if not _wonly_fuse_gate(self, layers, (x,) if context is None else (x, context)):
+            return False
+        if a1.use_act_quant or a2.use_act_quant or any(m.kind != 'linear' for m in layers):
+            return False
+        F2 = proj.wonly_plan().Cout
+        readers = [a1.to_q, a1.to_k, a1.to_v, a2.to_q, proj] + ([a2.to_k, a2.to_v] if context is None else [])
+        if not all(engine.wonly_plain_plan(m.wonly_plan(), C) and m.wonly_plan().ldx == proj.wonly_plan().ldx for m in readers):
+            return False
+        if F2 % 16 or not engine.wonly_plain_plan(ff_out.wonly_plan(), F2 // 2) or ff_out.wonly_plan().Cout != C:
+            return False
+        for att in (a1, a2):
+            inner = att.to_q.wonly_plan().Cout
+            if (inner % att.heads or att.to_k.wonly_plan().Cout != inner or att.to_v.wonly_plan().Cout != inner
+                    or not engine.wonly_plain_plan(att.to_out[0].wonly_plan(), inner) or att.to_out[0].wonly_plan().Cout != C):
+                return False
+        return True
+
+    def _attn_wonly(self, att, rows, B, T, C, ln, context):
+        """norm -> ONE buffer of operand rows -> to_q / to_k / to_v -> attention -> to_out with `rows` as the residual of its
+        epilogue.  The attention is qd_attn_h16 under engine.WEIGHT_ONLY_ATTN, else the library passes of cross_attn_forward;
+        to_k / to_v of a cross-attention read the context through their own module calls."""
+        h, M = att.heads, B * T
+        xh = engine.wonly_layernorm_rows(rows, M, C, ln, att.to_q.wonly_plan())
+        out_lin = att.to_out[0]
+        oplan = out_lin.wonly_plan()
+        inner = oplan.pack.segs[0]["clen"]
+        d = inner // h
+        fused = _wonly_attn_gate((att.to_q, att.to_k, att.to_v, out_lin), (rows,), d)
+        # the attention kernel rounds q / k / v to its operand type when it stages them: fp16 projections are the same bytes
+        # (self-attention only: the context projections come from their module calls in fp32, and the kernel takes one type)
+        qdt = torch.float16 if fused and context is None and engine.WEIGHT_ONLY_ATTN == torch.float16 else torch.float32
+        q = att.to_q.forward_rows(xh, 1, 1, M, out_dtype=qdt).view(B, T, inner)
+        if context is None:
+            k = att.to_k.forward_rows(xh, 1, 1, M, out_dtype=qdt).view(B, T, inner)
+            v = att.to_v.forward_rows(xh, 1, 1, M, out_dtype=qdt).view(B, T, inner)
+        else:
+            k, v = att.to_k(context), att.to_v(context)
+        S = k.shape[1]
+        if fused:
+            # fp16 operand rows of to_out straight from the kernel when the layouts agree (the same single rounding of the
+            # fp32 result that qd_rows_to_h16 would apply), else fp32 rows and that pass
+            direct = oplan.act_dtype == torch.float16 and oplan.ldx == inner
+            st = lambda t: (t.stride(0), t.stride(1), d, 1)
+            o = engine.attention_h16(q, k, v, B, T, S, h, d, st(q), st(k), st(v), att.scale, torch.float16 if direct else torch.float32)
+            oh = o if direct else engine.wonly_rows(o, oplan, 1, inner, M, (0, 1, inner))
+        else:
+            qh, kh, vh = (ldm_unet._split_heads(t, h) for t in (q, k, v))
+            p = (th.einsum('b i d, b j d -> b i j', qh, kh) * att.scale).softmax(dim=-1)
+            o = ldm_unet._merge_heads(th.einsum('b i j, b j d -> b i d', p, vh), h).reshape(M, inner)
+            oh = engine.wonly_rows(o, oplan, 1, inner, M, (0, 1, o.stride(0)))
+        return out_lin.forward_rows(oh, 1, 1, M, residual=rows)
+
+    def _forward_wonly(self, x, context):
+        """attention.py:229-231 in the weights-only state: every LayerNorm is qd_layernorm_h16 into the operand rows of its
+        consumers, the `+ x` adds ride in the epilogues of to_out / the FF output, the GEGLU projection is written once as fp32
+        [M][2F] and qd_geglu_h16 turns it into the FF output's operand rows."""
+        B, T, C = x.shape
+        M = B * T
+        rows = x.reshape(M, C)
+        rows = self._attn_wonly(self.attn1, rows, B, T, C, self.norm1, None)
+        rows = self._attn_wonly(self.attn2, rows, B, T, C, self.norm2, context)
+        proj, ff_out = self.ff.net[0].proj, self.ff.net[-1]
+        xh = engine.wonly_layernorm_rows(rows, M, C, self.norm3, proj.wonly_plan())
+        hcat = proj.forward_rows(xh, 1, 1, M)
+        gh = engine.wonly_geglu_rows(hcat, M, hcat.shape[1] // 2, ff_out.wonly_plan())
+        rows = ff_out.forward_rows(gh, 1, 1, M, residual=rows)
+        engine.WONLY_FUSED["transformer"] += 1
+        return rows.view(B, T, C)
 
     def _attn_int(self, att, rows, B, T, C, ln, ctx_rows, S, kv=None, pre_attention=None):
         """norm -> q/k/v projections -> fused quantised attention -> to_out (+ residual rows).

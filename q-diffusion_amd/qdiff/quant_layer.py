@@ -623,6 +623,15 @@ class QuantModule(nn.Module):
             y = engine.wonly_forward(plan, xh, 1, 1, M, 1, M, out_dtype).view(*lead, plan.Cout)
         return y if cast is None else y.to(cast)
 
+    def forward_rows(self, xh, B, H, W, Ho=None, Wo=None, rowbias=None, residual=None, out_dtype=torch.float32):
+        """Weights-only path for a producer that already emitted this module's fp16 / bf16 operand rows (fused blocks; the
+        counterpart of forward_codes).  xh: rows [B*H*W][plan.ldx]; rowbias: fp32 [B][Cout] added per sample; residual: rows
+        [B*Ho*Wo][Cout] added in the epilogue.  Returns channels-last rows [B*Ho*Wo][Cout]."""
+        plan = self.wonly_plan()
+        if Ho is None:
+            Ho, Wo = engine.conv_out_hw(H, W, plan)
+        return engine.wonly_forward(plan, xh, B, H, W, Ho, Wo, out_dtype, residual=residual, rowbias=rowbias)
+
     def geglu_plan(self):
         """Second plan of a GEGLU projection: rows packed (value tile, gate tile) interleaved for the fused
         value*gelu(gate)->quantise epilogue (engine.conv_forward_geglu).  None if the layer does not

@@ -14,6 +14,14 @@ table at SD's shapes (kernel us, TFLOP/s, share of the fp16 peak at 4*BH*T*S*d F
 and the library core in fp32 as yardsticks).
 
     python tools/bench_weight_only.py --attn [--models sd,ldm,churches] [--attn-shapes]
+
+--fuse adds the block-fusion column (engine.WEIGHT_ONLY_FUSE) with the layer kernel at fp16 (and, with --attn, the attention
+kernel at fp16): evaluation time with the fusion off and on, alternated A/B --rounds times in one process, best and spread of
+each side, the blocks that took the fused route, peak memory, and a box probe (hip.box_probe) so that two runs can be told
+apart.  --fuse-shapes prints the three producers alone at SD's shapes: microseconds and achieved GB/s (bytes read + written)
+next to a plain device copy of the same bytes and the ~6.3 TB/s streaming ceiling.
+
+    python tools/bench_weight_only.py --attn --fuse [--models sd,ldm] [--rounds 3] [--fuse-shapes]
 """
 import argparse
 import json
@@ -179,6 +187,94 @@ def run_attn(kind, batch, k, dev):
     return res
 
 
+def run_fuse(kind, batch, k, dev, attn, rounds):
+    import bench
+    from qdiff import engine, hip, synthetic
+    qnn, _ = bench.build_quantised_unet(kind, dev)
+    x, t, c = synthetic.synthetic_inputs(kind, batch, seed=0)
+    args = [a.to(dev) for a in (x, t, c) if a is not None]
+    qnn.set_quant_state(True, False)
+    one = lambda: qnn(*args)
+    res = {"model": kind, "batch": batch, "layer_knob": "fp16", "attn_knob": "fp16" if attn else "off", "evals_timed": k, "rounds": rounds}
+    prev = (engine.WEIGHT_ONLY_KERNEL, engine.WEIGHT_ONLY_ATTN, engine.WEIGHT_ONLY_FUSE)
+    try:
+        engine.set_weight_only_kernel(torch.float16)
+        engine.set_weight_only_attention(torch.float16 if attn else None)
+        ms, ticks = hip.box_probe(dev, 0, 512, 60000)
+        res["box_probe_mfma_ms"] = round(ms, 3)
+        off, on = [], []
+        for _ in range(rounds):                                  # alternated A/B
+            engine.set_weight_only_fusion(False)
+            off.append(_timed(one, k))
+            engine.set_weight_only_fusion(True)
+            on.append(_timed(one, k))
+        res["fuse_off_ms"], res["fuse_on_ms"] = round(min(off), 3), round(min(on), 3)
+        res["fuse_off_ms_all"], res["fuse_on_ms_all"] = [round(v, 3) for v in off], [round(v, 3) for v in on]
+        res["fuse_off_spread_ms"], res["fuse_on_spread_ms"] = round(max(off) - min(off), 3), round(max(on) - min(on), 3)
+        res["faster_by_more_than_spread"] = bool(min(off) - max(on) > 0 and min(off) - min(on) > max(max(off) - min(off), max(on) - min(on)))
+        for k2 in engine.WONLY_FUSED:
+            engine.WONLY_FUSED[k2] = 0
+        with torch.no_grad():
+            y_on = one()
+        res["blocks_fused"] = dict(engine.WONLY_FUSED)
+        engine.set_weight_only_fusion(False)
+        with torch.no_grad():
+            y_off = one()
+        res["fuse_on_vs_off_of_range"] = float((y_on - y_off).abs().max() / y_off.abs().max())
+        for name, flag in (("off", False), ("on", True)):
+            engine.set_weight_only_fusion(flag)
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats(dev)
+            with torch.no_grad():
+                one()
+            torch.cuda.synchronize()
+            res[f"fuse_{name}_max_mem_mib"] = round(torch.cuda.max_memory_allocated(dev) / 2 ** 20, 1)
+    finally:
+        engine.set_weight_only_kernel(prev[0])
+        engine.set_weight_only_attention(prev[1])
+        engine.set_weight_only_fusion(prev[2])
+    return res
+
+
+STREAM_CEILING_GBS = 6300.0        # HBM streaming ceiling of element-wise kernels (cdna_hip_programming.md Appendix B)
+# SD-v1.4 at batch 16: (tokens M = 16 * H * W, channels C) of the four latent levels; GroupNorm also at the widths of the
+# concatenated up-path inputs
+SD_LN_SHAPES = [(65536, 320), (16384, 640), (4096, 1280)]
+SD_GN_SHAPES = [(16, 4096, 320), (16, 4096, 640), (16, 4096, 960), (16, 1024, 640), (16, 1024, 1280), (16, 1024, 1920), (16, 256, 1280),
+                (16, 256, 2560), (16, 64, 1280), (16, 64, 2560)]
+
+
+def fuse_shape_table(dev):
+    from qdiff import hip
+    g = torch.Generator(device=dev).manual_seed(0)
+
+    def row(op, shape, fn, nbytes):
+        us = 1000 * _events_ms(fn, 20)
+        src = torch.empty(nbytes // 2, dtype=torch.uint8, device=dev)
+        dst = torch.empty_like(src)
+        cp = 1000 * _events_ms(lambda: dst.copy_(src), 20)
+        print(json.dumps({"op": op, "shape": shape, "us": round(us, 1), "gbs": round(nbytes / us / 1e3, 1),
+                          "of_ceiling": round(nbytes / us / 1e3 / STREAM_CEILING_GBS, 3), "device_copy_same_bytes_us": round(cp, 1)}), flush=True)
+
+    for M, C in SD_LN_SHAPES:
+        x = torch.randn(M, C, device=dev, generator=g)
+        gm, bt = torch.ones(C, device=dev), torch.zeros(C, device=dev)
+        out = torch.empty(M, C, dtype=torch.float16, device=dev)
+        row("layernorm_h16", [M, C], lambda: hip.layernorm_h16(x, M, C, C, 1e-5, gm, bt, out, C), M * C * 6)
+        Fd = 4 * C
+        h = torch.randn(M, 2 * Fd, device=dev, generator=g)
+        o2 = torch.empty(M, Fd, dtype=torch.float16, device=dev)
+        row("geglu_h16", [M, Fd], lambda: hip.geglu_h16(h, M, Fd, 2 * Fd, o2, Fd), M * Fd * 10)
+        del h, o2
+    for B, S, C in SD_GN_SHAPES:
+        x = torch.randn(B * S, C, device=dev, generator=g)
+        gm, bt = torch.ones(C, device=dev), torch.zeros(C, device=dev)
+        out = torch.empty(B * S, C, dtype=torch.float16, device=dev)
+        ws = torch.empty(hip.groupnorm_ws_bytes(B, C, S), dtype=torch.uint8, device=dev)
+        # two reads of x (statistics, apply) and one 16-bit write
+        row("groupnorm_h16+silu", [B, S, C], lambda: hip.groupnorm_h16(x, B, S, C, C, 32, 1e-5, gm, bt, True, out, C, ws), B * S * C * 10)
+
+
 # SD-v1.4 at batch 16 (B*H = 128): self-attention at the four latent levels, cross-attention over 77 tokens
 SD_SHAPES = [(128, 4096, 4096, 40), (128, 1024, 1024, 80), (128, 256, 256, 160), (128, 64, 64, 160),
              (128, 4096, 77, 40), (128, 1024, 77, 80), (128, 256, 77, 160), (128, 64, 77, 160)]
@@ -217,6 +313,9 @@ def main():
     ap.add_argument("--evals", type=int, default=3)
     ap.add_argument("--attn", action="store_true", help="the attention-knob column (layer kernel at fp16)")
     ap.add_argument("--attn-shapes", action="store_true", help="the per-shape attention table at SD's shapes")
+    ap.add_argument("--fuse", action="store_true", help="the block-fusion column (layer kernel at fp16; with --attn the attention kernel too)")
+    ap.add_argument("--rounds", type=int, default=3, help="A/B alternations of --fuse")
+    ap.add_argument("--fuse-shapes", action="store_true", help="the three producers alone at SD's shapes")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     from qdiff import hip
@@ -224,8 +323,14 @@ def main():
     dev = torch.device("cuda:0")
     if a.attn_shapes:
         attn_shape_table(dev, SD_SHAPES + LDM_SHAPES)
+    if a.fuse_shapes:
+        fuse_shape_table(dev)
     for kind in a.models.split(","):
-        print(json.dumps((run_attn if a.attn else run)(kind, a.batch, a.evals, dev)), flush=True)
+        if a.fuse:
+            res = run_fuse(kind, a.batch, a.evals, dev, a.attn, a.rounds)
+        else:
+            res = (run_attn if a.attn else run)(kind, a.batch, a.evals, dev)
+        print(json.dumps(res), flush=True)
         torch.cuda.empty_cache()
 
 
