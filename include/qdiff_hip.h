@@ -40,7 +40,7 @@ extern "C" {
 /* element types of floating-point tensors crossing the ABI */
 enum { QD_F32 = 0, QD_F16 = 1, QD_BF16 = 2 };
 /* epilogues of qd_conv2d_i8 */
-enum { QD_EPI_LINEAR = 0, QD_EPI_GEGLU_I8 = 1, QD_EPI_HEADS_I8 = 2, QD_EPI_HEADS_T_I8 = 3 };
+enum { QD_EPI_LINEAR = 0, QD_EPI_GEGLU_I8 = 1, QD_EPI_HEADS_I8 = 2, QD_EPI_HEADS_T_I8 = 3, QD_EPI_GEGLU_H16 = 4 /* qd_conv2d_wq_h16 only */ };
 
 int         qd_abi_version(void);
 const char* qd_last_error(void);
@@ -459,13 +459,20 @@ int qd_groupnorm_silu_h16(const float* x, int64_t B, int64_t S, int C, int64_t l
  *                    as for qd_conv2d_i8: the packs of the integer path serve this mode unchanged
  *         seg.scale  [Cout] delta_w[n] of the segment's weight quantiser;  seg.zw: [Cout] its RAW zero point z[n]
  *                    in [-128, 255] (not zw - 128);  seg.zc / zfill / fill16 must be NULL
- *         nseg 1 or 2 (split shortcut, quant_layer.py:257-269: each segment its own delta / z), epilogue = QD_EPI_LINEAR,
- *         out_dtype QD_F32 or QD_F16 (the residual has the type of the output), kh/kw/stride/pad_t/pad_l as for
+ *         nseg 1 or 2 (split shortcut, quant_layer.py:257-269: each segment its own delta / z), epilogue = QD_EPI_LINEAR
+ *         (or QD_EPI_GEGLU_H16, below), out_dtype QD_F32 or QD_F16 (the residual has the type of the output), kh/kw/stride/pad_t/pad_l as for
  *         qd_conv2d_i8; out-of-image taps, K tails and M tails read zeros.  gn_part, upsample2x must be unset;
  *         split-K, oq_* / hd_* are ignored.
  *         rowbias    optional fp32 [B][ld_rowbias] (ld_rowbias >= Cout): row b is added to every output row of sample b
  *                    after the bias and before the residual, as in qd_conv2d_i8 (the timestep-embedding add
  *                    `h + emb_out` of qdiff/quant_block.py:92-98).  NULL leaves the output bytes as they were.
+ *         epilogue = QD_EPI_GEGLU_H16: the layer is a GEGLU projection, Cout = 2 F with F % 32 == 0, and w was
+ *                    packed with its rows in 32-row tiles interleaved value, gate, value, ... (qdiff.engine.geglu_row_perm;
+ *                    seg.scale, seg.zw and bias in that order too).  out then receives the operand rows of the next layer,
+ *                    out[m][f] = value * gelu(gate) with value / gate the affine results of features f and F + f, gelu through
+ *                    the erf of qd_geglu_h16, rounded ONCE to out_dtype = act_dtype; [M][ldo] with ldo >= F, ldo % 8 == 0,
+ *                    16-byte aligned, channels [F, ldo) written as zeros.  One segment, no residual, no rowbias.  The bytes
+ *                    are those of the linear epilogue (fp32 out, un-permuted pack) followed by qd_geglu_h16.
  *         bf16 operands carry q - z exactly only while |q - z| <= 256 for every stored code: the caller checks (8-bit
  *         codes with z < -1 can exceed it); fp16 is exact for every zero point in [-128, 255].
  *     qd_rows_to_h16: the producer of those rows.  x is a logical [B][C][S] fp32 / fp16 / bf16 tensor addressed by element

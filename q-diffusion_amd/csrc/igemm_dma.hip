@@ -87,7 +87,7 @@ struct ConvD {
 // attn_i8.hip (rows [(b,h)][t][dpad] for q and k; transposed + key-permuted [(b,h)][dd][t] plus column
 // sums for v) — the fp32 projection output and the separate qd_quantize_heads pass disappear.
 // O_BF16 (WB = 16 only): bf16 rows (+ bf16 residual) — the floating-point mode of the kernel (first-stage decoder, §N1).
-enum { O_F32 = 0, O_F16 = 1, O_I32 = 2, O_GEGLU = 3, O_PART = 4, O_HROWS = 5, O_HTR = 6, O_BF16 = 7 };
+enum { O_F32 = 0, O_F16 = 1, O_I32 = 2, O_GEGLU = 3, O_PART = 4, O_HROWS = 5, O_HTR = 6, O_BF16 = 7, O_GEGLU_H = 8 };
 
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
@@ -2112,6 +2112,56 @@ __global__ __launch_bounds__(256, 2) void wq_h16_kernel(const WqD p) {
         const unsigned t = cur; cur = nxt; nxt = t;
     }
 
+    // ---- QD_EPI_GEGLU_H16: the weight rows are 32-column tiles interleaved value, gate, value, ... (geglu_row_perm), so the
+    // wave's n-tile j = 0 is a value tile and j = 1 its gate tile: acc[i][0][r] and acc[i][1][r] of one lane are the value and
+    // the gate of output feature (n0 + wn * 64) / 2 + frow.  Affine part and GEGLU through the functions qd_conv2d_wq_h16 +
+    // qd_geglu_h16 use (common.h), ONE rounding to the operand type.  The wave's 64 x 32 results go through its own region of
+    // the LDS ring (idle after the last K-step; rows padded to 80 bytes so that the two half-waves, 4 rows apart, hit
+    // different banks) and leave as 16-byte pieces: four per row instead of 32 two-byte stores.  Channels [F, ldo) are
+    // written as zeros by the last block of the row of blocks.
+    if constexpr (OUT == O_GEGLU_H) {
+        static_assert(!SPLIT, "the GEGLU epilogue takes one segment");
+        constexpr int GROW = 80;                                // staged row: 64 bytes of results + 16 bytes of padding
+        static_assert(4 * 64 * GROW <= 2 * STAGE, "the staged tiles fit the ring");
+        unsigned short* const outp = reinterpret_cast<unsigned short*>(p.out);
+        const int F = p.Cout >> 1;
+        const int ncol = n0 + wn * 64;                          // first (value) column of the wave; Cout % 64 == 0
+        unsigned char* const stg = smem + wave * (64 * GROW);
+        if (ncol < p.Cout) {
+            const float dv = dl[0][0], dg = dl[0][1];
+            const float bv = p.bias ? p.bias[ncol + frow] : 0.f, bg = p.bias ? p.bias[ncol + 32 + frow] : 0.f;
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float y = qd_geglu_f(qd_wq_affine(acc[i][0][r], dv, 0.f, bv), qd_wq_affine(acc[i][1][r], dg, 0.f, bg));
+                    // pin the fp32 rounding of the last product: left alone, the compiler fuses that multiply with the
+                    // conversion (v_fma_mixlo_f16: one rounding instead of two) and the fp16 rows are no longer those of
+                    // qd_geglu_h16, which converts the rounded fp32 value
+                    asm volatile("" : "+v"(y));
+                    const unsigned short h = (unsigned short)((FH ? qd_pack2h(y, 0.f) : qd_pack2bf(y, 0.f)) & 0xffffu);
+                    *reinterpret_cast<unsigned short*>(stg + (i * 32 + crow(r) + 4 * fhalf) * GROW + frow * 2) = h;
+                }
+        }
+        __syncthreads();
+        if (ncol < p.Cout) {
+            const int f0 = ncol >> 1;                           // the wave's 32 features start here: 64-byte aligned in the row
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int pc = lane + 64 * t, row = pc >> 2, q = pc & 3;
+                const long m = m0 + wm * 64 + row;
+                if (m < p.M) *reinterpret_cast<v4i*>(outp + m * p.ldo + f0 + q * 8) = *reinterpret_cast<const v4i*>(stg + row * GROW + q * 16);
+            }
+        }
+        const int npad = (int)((p.ldo - F) >> 3);               // 16-byte pieces of zeros per row
+        if (nb == p.nblk_n - 1 && npad > 0) {
+            for (int idx = tid; idx < BM * npad; idx += 256) {
+                const int row = idx / npad, q = idx - row * npad;
+                const long m = m0 + row;
+                if (m < p.M) *reinterpret_cast<v4i*>(outp + m * p.ldo + F + q * 8) = v4i{0, 0, 0, 0};
+            }
+        }
+    } else {
     // ---- epilogue in the C layout: lane = column, 16 rows per lane; 32 lanes write 32 consecutive columns of a row ----
     const int sl = SPLIT ? 1 : 0;
 #pragma unroll
@@ -2125,7 +2175,7 @@ __global__ __launch_bounds__(256, 2) void wq_h16_kernel(const WqD p) {
             for (int r = 0; r < 16; ++r) {
                 const long m = m0 + wm * 64 + i * 32 + crow(r) + 4 * fhalf;
                 if (m >= p.M) continue;
-                float v = __builtin_fmaf(acc[i][j][r], d, SPLIT ? facc[SPLIT ? i : 0][SPLIT ? j : 0][r] : 0.f) + bias;
+                float v = qd_wq_affine(acc[i][j][r], d, SPLIT ? facc[SPLIT ? i : 0][SPLIT ? j : 0][r] : 0.f, bias);
                 if (p.rowbias) v += p.rowbias[((int)m / HoWo) * p.ldrb + n];
                 if constexpr (OUT == O_F32) {
                     if (p.residual) v += reinterpret_cast<const float*>(p.residual)[m * p.ldr + n];
@@ -2135,6 +2185,7 @@ __global__ __launch_bounds__(256, 2) void wq_h16_kernel(const WqD p) {
                     reinterpret_cast<__half*>(p.out)[m * p.ldo + n] = __float2half(v);
                 }
             }
+    }
     }
 }
 
@@ -2174,17 +2225,25 @@ int run_wq_h16(const qd_conv_desc* d, int act_dtype, void* stream) {
     QD_REQUIRE(d->x && d->w && d->out, "qd_conv2d_wq_h16: null tensor pointer");
     QD_REQUIRE(act_dtype == QD_F16 || act_dtype == QD_BF16, "qd_conv2d_wq_h16: act_dtype must be QD_F16 or QD_BF16");
     QD_REQUIRE(d->w_tiled && (d->wbits == 4 || d->wbits == 8), "qd_conv2d_wq_h16: weights must be tile-ordered codes of qd_pack_weights_t4 / _t8 (w_tiled = 1, wbits 4 / 8)");
-    QD_REQUIRE(d->out_dtype == QD_F32 || d->out_dtype == QD_F16, "qd_conv2d_wq_h16: out_dtype must be f32/f16");
+    QD_REQUIRE(d->out_dtype == QD_F32 || d->out_dtype == QD_F16 || d->epilogue == QD_EPI_GEGLU_H16, "qd_conv2d_wq_h16: out_dtype must be f32/f16");
     QD_REQUIRE(d->nseg == 1 || d->nseg == 2, "qd_conv2d_wq_h16: nseg must be 1 or 2");
-    QD_REQUIRE(d->epilogue == QD_EPI_LINEAR && !d->gn_part && !d->upsample2x,
+    const bool geglu = d->epilogue == QD_EPI_GEGLU_H16;
+    QD_REQUIRE((d->epilogue == QD_EPI_LINEAR || geglu) && !d->gn_part && !d->upsample2x,
                "qd_conv2d_wq_h16: linear epilogue only (no GroupNorm statistics or up-sampling)");
+    if (geglu) {                                               // out = operand rows [M][ldo] of value * gelu(gate), F = Cout / 2
+        QD_REQUIRE(d->nseg == 1 && d->Cout % 64 == 0, "qd_conv2d_wq_h16: GEGLU epilogue: one segment, Cout = 2 F with F %% 32 == 0 (Cout=%d)", d->Cout);
+        QD_REQUIRE(d->out_dtype == act_dtype, "qd_conv2d_wq_h16: GEGLU epilogue: out_dtype must be act_dtype (operand rows)");
+        QD_REQUIRE(d->residual == nullptr && d->rowbias == nullptr, "qd_conv2d_wq_h16: GEGLU epilogue takes no residual and no rowbias");
+        QD_REQUIRE(d->ldo >= d->Cout / 2 && d->ldo % 8 == 0 && qd_aligned(d->out, 16),
+                   "qd_conv2d_wq_h16: GEGLU epilogue: out rows must be 16-byte aligned with ldo %% 8 == 0 and ldo >= F");
+    }
     QD_REQUIRE(!d->rowbias || d->ld_rowbias >= d->Cout, "qd_conv2d_wq_h16: ld_rowbias shorter than Cout");
     QD_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0 && d->Cout > 0, "qd_conv2d_wq_h16: bad shape");
     QD_REQUIRE(d->kh > 0 && d->kw > 0 && d->stride > 0 && d->kh * d->kw <= 32, "qd_conv2d_wq_h16: bad kernel/stride (at most 32 taps)");
     QD_REQUIRE(d->pad_t >= 0 && d->pad_l >= 0 && d->pad_t < 64 && d->pad_l < 64, "qd_conv2d_wq_h16: bad padding");
     QD_REQUIRE((long)d->B * d->Ho * d->Wo < (1L << 31), "qd_conv2d_wq_h16: M overflows int32");
     QD_REQUIRE(d->ldx % 8 == 0 && qd_aligned(d->x, 16) && qd_aligned(d->w, 16), "qd_conv2d_wq_h16: x/w must be 16-byte aligned, ldx %% 8 == 0");
-    QD_REQUIRE(d->ldo >= d->Cout && (!d->residual || d->ldr >= d->Cout), "qd_conv2d_wq_h16: ldo / ldr shorter than Cout");
+    QD_REQUIRE((geglu || d->ldo >= d->Cout) && (!d->residual || d->ldr >= d->Cout), "qd_conv2d_wq_h16: ldo / ldr shorter than Cout");
     WqD k{};
     k.x = reinterpret_cast<const unsigned short*>(d->x); k.wt = d->w; k.out = d->out; k.residual = d->residual; k.bias = d->bias;
     k.rowbias = d->rowbias; k.ldrb = d->ld_rowbias;
@@ -2209,7 +2268,7 @@ int run_wq_h16(const qd_conv_desc* d, int act_dtype, void* stream) {
     const bool fh = act_dtype == QD_F16, split = d->nseg == 2, o16 = d->out_dtype == QD_F16;
 #define QD_WQ(WB, FH, SP, O) hipLaunchKernelGGL((wq_h16_kernel<WB, FH, SP, O>), grid, block, 0, st, k)
 #define QD_WQ_OUT(WB, FH, SP) { if (o16) QD_WQ(WB, FH, SP, O_F16); else QD_WQ(WB, FH, SP, O_F32); }
-#define QD_WQ_SPLIT(WB, FH) { if (split) QD_WQ_OUT(WB, FH, true) else QD_WQ_OUT(WB, FH, false) }
+#define QD_WQ_SPLIT(WB, FH) { if (geglu) QD_WQ(WB, FH, false, O_GEGLU_H); else if (split) QD_WQ_OUT(WB, FH, true) else QD_WQ_OUT(WB, FH, false) }
     if (d->wbits == 4) { if (fh) QD_WQ_SPLIT(4, true) else QD_WQ_SPLIT(4, false) }
     else { if (fh) QD_WQ_SPLIT(8, true) else QD_WQ_SPLIT(8, false) }
 #undef QD_WQ_SPLIT

@@ -1003,7 +1003,7 @@ __global__ __launch_bounds__(256) void geglu_h16_kernel(const T* __restrict__ h,
             h16_ld8(h + row * ldh + c8 * 8, a);
             h16_ld8(h + row * ldh + F + c8 * 8, g);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) y[j] = a[j] * (0.5f * g[j] * (1.0f + qd_erff(g[j] * 0.70710678118654752440f)));
+            for (int j = 0; j < 8; ++j) y[j] = qd_geglu_f(a[j], g[j]);
             pk = h16_pack8(y, fh);
         }
         *reinterpret_cast<v4i*>(out + row * ldo + c8 * 8) = pk;

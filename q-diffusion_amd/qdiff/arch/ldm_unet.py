@@ -196,6 +196,9 @@ class SpatialTransformer(nn.Module):
             else:
                 out = qb._linear_rows(self.proj_out, t.reshape(b * h * w, t.shape[-1]), residual=rows, gn_stats=True, slot=out_slot)
             return qb._rows_to_nchw(out, b, h, w)
+        if qb.spatial_wonly_wide(self, x):
+            # weights-only state with engine.WEIGHT_ONLY_FUSE_WIDE: the norm writes proj_in's operand rows, `+ x` rides in proj_out
+            return qb.spatial_forward_wonly(self, x, context)
         t = self.proj_in(self.norm(x))
         t = t.permute(0, 2, 3, 1).reshape(b, h * w, t.shape[1])
         for blk in self.transformer_blocks:

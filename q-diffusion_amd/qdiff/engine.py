@@ -517,16 +517,23 @@ def wonly_code_span(pack):
     return span
 
 
-def build_wonly_plan(pack, kh, kw, stride, pad, bias, act_dtype):
+def build_wonly_plan(pack, kh, kw, stride, pad, bias, act_dtype, geglu=False):
     """WonlyPlan for `pack` (engine.pack_module_weights or a packed checkpoint's frozen pack), or None when the kernel does
-    not take it: a row-permuted pack, or bf16 operands and a stored code with |q - z| > 256 (not exact in bf16)."""
-    if not pack.tiled or pack.row_perm is not None or pack.mode not in (4, 8):
+    not take it: a row-permuted pack, or bf16 operands and a stored code with |q - z| > 256 (not exact in bf16).
+    geglu: the plan of the QD_EPI_GEGLU_H16 epilogue (QuantModule.wonly_geglu_plan) — the one caller whose pack IS permuted, by
+    geglu_row_perm; delta / z come permuted from the pack, the bias is permuted here."""
+    if not pack.tiled or (pack.row_perm is not None) != bool(geglu) or pack.mode not in (4, 8):
+        return None
+    if geglu and (len(pack.segs) != 1 or pack.taps != 1 or pack.Cout % 64
+                  or not torch.equal(pack.row_perm.cpu(), geglu_row_perm(pack.Cout // 2, "cpu"))):
         return None
     if act_dtype == torch.bfloat16 and wonly_code_span(pack) > 256:
         return None
     plan = WonlyPlan()
     plan.pack, plan.kh, plan.kw, plan.stride, plan.pad = pack, kh, kw, stride, pad
     plan.bias = bias.detach().float().contiguous() if bias is not None else None
+    if plan.bias is not None and geglu:
+        plan.bias = plan.bias.index_select(0, pack.row_perm.to(plan.bias.device)).contiguous()
     plan.Cout, plan.Cin, plan.act_dtype = pack.Cout, pack.Cin, act_dtype
     plan.segs = []
     for sg in pack.segs:
@@ -576,6 +583,24 @@ def wonly_forward(plan, xh, B, H, W, Ho, Wo, out_dtype=torch.float32, residual=N
     return out
 
 
+def wonly_forward_geglu(gplan, xh, M, next_plan):
+    """GEGLU projection (gplan: QuantModule.wonly_geglu_plan, packed with geglu_row_perm) with the value * gelu(gate) epilogue
+    of qd_conv2d_wq_h16 (QD_EPI_GEGLU_H16): returns the operand rows [M][next_plan.ldx] that `next_plan` (the FF output Linear)
+    reads, pad channels zero.  The [M][2F] intermediate of wonly_forward + wonly_geglu_rows is never written."""
+    F = gplan.Cout // 2
+    if gplan.pack.row_perm is None or len(gplan.segs) != 1 or gplan.Cout % 64:
+        raise hip.HipEngineError("wonly_forward_geglu: the projection must be packed with geglu_row_perm (F % 32 == 0, one segment)")
+    if not wonly_plain_plan(next_plan, F) or next_plan.act_dtype != gplan.act_dtype:
+        raise hip.HipEngineError("wonly_forward_geglu: the next layer must read the F GEGLU features as one plain segment of the same operand type")
+    out = torch.empty((M, next_plan.ldx), dtype=gplan.act_dtype, device=xh.device)
+    call = hip.ConvCall(x=xh, w=gplan.pack.wq, out=out, bias=gplan.bias, ldx=gplan.ldx, ldk=gplan.pack.ldk, ldo=next_plan.ldx,
+                        B=1, H=1, W=M, Ho=1, Wo=M, Cout=gplan.Cout, kh=1, kw=1, stride=1, pad_t=0, pad_l=0,
+                        wbits=gplan.pack.wbits, w_tiled=True, segs=gplan.segs, epilogue=hip.EPI_GEGLU_H16)
+    hip.conv2d_wq_h16(call, gplan.act_dtype)
+    WONLY_GEGLU_EPI[0] += 1
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # weights-only block fusion: the norms, GEGLU, the embedding add and the residual adds of a weights-only block as producers
 # and epilogues of the kernels above (qd_groupnorm_h16, qd_layernorm_h16, qd_geglu_h16, rowbias / residual of qd_conv2d_wq_h16)
@@ -600,6 +625,37 @@ WONLY_FUSED = {"resblock": 0, "transformer": 0}
 
 # widest LayerNorm row of qd_layernorm_h16
 WONLY_LN_CMAX = 2048
+
+# Wide fusion, on top of WEIGHT_ONLY_FUSE (effective only while wonly_fuse_state() holds): False (default) = the routes above
+# exactly; True = the transformer block's GEGLU rides in the epilogue of its projection (QD_EPI_GEGLU_H16: no fp32 [M][2F]
+# intermediate, no qd_geglu_h16 launch), and SpatialTransformer / QuantAttentionBlock write the operand rows of proj_in / qkv
+# with qd_groupnorm_h16 and add their input in proj_out's epilogue.  QDIFF_WEIGHT_ONLY_FUSE_WIDE=1, or
+# engine.set_weight_only_fusion_wide().
+WEIGHT_ONLY_FUSE_WIDE = _parse_flag(os.environ.get("QDIFF_WEIGHT_ONLY_FUSE_WIDE"), "QDIFF_WEIGHT_ONLY_FUSE_WIDE")
+
+# launches of the GEGLU epilogue (tests read it); WONLY_FUSED gets the keys "spatial" / "attnblock" when such a block takes
+# the wide route, never while the knob is off
+WONLY_GEGLU_EPI = [0]
+
+
+def set_weight_only_fusion_wide(on):
+    """True / False (or the strings QDIFF_WEIGHT_ONLY_FUSE_WIDE accepts)."""
+    global WEIGHT_ONLY_FUSE_WIDE
+    if isinstance(on, str):
+        on = _parse_flag(on, "QDIFF_WEIGHT_ONLY_FUSE_WIDE")
+    if not isinstance(on, bool):
+        raise ValueError("wide weight-only fusion must be True or False")
+    WEIGHT_ONLY_FUSE_WIDE = on
+
+
+def wonly_wide_state():
+    """The wide routes engage: the knob, and everything wonly_fuse_state() asks."""
+    return WEIGHT_ONLY_FUSE_WIDE and wonly_fuse_state()
+
+
+def wonly_count(kind):
+    """One more block forward of `kind` on a fused route (a default: tests replace WONLY_FUSED by a dict without the new keys)."""
+    WONLY_FUSED[kind] = WONLY_FUSED.get(kind, 0) + 1
 
 
 def set_weight_only_fusion(on):

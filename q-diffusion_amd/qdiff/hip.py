@@ -58,6 +58,7 @@ class RawQuant(ctypes.Structure):
 
 
 EPI_LINEAR, EPI_GEGLU_I8, EPI_HEADS_I8, EPI_HEADS_T_I8 = 0, 1, 2, 3
+EPI_GEGLU_H16 = 4          # qd_conv2d_wq_h16 only: value * gelu(gate) -> operand rows of the next layer
 
 
 EXPORTS = ["qd_abi_version", "qd_last_error", "qd_device_ok", "qd_box_probe", "qd_make_qparams", "qd_quantize_act", "qd_pack_weights", "qd_pack_weights_t4",
@@ -303,7 +304,7 @@ def _conv_desc(c):
     d.wbits = c.wbits
     d.w_tiled = 1 if c.w_tiled else 0
     d.epilogue = c.epilogue or EPI_LINEAR
-    if d.epilogue != EPI_LINEAR:
+    if d.epilogue not in (EPI_LINEAR, EPI_GEGLU_H16):
         c.oq_params = _qp(c.oq_params)              # kept on the call object: the pointer must outlive the launch
         d.oq_params = _ptr(c.oq_params, "oq_params")
         d.oq_min, d.oq_max, d.oq_off = c.oq_grid.qmin, c.oq_grid.qmax, c.oq_grid.off
@@ -314,6 +315,8 @@ def _conv_desc(c):
             d.hd_H, d.hd_d, d.hd_T, d.hd_Tpad, d.hd_dpad = hd["H"], hd["d"], hd["T"], hd["Tpad"], hd["dpad"]
             d.oq_prescale = float(hd["prescale"])
             d.hd_sum = _ptr(hd.get("sum"), "hd_sum")
+    elif d.epilogue == EPI_GEGLU_H16:
+        d.out_dtype = _H16[c.out.dtype]             # fp16 / bf16 operand rows (conv2d_wq_h16 checked the type)
     else:
         d.out_dtype = _dtype(c.out) if c.out is not None else F32
     d.gn_part = _ptr(c.gn_part, "gn_part")
@@ -393,6 +396,20 @@ def conv2d_wq_h16(c, act_dtype):
     """ConvCall whose x are fp16 / bf16 rows and whose segs carry scale = delta_w, zw = raw zero points (qd_conv2d_wq_h16)."""
     if act_dtype not in (torch.float16, torch.bfloat16):
         raise HipEngineError("conv2d_wq_h16: activations must be float16 or bfloat16")
+    if c.epilogue == EPI_GEGLU_H16:
+        # Cout = 2 F rows packed (value tile, gate tile) interleaved; out = operand rows [M][ldo >= F] of act_dtype
+        F = c.Cout // 2
+        if c.Cout % 2 or F % 32:
+            raise HipEngineError(f"conv2d_wq_h16: GEGLU epilogue needs Cout = 2 F with F % 32 == 0 (Cout={c.Cout})")
+        if len(c.segs) != 1 or c.residual is not None or c.rowbias is not None:
+            raise HipEngineError("conv2d_wq_h16: GEGLU epilogue takes one segment, no residual and no rowbias")
+        if c.out.dtype != act_dtype:
+            raise HipEngineError(f"conv2d_wq_h16: GEGLU epilogue writes operand rows of {act_dtype}, got out {c.out.dtype}")
+        if c.ldo < F or c.ldo % 8 or c.out.data_ptr() % 16:
+            raise HipEngineError(f"conv2d_wq_h16: GEGLU epilogue: output rows must be 16-byte aligned with ldo % 8 == 0 and "
+                                 f"ldo >= {F} (ldo {c.ldo})")
+    elif c.epilogue not in (None, EPI_LINEAR):
+        raise HipEngineError("conv2d_wq_h16: epilogue must be EPI_LINEAR or EPI_GEGLU_H16")
     d = _conv_desc(c)
     _check(load().qd_conv2d_wq_h16(ctypes.byref(d), _H16[act_dtype], _stream()), "qd_conv2d_wq_h16")
 

@@ -158,6 +158,49 @@ def _wonly_fuse_gate(block, layers, tensors):
             and _no_hooks(*list(block.modules())[1:]))
 
 
+def _wonly_wide_edges(block, x, first, last, C, Cmid):
+    """engine.WEIGHT_ONLY_FUSE_WIDE takes the edges of a SpatialTransformer / QuantAttentionBlock: the gate of the fused route
+    (_wonly_fuse_gate on the two projections: knobs, fp32 GPU input, unsplit, wonly_ready, no hook below the block), an
+    affine-or-not nn.GroupNorm over C % 8 == 0 channels in front of `first`, `first` reading those C channels and `last` its
+    Cmid input channels as one plain segment, both one-tap stride-1 layers, and `last` giving back C channels."""
+    if not engine.WEIGHT_ONLY_FUSE_WIDE or x.dim() != 4 or C % 8 or not isinstance(block.norm, nn.GroupNorm):
+        return False
+    if not _wonly_fuse_gate(block, (first, last), (x,)):
+        return False
+    pf, pl = first.wonly_plan(), last.wonly_plan()
+    one_tap = lambda p: (p.kh, p.kw, p.stride, p.pad) == (1, 1, 1, 0)
+    return (one_tap(pf) and one_tap(pl) and engine.wonly_plain_plan(pf, C) and engine.wonly_plain_plan(pl, Cmid)
+            and pf.Cout % 8 == 0 and pl.Cout == C)
+
+
+def spatial_wonly_wide(st, x):
+    """SpatialTransformer.forward takes the wide weights-only route for this call."""
+    return (engine.wonly_wide_state() and isinstance(st.proj_in, QuantModule) and isinstance(st.proj_out, QuantModule)
+            and st.proj_in.split == 0 and st.proj_out.split == 0 and st.proj_in.wonly_plan() is not None
+            and _wonly_wide_edges(st, x, st.proj_in, st.proj_out, x.shape[1], st.proj_in.wonly_plan().Cout))
+
+
+def spatial_forward_wonly(st, x, context):
+    """attention.py:262-287 in the weights-only state with the wide knob: qd_groupnorm_h16 (no SiLU) writes proj_in's operand
+    rows from the channels-last rows of x (made channels-last once here if it is not), the blocks see the token rows, and
+    proj_out adds x's rows in its epilogue.  A Linear proj_in / proj_out (`use_linear`) is the same on rows."""
+    b, c, h, w = x.shape
+    M = b * h * w
+    rows = _nhwc_rows(x)
+    pin, pout = st.proj_in.wonly_plan(), st.proj_out.wonly_plan()
+    xh = engine.wonly_groupnorm_rows(rows, b, h * w, c, st.norm, False, pin)
+    t = st.proj_in.forward_rows(xh, 1, 1, M, 1, M).view(b, h * w, pin.Cout)
+    for blk in st.transformer_blocks:
+        t = blk(t, context)
+    t = t.reshape(M, pin.Cout)
+    if t.stride(1) != 1:
+        t = t.contiguous()
+    th_ = engine.wonly_rows(t, pout, 1, pin.Cout, M, (0, 1, t.stride(0)))
+    out = st.proj_out.forward_rows(th_, 1, 1, M, 1, M, residual=rows)
+    engine.wonly_count("spatial")
+    return _rows_to_nchw(out, b, h, w)
+
+
 def _gn_silu_to(conv, rows, B, S, C, gn, silu=True, raw_plan=None, mod=None):
     """GroupNorm(+SiLU) -> int8 rows for `conv`; initialises conv's act quantiser on first use.
     raw_plan: also return the int8 rows of a 1x1 consumer of the un-normalised `rows` (the skip connection), quantised
@@ -880,6 +923,9 @@ class QuantAttentionBlock(BaseQuantBlock, _AttnQuant):
             if plans is not None and all(engine.heads_fusable(p, T, self.num_heads) for p in plans):
                 return self._forward_heads(x, plans, out_slot)
             return self._forward_int(x, out_slot)
+        if (engine.WEIGHT_ONLY_FUSE_WIDE and not self.use_act_quant and isinstance(self.qkv, QuantModule) and isinstance(self.proj_out, QuantModule)
+                and _wonly_wide_edges(self, x, self.qkv, self.proj_out, c, c)):
+            return self._forward_wonly_wide(x)
         xf = x.reshape(b, c, -1)
         qkv = self.qkv(self.norm(xf))
         if self._wonly_attention_ok(qkv):
@@ -887,6 +933,24 @@ class QuantAttentionBlock(BaseQuantBlock, _AttnQuant):
         else:
             h = self.proj_out(self.attention(qkv))
         return (xf + h).reshape(b, c, *spatial)
+
+    def _forward_wonly_wide(self, x):
+        """Reference :175-187 in the weights-only state with engine.WEIGHT_ONLY_FUSE_WIDE: qd_groupnorm_h16 (no SiLU) writes
+        qkv's operand rows from the channels-last rows of x, the attention is qd_attn_h16 when its gate holds (else the library
+        attention), and proj_out adds x's rows in its epilogue."""
+        b, c, H, W = x.shape
+        T = H * W
+        rows = _nhwc_rows(x)
+        xh = engine.wonly_groupnorm_rows(rows, b, T, c, self.norm, False, self.qkv.wonly_plan())
+        q = self.qkv.forward_rows(xh, 1, 1, b * T, 1, b * T)
+        qkv = q.view(b, T, q.shape[1]).permute(0, 2, 1)
+        a = self._attention_h16(qkv) if self._wonly_attention_ok(qkv) else self.attention(qkv)
+        if a.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            a = a.float()
+        ah = engine.wonly_rows(a, self.proj_out.wonly_plan(), b, c, T, a.stride())
+        out = self.proj_out.forward_rows(ah, 1, 1, b * T, 1, b * T, residual=rows)
+        engine.wonly_count("attnblock")
+        return _rows_to_nchw(out, b, H, W)
 
     def _wonly_attention_ok(self, qkv):
         """engine.attention_h16 replaces self.attention(qkv): the repo's (or the reference's) QKVAttentionLegacy whose two
@@ -1136,8 +1200,14 @@ class QuantBasicTransformerBlock(BaseQuantBlock, _AttnQuant):
         rows = self._attn_wonly(self.attn2, rows, B, T, C, self.norm2, context)
         proj, ff_out = self.ff.net[0].proj, self.ff.net[-1]
         xh = engine.wonly_layernorm_rows(rows, M, C, self.norm3, proj.wonly_plan())
-        hcat = proj.forward_rows(xh, 1, 1, M)
-        gh = engine.wonly_geglu_rows(hcat, M, hcat.shape[1] // 2, ff_out.wonly_plan())
+        gplan = proj.wonly_geglu_plan() if engine.wonly_wide_state() else None
+        if gplan is not None and gplan.ldx == xh.shape[1]:
+            # engine.WEIGHT_ONLY_FUSE_WIDE: value * gelu(gate) in the projection's epilogue, the same bytes without the
+            # fp32 [M][2F] intermediate
+            gh = engine.wonly_forward_geglu(gplan, xh, M, ff_out.wonly_plan())
+        else:
+            hcat = proj.forward_rows(xh, 1, 1, M)
+            gh = engine.wonly_geglu_rows(hcat, M, hcat.shape[1] // 2, ff_out.wonly_plan())
         rows = ff_out.forward_rows(gh, 1, 1, M, residual=rows)
         engine.WONLY_FUSED["transformer"] += 1
         return rows.view(B, T, C)

@@ -448,6 +448,7 @@ class QuantModule(nn.Module):
         engine.bump_state()
         self._pack_key = self._plan_key = self._wdq_key = None
         self.__dict__.pop('_wonly_cache', None)
+        self.__dict__.pop('_wonly_geglu_cache', None)
         self.__dict__.pop('_geglu_cache', None)
         self.__dict__.pop('_heads_cache', None)
         self.__dict__.pop('_frozen_pack', None)
@@ -462,6 +463,7 @@ class QuantModule(nn.Module):
         self.__dict__['_frozen_geglu_pack'] = geglu_pack
         self._pack_key = self._plan_key = None
         self.__dict__.pop('_wonly_cache', None)
+        self.__dict__.pop('_wonly_geglu_cache', None)
         self.__dict__.pop('_geglu_cache', None)
         self.__dict__.pop('_heads_cache', None)
 
@@ -584,6 +586,40 @@ class QuantModule(nn.Module):
                 self._pack, self._pack_key, self._plan_key = pack, wkey, None
         kh, kw, stride, pad = geo
         plan = engine.build_wonly_plan(pack, kh, kw, stride, pad, self.bias, dt) if pack is not None else None
+        cache[0], cache[1] = key, plan
+        return plan
+
+    def wonly_geglu_plan(self):
+        """engine.WonlyPlan of a GEGLU projection over the (value tile, gate tile) interleaved pack, for the value * gelu(gate)
+        epilogue of the weights-only contraction (engine.wonly_forward_geglu), or None: not a Linear, a split input, halves
+        that are not whole 32-row tiles, a weight quantiser the packer refuses, bf16 operands with |q - z| > 256.  The pack is,
+        in this order, the interleaved pack of a packed checkpoint, the layer's own (possibly frozen) pack gathered tile by tile
+        — nothing is re-quantised, so freed fp32 weights are no obstacle — or a fresh pack of the permuted rows.  Like
+        wonly_plan() it never touches the activation quantisers, is cached under the weight part of plan_keys() and the
+        operand type, and is dropped by invalidate() / load_packed()."""
+        dt = engine.WEIGHT_ONLY_KERNEL
+        if dt is None or self.kind != 'linear' or self.split != 0:
+            return None
+        wkey, akey = self.plan_keys()
+        key = (wkey, akey[2], dt)
+        cache = self.__dict__.setdefault('_wonly_geglu_cache', [None, None])
+        if cache[0] == key:
+            return cache[1]
+        plan = None
+        base = self.wonly_plan()                             # the layer's own pack (frozen, the integer path's, or fresh)
+        if base is not None and base.Cout % 64 == 0:
+            F = base.Cout // 2
+            pack = self.__dict__.get('_frozen_geglu_pack')
+            if pack is None:
+                pack = engine.pack_select_tiles(base.pack, engine.geglu_row_perm(F, base.pack.wq.device))
+            if pack is None and not self._weights_freed():
+                try:
+                    pack = engine.pack_module_weights(self.weight, self._weight_quantizers(), 0,
+                                                      row_perm=engine.geglu_row_perm(F, self.weight.device))
+                except hip.HipEngineError:
+                    pack = None
+            if pack is not None:
+                plan = engine.build_wonly_plan(pack, 1, 1, 1, 0, self.bias, dt, geglu=True)
         cache[0], cache[1] = key, plan
         return plan
 

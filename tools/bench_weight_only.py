@@ -236,6 +236,91 @@ def run_fuse(kind, batch, k, dev, attn, rounds):
     return res
 
 
+def run_wide(kind, batch, k, dev, attn, rounds):
+    """Layer knob fp16, block fusion on, engine.WEIGHT_ONLY_FUSE_WIDE off / on alternated `rounds` times in one process."""
+    import bench
+    from qdiff import engine, hip, synthetic
+    qnn, _ = bench.build_quantised_unet(kind, dev)
+    x, t, c = synthetic.synthetic_inputs(kind, batch, seed=0)
+    args = [a.to(dev) for a in (x, t, c) if a is not None]
+    qnn.set_quant_state(True, False)
+    one = lambda: qnn(*args)
+    res = {"model": kind, "batch": batch, "layer_knob": "fp16", "attn_knob": "fp16" if attn else "off", "fuse": True, "evals_timed": k, "rounds": rounds}
+    prev = (engine.WEIGHT_ONLY_KERNEL, engine.WEIGHT_ONLY_ATTN, engine.WEIGHT_ONLY_FUSE, engine.WEIGHT_ONLY_FUSE_WIDE)
+    try:
+        engine.set_weight_only_kernel(torch.float16)
+        engine.set_weight_only_attention(torch.float16 if attn else None)
+        engine.set_weight_only_fusion(True)
+        ms, ticks = hip.box_probe(dev, 0, 512, 60000)
+        res["box_probe_mfma_ms"] = round(ms, 3)
+        off, on = [], []
+        for _ in range(rounds):                                  # alternated A/B
+            engine.set_weight_only_fusion_wide(False)
+            off.append(_timed(one, k))
+            engine.set_weight_only_fusion_wide(True)
+            on.append(_timed(one, k))
+        res["wide_off_ms"], res["wide_on_ms"] = round(min(off), 3), round(min(on), 3)
+        res["wide_off_ms_all"], res["wide_on_ms_all"] = [round(v, 3) for v in off], [round(v, 3) for v in on]
+        res["wide_off_spread_ms"], res["wide_on_spread_ms"] = round(max(off) - min(off), 3), round(max(on) - min(on), 3)
+        res["faster_by_more_than_spread"] = bool(min(off) - max(on) > 0 and min(off) - min(on) > max(max(off) - min(off), max(on) - min(on)))
+        outs = {}
+        for name, flag in (("off", False), ("on", True)):
+            engine.set_weight_only_fusion_wide(flag)
+            engine.WONLY_FUSED.pop("spatial", None)
+            engine.WONLY_FUSED.pop("attnblock", None)
+            for k2 in engine.WONLY_FUSED:
+                engine.WONLY_FUSED[k2] = 0
+            engine.WONLY_GEGLU_EPI[0] = 0
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats(dev)
+            with torch.no_grad():
+                outs[name] = one()
+            torch.cuda.synchronize()
+            res[f"wide_{name}_max_mem_mib"] = round(torch.cuda.max_memory_allocated(dev) / 2 ** 20, 1)
+            res[f"wide_{name}_blocks"] = dict(engine.WONLY_FUSED, geglu_epilogues=engine.WONLY_GEGLU_EPI[0])
+        res["wide_on_vs_off_of_range"] = float((outs["on"] - outs["off"]).abs().max() / outs["off"].abs().max())
+    finally:
+        engine.set_weight_only_kernel(prev[0])
+        engine.set_weight_only_attention(prev[1])
+        engine.set_weight_only_fusion(prev[2])
+        engine.set_weight_only_fusion_wide(prev[3])
+        engine.WONLY_FUSED.pop("spatial", None)
+        engine.WONLY_FUSED.pop("attnblock", None)
+    return res
+
+
+def wide_shape_table(dev):
+    """The GEGLU projection alone at SD's three shapes (W4, fp16): one launch with the GEGLU epilogue on the interleaved pack
+    against the linear launch (fp32 [M][2F]) + qd_geglu_h16 on the same weights."""
+    from types import SimpleNamespace as NS
+    from qdiff import engine, hip
+    g = torch.Generator(device=dev).manual_seed(0)
+    for M, C in SD_LN_SHAPES:
+        Fd = 4 * C
+        w = torch.randn(2 * Fd, C, device=dev, generator=g) * 0.05
+        flat_min, flat_max = w.min(1)[0].clamp(max=0), w.max(1)[0].clamp(min=0)
+        d = ((flat_max - flat_min) / 15).clamp(min=1e-8)
+        q = NS(delta=d, zero_point=torch.round(-flat_min / d), n_bits=4, n_levels=16, sym=False, alpha=None, soft_targets=False)
+        bias = torch.randn(2 * Fd, device=dev, generator=g)
+        pack = engine.pack_module_weights(w, [q], 0)
+        plan = engine.build_wonly_plan(pack, 1, 1, 1, 0, bias, torch.float16)
+        gplan = engine.build_wonly_plan(engine.pack_select_tiles(pack, engine.geglu_row_perm(Fd, dev)), 1, 1, 1, 0, bias, torch.float16, geglu=True)
+        nxt = NS(segs=[dict(c0=0)], pack=NS(segs=[dict(c0w=0, clen=Fd)]), ldx=Fd, act_dtype=torch.float16)   # the FF output's row layout
+        xh = torch.randn(M, C, device=dev, generator=g).half()
+        o2 = torch.empty(M, Fd, dtype=torch.float16, device=dev)
+
+        def two():
+            h = engine.wonly_forward(plan, xh, 1, 1, M, 1, M)
+            hip.geglu_h16(h, M, Fd, 2 * Fd, o2, Fd)
+
+        lin = 1000 * _events_ms(lambda: engine.wonly_forward(plan, xh, 1, 1, M, 1, M), 20)
+        both = 1000 * _events_ms(two, 20)
+        epi = 1000 * _events_ms(lambda: engine.wonly_forward_geglu(gplan, xh, M, nxt), 20)
+        print(json.dumps({"op": "geglu_projection", "M": M, "K": C, "F": Fd, "linear_us": round(lin, 1), "linear_plus_geglu_h16_us": round(both, 1),
+                          "geglu_epilogue_us": round(epi, 1), "speedup": round(both / epi, 2)}), flush=True)
+        del w, pack, plan, gplan, xh, o2
+
+
 STREAM_CEILING_GBS = 6300.0        # HBM streaming ceiling of element-wise kernels (cdna_hip_programming.md Appendix B)
 # SD-v1.4 at batch 16: (tokens M = 16 * H * W, channels C) of the four latent levels; GroupNorm also at the widths of the
 # concatenated up-path inputs
@@ -316,6 +401,8 @@ def main():
     ap.add_argument("--fuse", action="store_true", help="the block-fusion column (layer kernel at fp16; with --attn the attention kernel too)")
     ap.add_argument("--rounds", type=int, default=3, help="A/B alternations of --fuse")
     ap.add_argument("--fuse-shapes", action="store_true", help="the three producers alone at SD's shapes")
+    ap.add_argument("--wide", action="store_true", help="with --fuse: the wide-fusion column (fusion on, wide off / on alternated) and the "
+                                                        "GEGLU projection alone at SD's three shapes")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     from qdiff import hip
@@ -325,8 +412,12 @@ def main():
         attn_shape_table(dev, SD_SHAPES + LDM_SHAPES)
     if a.fuse_shapes:
         fuse_shape_table(dev)
+    if a.wide:
+        wide_shape_table(dev)
     for kind in a.models.split(","):
-        if a.fuse:
+        if a.wide:
+            res = run_wide(kind, a.batch, a.evals, dev, a.attn, a.rounds)
+        elif a.fuse:
             res = run_fuse(kind, a.batch, a.evals, dev, a.attn, a.rounds)
         else:
             res = (run_attn if a.attn else run)(kind, a.batch, a.evals, dev)
