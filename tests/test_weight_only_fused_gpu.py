@@ -69,25 +69,45 @@ def _check_rows(buf, out, C, ref, tol, what):
 
 
 # ---- LayerNorm -------------------------------------------------------------------------------------------------------------
-def _ln_case(dev, seed, C, M, xdt, odt, pad, gscale=1.0, drop_beta=False):
-    from qdiff import hip
-    g = torch.Generator().manual_seed(seed)
-    x = (torch.randn(M, C, generator=g) * (0.2 + 3 * torch.rand(M, 1, generator=g)) + torch.randn(M, 1, generator=g)).to(xdt)
-    gamma, beta = 1 + 0.3 * torch.randn(C, generator=g), 0.3 * torch.randn(C, generator=g)
-    eps = 1e-5
-    xd = x.double()
+def _ln_ref(x, gamma, beta, eps):
+    """fp64 LayerNorm of the rows x [M, C] (any float type, any device) and the fp32 term T of the bound, both on the CPU."""
+    C = x.shape[1]
+    xd, gd, bd = x.double().cpu(), gamma.double().cpu(), beta.double().cpu()
     m = xd.mean(1, keepdim=True)
     r = 1 / torch.sqrt(xd.var(1, unbiased=False, keepdim=True) + eps)
     z = (xd - m) * r
-    ref = z * gamma.double() + beta.double()
-    T = U * (gamma.double().abs() * r * ((xd - m).abs() + C * xd.abs().mean(1, keepdim=True)) + (C / 2 + 12) * (z * gamma.double()).abs()
-             + 2 * ((z * gamma.double()).abs() + beta.double().abs()))
+    ref = z * gd + bd
+    T = U * (gd.abs() * r * ((xd - m).abs() + C * xd.abs().mean(1, keepdim=True)) + (C / 2 + 12) * (z * gd).abs()
+             + 2 * ((z * gd).abs() + bd.abs()))
+    return ref, T
+
+
+def _ln_lib(x, gamma, beta, eps, odt):
+    """The library's fp32 LayerNorm followed by the cast, on the device of x."""
+    return F.layer_norm(x.float(), (x.shape[1],), gamma.to(x.device), beta.to(x.device), eps).to(odt)
+
+
+def _ln_launch(dev, x, gamma, beta, eps, odt, pad):
+    """qd_layernorm_h16 of the CPU rows x into guarded rows on dev -> (buffer, rows)."""
+    from qdiff import hip
+    M, C = x.shape
+    buf, out = _guarded(M, C + pad, odt, dev)
+    hip.layernorm_h16(x.to(dev), M, C, C, eps, gamma.to(dev), beta.to(dev), out, C + pad)
+    return buf, out
+
+
+def _ln_case(dev, seed, C, M, xdt, odt, pad, gscale=1.0, drop_beta=False, x=None, gamma=None, beta=None):
+    g = torch.Generator().manual_seed(seed)
+    if x is None:
+        x = (torch.randn(M, C, generator=g) * (0.2 + 3 * torch.rand(M, 1, generator=g)) + torch.randn(M, 1, generator=g)).to(xdt)
+    if gamma is None:
+        gamma, beta = 1 + 0.3 * torch.randn(C, generator=g), 0.3 * torch.randn(C, generator=g)
+    eps = 1e-5
+    ref, T = _ln_ref(x, gamma, beta, eps)
     tol = _half_ulp(ref, odt) + T
-    ldo = C + pad
-    buf, out = _guarded(M, ldo, odt, dev)
-    hip.layernorm_h16(x.to(dev), M, C, C, eps, (gamma * gscale).to(dev), (torch.zeros(C) if drop_beta else beta).to(dev), out, ldo)
+    buf, out = _ln_launch(dev, x, gamma * gscale, torch.zeros(C) if drop_beta else beta, eps, odt, pad)
     worst = _check_rows(buf, out, C, ref, tol, f"layernorm C={C} M={M}")
-    lib = F.layer_norm(x.to(dev).float(), (C,), gamma.to(dev), beta.to(dev), eps).to(odt)
+    lib = _ln_lib(x.to(dev), gamma, beta, eps, odt)
     worst_lib = ((lib.double().cpu() - ref).abs() / tol).max().item()
     return worst, worst_lib
 
@@ -125,24 +145,43 @@ def test_layernorm_bound_bites(cuda, odt):
 
 
 # ---- GEGLU -------------------------------------------------------------------------------------------------------------------
-def _geglu_case(dev, seed, Fd, M, xdt, odt, pad, tanh=False):
-    from qdiff import hip
-    g = torch.Generator().manual_seed(seed)
-    h = (torch.randn(M, 2 * Fd, generator=g) * 2.5).to(xdt)
-    hd = h.double()
-    a, gt = hd[:, :Fd], hd[:, Fd:]
+def _geglu_ref(h, Fd):
+    """fp64 GEGLU of the rows h [M, >= 2 F] (value columns first) and the fp32 term T of the bound, both on the CPU."""
+    hd = h.double().cpu()
+    a, gt = hd[:, :Fd], hd[:, Fd:2 * Fd]
     ref = a * (0.5 * gt * (1 + torch.erf(gt / math.sqrt(2))))
-    tol = _half_ulp(ref, odt) + 2.0 ** -23 * (a * gt).abs() + 3 * U * ref.abs()
-    ldo = Fd + pad
-    buf, out = _guarded(M, ldo, odt, dev)
+    return ref, 2.0 ** -23 * (a * gt).abs() + 3 * U * ref.abs()
+
+
+def _geglu_lib(h, Fd, odt):
+    """The library's fp32 GELU times the value followed by the cast, on the device of h."""
+    hl = h.float()
+    return (hl[:, :Fd] * F.gelu(hl[:, Fd:2 * Fd])).to(odt)
+
+
+def _geglu_launch(dev, h, Fd, odt, pad):
+    """qd_geglu_h16 of the CPU rows h into guarded rows on dev -> (buffer, rows)."""
+    from qdiff import hip
+    M = h.shape[0]
+    buf, out = _guarded(M, Fd + pad, odt, dev)
+    hip.geglu_h16(h.to(dev), M, Fd, h.shape[1], out, Fd + pad)
+    return buf, out
+
+
+def _geglu_case(dev, seed, Fd, M, xdt, odt, pad, tanh=False, h=None):
+    g = torch.Generator().manual_seed(seed)
+    if h is None:
+        h = (torch.randn(M, 2 * Fd, generator=g) * 2.5).to(xdt)
+    ref, T = _geglu_ref(h, Fd)
+    tol = _half_ulp(ref, odt) + T
     if tanh:                                                 # what a kernel with the tanh approximation would write
+        buf, out = _guarded(M, Fd + pad, odt, dev)
         out[:, :Fd] = (h.to(dev).float()[:, :Fd] * F.gelu(h.to(dev).float()[:, Fd:], approximate="tanh")).to(odt)
         out[:, Fd:] = 0
     else:
-        hip.geglu_h16(h.to(dev), M, Fd, 2 * Fd, out, ldo)
+        buf, out = _geglu_launch(dev, h, Fd, odt, pad)
     worst = _check_rows(buf, out, Fd, ref, tol, f"geglu F={Fd} M={M}")
-    hl = h.to(dev).float()
-    lib = (hl[:, :Fd] * F.gelu(hl[:, Fd:])).to(odt)
+    lib = _geglu_lib(h.to(dev), Fd, odt)
     return worst, ((lib.double().cpu() - ref).abs() / tol).max().item()
 
 
@@ -164,34 +203,53 @@ def test_geglu_bound_bites(cuda, odt):
 
 
 # ---- GroupNorm (+ SiLU) ------------------------------------------------------------------------------------------------------
-def _gn_case(dev, seed, C, S, B, xdt, odt, pad, silu, groups=None, gscale=1.0, drop_beta=False):
-    from qdiff import hip
-    G = groups or (32 if C % 32 == 0 else 8 if C % 8 == 0 else 1)
-    g = torch.Generator().manual_seed(seed)
-    x = (torch.randn(B, S, C, generator=g) * (0.3 + 2 * torch.rand(1, 1, C, generator=g)) + 0.5 * torch.randn(1, 1, C, generator=g)).to(xdt)
-    gamma, beta = 1 + 0.3 * torch.randn(C, generator=g), 0.3 * torch.randn(C, generator=g)
-    eps = 1e-5
-    xd = x.double().view(B, S, G, C // G)
+def _gn_ref(x, G, gamma, beta, eps, silu):
+    """fp64 GroupNorm (+ SiLU) of x [B, S, C] as rows [B * S, C] and the fp32 term T of the bound, both on the CPU."""
+    B, S, C = x.shape
+    xd = x.double().cpu().view(B, S, G, C // G)
     m = xd.mean((1, 3), keepdim=True)
     var = xd.var((1, 3), unbiased=False, keepdim=True)
     ex2, eabs = (xd * xd).mean((1, 3), keepdim=True), xd.abs().mean((1, 3), keepdim=True)
-    gm, bt = gamma.double().view(1, 1, G, C // G), beta.double().view(1, 1, G, C // G)
+    gm, bt = gamma.double().cpu().view(1, 1, G, C // G), beta.double().cpu().view(1, 1, G, C // G)
     a = gm / torch.sqrt(var + eps)
     y = (xd - m) * a + bt
     ref = y * torch.sigmoid(y) if silu else y
     dm = 33 * U * eabs
     rho = (33 * U * ex2 + 2 * m.abs() * dm) / (2 * (var + eps)) + 2 * U
     T = 1.1 * (((xd * a).abs() + (m * a).abs()) * (rho + 3 * U) + a.abs() * dm + U * (bt.abs() + y.abs())) + (y.abs() + 6) * U * ref.abs()
-    ref, T = ref.reshape(B * S, C), T.reshape(B * S, C)
-    tol = _half_ulp(ref, odt) + T
-    ldo = C + pad
-    buf, out = _guarded(B * S, ldo, odt, dev)
+    return ref.reshape(B * S, C), T.reshape(B * S, C)
+
+
+def _gn_lib(x, G, gamma, beta, eps, silu, odt):
+    """The library's fp32 GroupNorm (+ SiLU) followed by the cast, as rows [B * S, C], on the device of x."""
+    B, S, C = x.shape
+    lib = F.group_norm(x.float().permute(0, 2, 1), G, gamma.to(x.device), beta.to(x.device), eps)
+    return (F.silu(lib) if silu else lib).permute(0, 2, 1).reshape(B * S, C).to(odt)
+
+
+def _gn_launch(dev, x, G, gamma, beta, eps, silu, odt, pad):
+    """qd_groupnorm_h16 of the CPU tensor x [B, S, C] into guarded rows on dev -> (buffer, rows)."""
+    from qdiff import hip
+    B, S, C = x.shape
+    buf, out = _guarded(B * S, C + pad, odt, dev)
     ws = torch.empty(hip.groupnorm_ws_bytes(B, C, S), dtype=torch.uint8, device=dev)
-    hip.groupnorm_h16(x.to(dev).view(B * S, C), B, S, C, C, G, eps, (gamma * gscale).to(dev), (torch.zeros(C) if drop_beta else beta).to(dev),
-                      silu, out, ldo, ws)
+    hip.groupnorm_h16(x.to(dev).view(B * S, C), B, S, C, C, G, eps, gamma.to(dev), beta.to(dev), silu, out, C + pad, ws)
+    return buf, out
+
+
+def _gn_case(dev, seed, C, S, B, xdt, odt, pad, silu, groups=None, gscale=1.0, drop_beta=False, x=None, gamma=None, beta=None):
+    G = groups or (32 if C % 32 == 0 else 8 if C % 8 == 0 else 1)
+    g = torch.Generator().manual_seed(seed)
+    if x is None:
+        x = (torch.randn(B, S, C, generator=g) * (0.3 + 2 * torch.rand(1, 1, C, generator=g)) + 0.5 * torch.randn(1, 1, C, generator=g)).to(xdt)
+    if gamma is None:
+        gamma, beta = 1 + 0.3 * torch.randn(C, generator=g), 0.3 * torch.randn(C, generator=g)
+    eps = 1e-5
+    ref, T = _gn_ref(x, G, gamma, beta, eps, silu)
+    tol = _half_ulp(ref, odt) + T
+    buf, out = _gn_launch(dev, x, G, gamma * gscale, torch.zeros(C) if drop_beta else beta, eps, silu, odt, pad)
     worst = _check_rows(buf, out, C, ref, tol, f"groupnorm C={C} S={S} B={B}")
-    lib = F.group_norm(x.to(dev).float().permute(0, 2, 1), G, gamma.to(dev), beta.to(dev), eps)
-    lib = (F.silu(lib) if silu else lib).permute(0, 2, 1).reshape(B * S, C).to(odt)
+    lib = _gn_lib(x.to(dev), G, gamma, beta, eps, silu, odt)
     return worst, ((lib.double().cpu() - ref).abs() / tol).max().item()
 
 

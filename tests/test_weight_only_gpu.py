@@ -67,13 +67,52 @@ def _fp64_conv(kind, x, w, stride, pad):
     return F.linear(x, w)
 
 
-def _run_case(dev, kind, wbits, act, out_dtype, split, B, Cin, Cout, H, W, k, stride, has_bias, has_res, zmode, seed):
+def _contraction_ref(kind, x, w, qs, bounds, bias, res, act, out_dtype, stride, pad):
+    """fp64 contraction of the SAME rounded operands (x rounded to `act`, weight (q - z) * delta per segment of `bounds`) plus
+    bias and residual, as rows [M, Cout], and the bound of the module docstring: (ref, tol, dequantised weight [Cout, Cin...])."""
+    Cout, Cin = w.shape[0], w.shape[1]
+    kh, kw = (w.shape[2], w.shape[3]) if kind == "conv2d" else (1, 1)
+    xr = x.to(act).double()
+    ref = torch.zeros(())
+    S = torch.zeros(())
+    wqs = []
+    for (a, b), q in zip(bounds, qs):
+        wq = ((_codes(w[:, a:b], q) - q.zero_point.view((-1,) + (1,) * (w.dim() - 1))) * q.delta.view((-1,) + (1,) * (w.dim() - 1))).double()
+        wqs.append(wq)
+        xs = xr[:, a:b] if kind != "linear" else xr[..., a:b]
+        ref = ref + _fp64_conv(kind, xs, wq, stride, pad)
+        S = S + _fp64_conv(kind, xs.abs(), wq.abs(), stride, pad)
+    M = ref.numel() // Cout
+    if kind == "conv2d":
+        ref, S = ref.permute(0, 2, 3, 1).reshape(M, Cout), S.permute(0, 2, 3, 1).reshape(M, Cout)
+    elif kind == "conv1d":
+        ref, S = ref.permute(0, 2, 1).reshape(M, Cout), S.permute(0, 2, 1).reshape(M, Cout)
+    else:
+        ref, S = ref.reshape(M, Cout), S.reshape(M, Cout)
+    extra = torch.zeros(M, Cout, dtype=torch.float64)
+    if bias is not None:
+        ref = ref + bias.double()
+        extra = extra + bias.double().abs()
+    if res is not None:
+        ref = ref + res.double()
+        extra = extra + res.double().abs()
+    K = kh * kw * Cin
+    tol = K * 2.0 ** -26 * S + 2.0 ** -22 * (extra + ref.abs())
+    if out_dtype == torch.float16:                     # + the rounding of the fp32 value to fp16 (and its subnormal step)
+        tol = tol * (1 + 2.0 ** -11) + 2.0 ** -11 * ref.abs() + 2.0 ** -24
+    return ref, tol, torch.cat(wqs, 1)
+
+
+def _run_case(dev, kind, wbits, act, out_dtype, split, B, Cin, Cout, H, W, k, stride, has_bias, has_res, zmode, seed, x=None, w=None, qs=None):
+    """One launch against the fp64 bound; x, w and the per-segment quantisers qs are drawn from `seed` unless given."""
     from qdiff import engine
     g = torch.Generator().manual_seed(seed)
-    x, w = _layer(kind, B, Cin, Cout, H, W, k, stride, g)
+    if x is None:
+        x, w = _layer(kind, B, Cin, Cout, H, W, k, stride, g)
     pad = k // 2 if kind == "conv2d" else 0
     bounds = [(0, Cin)] if not split else [(0, split), (split, Cin)]
-    qs = [_wquant(w[:, a:b], wbits, zmode, g) for a, b in bounds]
+    if qs is None:
+        qs = [_wquant(w[:, a:b], wbits, zmode, g) for a, b in bounds]
     bias = torch.randn(Cout, generator=g) if has_bias else None
     pack = engine.pack_module_weights(w.to(dev), [NS(**{**vars(q), "delta": q.delta.to(dev), "zero_point": q.zero_point.to(dev)})
                                                    for q in qs], split or 0)
@@ -99,32 +138,7 @@ def _run_case(dev, kind, wbits, act, out_dtype, split, B, Cin, Cout, H, W, k, st
     out = engine.wonly_forward(plan, xh, *geo, out_dtype=out_dtype, residual=None if res is None else res.to(dev))
     torch.cuda.synchronize()
     got = out.double().cpu()
-    # fp64 reference on the same rounded operands
-    xr = x.to(act).double()
-    ref = torch.zeros(())
-    S = torch.zeros(())
-    for (a, b), q in zip(bounds, qs):
-        wq = ((_codes(w[:, a:b], q) - q.zero_point.view((-1,) + (1,) * (w.dim() - 1))) * q.delta.view((-1,) + (1,) * (w.dim() - 1))).double()
-        xs = xr[:, a:b] if kind != "linear" else xr[..., a:b]
-        ref = ref + _fp64_conv(kind, xs, wq, stride, pad)
-        S = S + _fp64_conv(kind, xs.abs(), wq.abs(), stride, pad)
-    if kind == "conv2d":
-        ref, S = ref.permute(0, 2, 3, 1).reshape(M, Cout), S.permute(0, 2, 3, 1).reshape(M, Cout)
-    elif kind == "conv1d":
-        ref, S = ref.permute(0, 2, 1).reshape(M, Cout), S.permute(0, 2, 1).reshape(M, Cout)
-    else:
-        ref, S = ref.reshape(M, Cout), S.reshape(M, Cout)
-    extra = torch.zeros(M, Cout, dtype=torch.float64)
-    if bias is not None:
-        ref = ref + bias.double()
-        extra = extra + bias.double().abs()
-    if res is not None:
-        ref = ref + res.double()
-        extra = extra + res.double().abs()
-    K = kh * kw * Cin
-    tol = K * 2.0 ** -26 * S + 2.0 ** -22 * (extra + ref.abs())
-    if out_dtype == torch.float16:                     # + the rounding of the fp32 value to fp16 (and its subnormal step)
-        tol = tol * (1 + 2.0 ** -11) + 2.0 ** -11 * ref.abs() + 2.0 ** -24
+    ref, tol, _ = _contraction_ref(kind, x, w, qs, bounds, bias, res, act, out_dtype, stride, pad)
     err = (got - ref).abs()
     worst = (err / tol).max().item()
     assert worst <= 1.0, (f"{kind} W{wbits} {act} -> {out_dtype} split={split} B={B} Cin={Cin} Cout={Cout} {H}x{W} k={k} s={stride}: "

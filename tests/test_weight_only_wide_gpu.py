@@ -53,13 +53,15 @@ def _reset(engine):
 
 
 # ---- the epilogue alone ------------------------------------------------------------------------------------------------------
-def _epi_setup(dev, seed, wbits, act, Fd, K, M, pad, via_tiles=False, edges=False):
-    """One GEGLU projection [2F][K]: the un-permuted plan, the interleaved plan, the rounded operand rows and the host copies."""
-    from qdiff import engine
+def _epi_host(seed, wbits, act, Fd, K, M, pad, edges=False, x=None, bias=None, dscale=1.0):
+    """Host side of one GEGLU projection [2F][K]: activations, weights, bias and the per-channel quantiser.  x / bias replace the
+    drawn ones; dscale (a power of two) scales weights, delta and bias alike: the same codes, every projection times dscale."""
     g = torch.Generator().manual_seed(seed)
-    x = torch.randn(M, K, generator=g)
+    xr = torch.randn(M, K, generator=g)
     w = torch.randn(2 * Fd, K, generator=g) * (2.0 / math.sqrt(K))
-    bias = torch.randn(2 * Fd, generator=g)
+    br = torch.randn(2 * Fd, generator=g)
+    x = xr if x is None else x.clone()
+    bias = br * dscale if bias is None else bias.clone()
     if edges:                                   # rows of zeros: value / gate are then the bias itself, placed at the edges
         x[:min(M, 4)] = 0
         vals = torch.tensor([BRANCH, -BRANCH, 12.0, -12.0, 40.0, -40.0, 0.0, 3e4, -3e4], dtype=torch.float32)
@@ -67,15 +69,24 @@ def _epi_setup(dev, seed, wbits, act, Fd, K, M, pad, via_tiles=False, edges=Fals
             vals = torch.cat([vals, torch.nextafter(vals[:2], vals[:2] + d)])
         bias[Fd:Fd + min(Fd, vals.numel())] = vals[:min(Fd, vals.numel())]
     q = _wquant(w, wbits, "range", g)
-    qd = NS(**{**vars(q), "delta": q.delta.to(dev), "zero_point": q.zero_point.to(dev)})
-    pack = engine.pack_module_weights(w.to(dev), [qd], 0)
+    q.delta = q.delta * dscale
+    return NS(x=x, w=w * dscale, bias=bias, q=q, M=M, F=Fd, K=K, ldo=Fd + pad, act=act)
+
+
+def _epi_setup(dev, seed, wbits, act, Fd, K, M, pad, via_tiles=False, edges=False, host=None):
+    """One GEGLU projection [2F][K]: the un-permuted plan, the interleaved plan, the rounded operand rows and the host copies."""
+    from qdiff import engine
+    s = host or _epi_host(seed, wbits, act, Fd, K, M, pad, edges)
+    Fd, K, M = s.F, s.K, s.M
+    qd = NS(**{**vars(s.q), "delta": s.q.delta.to(dev), "zero_point": s.q.zero_point.to(dev)})
+    pack = engine.pack_module_weights(s.w.to(dev), [qd], 0)
     perm = engine.geglu_row_perm(Fd, dev)
-    gpack = engine.pack_select_tiles(pack, perm) if via_tiles else engine.pack_module_weights(w.to(dev), [qd], 0, row_perm=perm)
-    plan = engine.build_wonly_plan(pack, 1, 1, 1, 0, bias.to(dev), act)
-    gplan = engine.build_wonly_plan(gpack, 1, 1, 1, 0, bias.to(dev), act, geglu=True)
+    gpack = engine.pack_select_tiles(pack, perm) if via_tiles else engine.pack_module_weights(s.w.to(dev), [qd], 0, row_perm=perm)
+    plan = engine.build_wonly_plan(pack, 1, 1, 1, 0, s.bias.to(dev), s.act)
+    gplan = engine.build_wonly_plan(gpack, 1, 1, 1, 0, s.bias.to(dev), s.act, geglu=True)
     assert plan is not None and gplan is not None
-    xh = engine.wonly_rows(x.to(dev), plan, 1, K, M, (0, 1, K))
-    return NS(x=x, w=w, bias=bias, q=q, plan=plan, gplan=gplan, xh=xh, M=M, F=Fd, K=K, ldo=Fd + pad, act=act)
+    xh = engine.wonly_rows(s.x.to(dev), plan, 1, K, M, (0, 1, K))
+    return NS(**vars(s), plan=plan, gplan=gplan, xh=xh)
 
 
 def _epi_launch(s, dev, plan=None):
@@ -134,8 +145,10 @@ def test_geglu_epilogue_equals_the_two_launch_form(cuda, case):
     assert n == 0, f"{n} elements differ; first at {diff.nonzero()[0].tolist()}"
 
 
-def _fp64_case(dev, seed, wbits, act, Fd, K, M, pad, mode="kernel"):
-    s = _epi_setup(dev, seed, wbits, act, Fd, K, M, pad, edges=True)
+def _epi_ref(s):
+    """fp64 value * GELU(gate) of the host projection s (the SAME rounded operands) and the bound of the module docstring:
+    (ref, tol, fp64 projection h)."""
+    Fd, K, act = s.F, s.K, s.act
     xr = s.x.to(act).double()
     wq = ((_codes(s.w, s.q) - s.q.zero_point.view(-1, 1)) * s.q.delta.view(-1, 1)).double()
     h = xr @ wq.t() + s.bias.double()
@@ -145,6 +158,12 @@ def _fp64_case(dev, seed, wbits, act, Fd, K, M, pad, mode="kernel"):
     G = 0.5 * gt * (1 + torch.erf(gt / math.sqrt(2)))
     ref = a * G
     tol = _half_ulp(ref, act) + 2.0 ** -23 * (a * gt).abs() + 3 * U * ref.abs() + G.abs() * ca + 1.13 * a.abs() * cg + 1.13 * ca * cg
+    return ref, tol, h
+
+
+def _fp64_case(dev, seed, wbits, act, Fd, K, M, pad, mode="kernel"):
+    s = _epi_setup(dev, seed, wbits, act, Fd, K, M, pad, edges=True)
+    ref, tol, h = _epi_ref(s)
     if mode in ("kernel", "unpermuted"):
         buf, out = _epi_launch(s, dev, plan=None if mode == "kernel" else NS(pack=s.plan.pack, bias=s.plan.bias, ldx=s.plan.ldx,
                                                                              Cout=s.plan.Cout, segs=s.plan.segs))
