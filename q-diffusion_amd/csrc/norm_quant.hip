@@ -4,6 +4,9 @@
 // elementwise passes over an fp32 tensor (ddim/models/diffusion.py:121-130, openaimodel.py:201-232,
 // quant_layer.py:82-88).  Here: one statistics pass (deterministic two-level reduction, no float
 // atomics) and one apply pass that reads the activation once and writes one byte per element.
+// GroupNorm has ONE statistics driver (gn_stats: partial sums, gn_finalize_kernel<64 | 256>, optional modulation) behind its
+// three kinds of entry, which differ in the apply pass alone: int8 codes (gn_apply_kernel, gn_apply_rows_kernel,
+// gn_apply_rows_h8_kernel), and fp16 / bf16 rows (gn_apply_h16_kernel) for the first-stage decoder and the weights-only blocks.
 #include "common.h"
 
 namespace {
@@ -68,16 +71,22 @@ __global__ __launch_bounds__(256) void gn_partial_h8_kernel(const __half* __rest
     }
 }
 
-// finalize: grid (groups, B), 64 threads.  Writes per-(b,c) affine a = rstd*gamma, sh = beta - mean*a.
-__global__ __launch_bounds__(64) void gn_finalize_kernel(const float* __restrict__ part, int nchunk, long ldp, long S, int C,
+// finalize: grid (groups, B), NT threads.  Writes per-(b,c) affine a = rstd*gamma, sh = beta - mean*a.  fp64 sums in a fixed
+// order: thread-strided partial sums, then the wave butterfly.  NT = 64 is one wave and ends there (no LDS).  NT = 256 is for
+// long chunk lists (first-stage decoder: 512 x 512 maps = 2048 chunks of 128 rows, 4-16 channels per group — one wave walks
+// 128-512 strided loads per thread there, 30-130 us) and adds the four wave results in wave order, so the two widths differ
+// in the last bits of the sums: which width an entry uses is part of its result (gn_stats).
+template <int NT>
+__global__ __launch_bounds__(NT) void gn_finalize_kernel(const float* __restrict__ part, int nchunk, long ldp, long S, int C,
                                                          int groups, float eps, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, float* __restrict__ ab) {
+    static_assert(NT == 64 || NT == 256, "one wave, or four whose results are added in wave order");
     const int g = blockIdx.x;
     const long b = blockIdx.y;
     const int cpg = C / groups;
     double s = 0.0, q = 0.0;
     const int items = nchunk * cpg;
-    for (int i = threadIdx.x; i < items; i += 64) {
+    for (int i = threadIdx.x; i < items; i += NT) {
         int chunk = i / cpg, c = g * cpg + i % cpg;
         const float* p = part + (((b * nchunk + chunk) * ldp) + c) * 2;
         s += (double)p[0];
@@ -88,55 +97,20 @@ __global__ __launch_bounds__(64) void gn_finalize_kernel(const float* __restrict
         s += __shfl_xor(s, o);
         q += __shfl_xor(q, o);
     }
+    if constexpr (NT == 256) {
+        __shared__ double red[8];
+        if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = s; red[4 + (threadIdx.x >> 6)] = q; }
+        __syncthreads();
+        s = ((red[0] + red[1]) + red[2]) + red[3];
+        q = ((red[4] + red[5]) + red[6]) + red[7];
+    }
     const double n = (double)S * cpg;
     const double mean = s / n;
     double var = q / n - mean * mean;
     if (var < 0.0) var = 0.0;
     const float rstd = (float)(1.0 / sqrt(var + (double)eps));
     const float fmean = (float)mean;
-    for (int i = threadIdx.x; i < cpg; i += 64) {
-        int c = g * cpg + i;
-        float a = rstd * (gamma ? gamma[c] : 1.f);
-        float sh = (beta ? beta[c] : 0.f) - fmean * a;
-        ab[(b * C + c) * 2] = a;
-        ab[(b * C + c) * 2 + 1] = sh;
-    }
-}
-
-// finalize for long chunk lists (first-stage decoder: 512 x 512 maps = 2048 chunks of 128 rows, 4-16 channels per group —
-// the 64-thread kernel above walks 128-512 strided loads per thread there, 30-130 us): 256 threads, same fp64 sums in a
-// fixed order (thread-strided partial sums, wave butterflies, then the four wave results in wave order).
-__global__ __launch_bounds__(256) void gn_finalize_wide_kernel(const float* __restrict__ part, int nchunk, long ldp, long S, int C,
-                                                               int groups, float eps, const float* __restrict__ gamma,
-                                                               const float* __restrict__ beta, float* __restrict__ ab) {
-    __shared__ double red[8];
-    const int g = blockIdx.x;
-    const long b = blockIdx.y;
-    const int cpg = C / groups;
-    double s = 0.0, q = 0.0;
-    const int items = nchunk * cpg;
-    for (int i = threadIdx.x; i < items; i += 256) {
-        int chunk = i / cpg, c = g * cpg + i % cpg;
-        const float* p = part + (((b * nchunk + chunk) * ldp) + c) * 2;
-        s += (double)p[0];
-        q += (double)p[1];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s += __shfl_xor(s, o);
-        q += __shfl_xor(q, o);
-    }
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = s; red[4 + (threadIdx.x >> 6)] = q; }
-    __syncthreads();
-    s = ((red[0] + red[1]) + red[2]) + red[3];
-    q = ((red[4] + red[5]) + red[6]) + red[7];
-    const double n = (double)S * cpg;
-    const double mean = s / n;
-    double var = q / n - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
-    const float fmean = (float)mean;
-    for (int i = threadIdx.x; i < cpg; i += 256) {
+    for (int i = threadIdx.x; i < cpg; i += NT) {
         int c = g * cpg + i;
         float a = rstd * (gamma ? gamma[c] : 1.f);
         float sh = (beta ? beta[c] : 0.f) - fmean * a;
@@ -161,6 +135,44 @@ __global__ __launch_bounds__(256) void gn_modulate_kernel(float* __restrict__ ab
     ab[2 * i + 1] = sh * sc + sf;
 }
 
+// the load widths a row stream allows: 4-element lanes (16 bytes of fp32, 8 of fp16), and 8-half (16-byte) lanes of fp16 rows
+inline bool gn_vec4(const void* x, int x_dtype, int64_t ldx) { return qd_aligned(x, x_dtype == QD_F32 ? 16 : 8) && ldx % 4 == 0; }
+inline bool gn_vec8(const void* x, int x_dtype, int64_t ldx) { return x_dtype == QD_F16 && qd_aligned(x, 16) && ldx % 8 == 0; }
+
+// The statistics passes of every GroupNorm entry.  ws (qd_groupnorm_ws_bytes) = part | ab.  Launches the first level (the widest
+// partial kernel the rows allow; C % 8 == 0 for 16-byte fp16 lanes is the caller's check) unless the producer of x wrote it
+// (part_in: nchunk_in chunks, part_ld channels per chunk row, 0 = C), the finalise and, with mod, the scale | shift fold.
+// Returns the per-(sample, channel) affine ab [B][C][2] the apply pass reads.
+// wide_ok: the 256-thread finalise from nchunk * (C / groups) >= 2048.  The int8 entries pass false: the four-wave sum runs in
+// another order, so their codes would change bits at round() ties — a change of results, not a tidy-up.
+float* gn_stats(const void* x, int x_dtype, int64_t B, int64_t S, int C, int64_t ldx, int groups, float eps, const float* gamma,
+                const float* beta, void* ws, const float* part_in, int nchunk_in, int64_t part_ld, bool wide_ok, const float* mod,
+                int64_t mod_ld, hipStream_t st) {
+    const int nchunk_own = (int)((S + gn_rows(S) - 1) / gn_rows(S));
+    float* part = reinterpret_cast<float*>(ws);
+    float* ab = part + (size_t)B * nchunk_own * C * 2;
+    const long ldp = part_in && part_ld ? (long)part_ld : (long)C;
+    const int nchunk = part_in ? nchunk_in : nchunk_own;
+    const dim3 pgrid(nchunk, (unsigned)B), fgrid(groups, (unsigned)B);
+    if (part_in) {
+        // first statistics level came with the tensor (written by the producing GEMM's epilogue)
+    } else if (x_dtype == QD_F32)
+        hipLaunchKernelGGL(gn_partial_kernel<float>, pgrid, dim3(256), 0, st, (const float*)x, (long)S, C, (long)ldx, part, nchunk, (int)gn_vec4(x, x_dtype, ldx));
+    else if (gn_vec8(x, x_dtype, ldx))
+        hipLaunchKernelGGL(gn_partial_h8_kernel, pgrid, dim3(256), 0, st, (const __half*)x, (long)S, C, (long)ldx, part, nchunk);
+    else
+        hipLaunchKernelGGL(gn_partial_kernel<__half>, pgrid, dim3(256), 0, st, (const __half*)x, (long)S, C, (long)ldx, part, nchunk, (int)gn_vec4(x, x_dtype, ldx));
+    if (wide_ok && (long)nchunk * (C / groups) >= 2048)
+        hipLaunchKernelGGL(gn_finalize_kernel<256>, fgrid, dim3(256), 0, st, part_in ? part_in : part, nchunk, ldp, (long)S, C, groups, eps, gamma, beta, ab);
+    else
+        hipLaunchKernelGGL(gn_finalize_kernel<64>, fgrid, dim3(64), 0, st, part_in ? part_in : part, nchunk, ldp, (long)S, C, groups, eps, gamma, beta, ab);
+    if (mod) {
+        const long tot = (long)B * C;
+        hipLaunchKernelGGL(gn_modulate_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, ab, mod, (long)mod_ld, C, tot);
+    }
+    return ab;
+}
+
 // second, optional output of the apply pass: the RAW input quantised for another consumer of the same tensor — the 1x1
 // skip connection of a residual block (reference quant_block.py:108-111: `skip_connection(x, split)` reads the very
 // tensor `in_layers` normalises; up to two channel segments with their own activation quantisers, quant_layer.py:257-269).
@@ -173,6 +185,19 @@ struct RawQ {
     float   qmin[2], qmax[2];
     const float* qp[2];
 };
+
+// The segment a lane's channels [c, c + 4 or 8) fall into, if any: segment bounds are multiples of 16 channels (checked by the
+// host), so a lane's channels share one.  Explicit selects only: a dynamically indexed kernel argument would be copied to
+// scratch.  q is loaded only where a segment is.
+struct RawSel { bool here; int col; QP q; float qmin, qmax; int off; };
+__device__ __forceinline__ RawSel gn_raw_select(const RawQ& raw, int c) {
+    const bool s1 = raw.out && raw.nseg > 1 && c >= raw.c0[1];
+    const int rc0 = s1 ? raw.c0[1] : raw.c0[0], rlen = s1 ? raw.clen[1] : raw.clen[0], roc0 = s1 ? raw.oc0[1] : raw.oc0[0];
+    RawSel r{raw.out && c >= rc0 && c < rc0 + rlen, roc0 + (c - rc0), QP{1.f, 0.f, 1.f, false}, s1 ? raw.qmin[1] : raw.qmin[0],
+             s1 ? raw.qmax[1] : raw.qmax[0], s1 ? raw.off[1] : raw.off[0]};
+    if (r.here) r.q = qd_load_qp(s1 ? raw.qp[1] : raw.qp[0]);
+    return r;
+}
 
 // apply: lane = 4 consecutive channels of one row (float4 in, 4 bytes out; both sides fully coalesced).
 template <typename T>
@@ -206,23 +231,16 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
     };
     QD_FAST_DISPATCH(q.fast, body);
     if (out) *reinterpret_cast<unsigned*>(out + row * ldo + c) = u;
-    if (raw.out) {
-        // segment boundaries are multiples of 16 channels (checked by the host): a lane's 4 channels share a segment
-        const bool s1 = raw.nseg > 1 && c >= raw.c0[1];           // explicit selects: no dynamically indexed kernel argument
-        const int rc0 = s1 ? raw.c0[1] : raw.c0[0], rlen = s1 ? raw.clen[1] : raw.clen[0], roc0 = s1 ? raw.oc0[1] : raw.oc0[0];
-        if (c >= rc0 && c < rc0 + rlen) {
-            const QP rq = qd_load_qp(s1 ? raw.qp[1] : raw.qp[0]);
-            const float rmin = s1 ? raw.qmin[1] : raw.qmin[0], rmax = s1 ? raw.qmax[1] : raw.qmax[0];
-            const int roff = s1 ? raw.off[1] : raw.off[0];
-            unsigned w = 0;
-            auto rbody = [&](auto ft) __attribute__((always_inline)) {
+    const RawSel rs = gn_raw_select(raw, c);
+    if (rs.here) {
+        unsigned w = 0;
+        auto rbody = [&](auto ft) __attribute__((always_inline)) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    w |= (unsigned)((qd_code_t<decltype(ft)::value>(v[j], rq, rmin, rmax) - roff) & 0xff) << (8 * j);
-            };
-            QD_FAST_DISPATCH(rq.fast, rbody);
-            *reinterpret_cast<unsigned*>(raw.out + row * raw.ldo + roc0 + (c - rc0)) = w;
-        }
+            for (int j = 0; j < 4; ++j)
+                w |= (unsigned)((qd_code_t<decltype(ft)::value>(v[j], rs.q, rs.qmin, rs.qmax) - rs.off) & 0xff) << (8 * j);
+        };
+        QD_FAST_DISPATCH(rs.q.fast, rbody);
+        *reinterpret_cast<unsigned*>(raw.out + row * raw.ldo + rs.col) = w;
     }
 }
 
@@ -249,14 +267,8 @@ __global__ __launch_bounds__(256) void gn_apply_rows_kernel(const float* __restr
     const float4 ab1 = *reinterpret_cast<const float4*>(ab + (b * C + c) * 2 + 4);
     const float a4[4] = {ab0.x, ab0.z, ab1.x, ab1.z}, s4[4] = {ab0.y, ab0.w, ab1.y, ab1.w};
     const QP q = qd_load_qp(qp);
-    const bool s1 = raw.out && raw.nseg > 1 && c >= raw.c0[1];
-    const int rc0 = s1 ? raw.c0[1] : raw.c0[0], rlen = s1 ? raw.clen[1] : raw.clen[0], roc0 = s1 ? raw.oc0[1] : raw.oc0[0];
-    const bool rawhere = raw.out && c >= rc0 && c < rc0 + rlen;
-    QP rq{1.f, 0.f, 1.f, false};
-    if (rawhere) rq = qd_load_qp(s1 ? raw.qp[1] : raw.qp[0]);
-    const float rmin = s1 ? raw.qmin[1] : raw.qmin[0], rmax = s1 ? raw.qmax[1] : raw.qmax[0];
-    const int roff = s1 ? raw.off[1] : raw.off[0];
-    const QB qb = qd_bytes_setup(q, qmin, qmax, off), rqb = qd_bytes_setup(rq, rmin, rmax, roff);
+    const RawSel rs = gn_raw_select(raw, c);
+    const QB qb = qd_bytes_setup(q, qmin, qmax, off), rqb = qd_bytes_setup(rs.q, rs.qmin, rs.qmax, rs.off);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const float v[4] = {xv[u].x, xv[u].y, xv[u].z, xv[u].w};
@@ -271,11 +283,11 @@ __global__ __launch_bounds__(256) void gn_apply_rows_kernel(const float* __restr
         auto body = [&](auto ft) __attribute__((always_inline)) { w0 = qd_pack4_t<decltype(ft)::value>(y[0], y[1], y[2], y[3], q, qb); };
         QD_FAST_DISPATCH(q.fast, body);
         *reinterpret_cast<unsigned*>(out + row * ldo + c) = w0;
-        if (rawhere) {
+        if (rs.here) {
             unsigned w = 0;
-            auto rbody = [&](auto ft) __attribute__((always_inline)) { w = qd_pack4_t<decltype(ft)::value>(v[0], v[1], v[2], v[3], rq, rqb); };
-            QD_FAST_DISPATCH(rq.fast, rbody);
-            *reinterpret_cast<unsigned*>(raw.out + row * raw.ldo + roc0 + (c - rc0)) = w;
+            auto rbody = [&](auto ft) __attribute__((always_inline)) { w = qd_pack4_t<decltype(ft)::value>(v[0], v[1], v[2], v[3], rs.q, rqb); };
+            QD_FAST_DISPATCH(rs.q.fast, rbody);
+            *reinterpret_cast<unsigned*>(raw.out + row * raw.ldo + rs.col) = w;
         }
     }
 }
@@ -311,15 +323,8 @@ __global__ __launch_bounds__(256) void gn_apply_rows_h8_kernel(const __half* __r
         a8[2 * j] = t.x; s8[2 * j] = t.y; a8[2 * j + 1] = t.z; s8[2 * j + 1] = t.w;
     }
     const QP q = qd_load_qp(qp);
-    // segment bounds are multiples of 16 channels (host): a lane's 8 channels share a segment
-    const bool s1 = raw.out && raw.nseg > 1 && c >= raw.c0[1];
-    const int rc0 = s1 ? raw.c0[1] : raw.c0[0], rlen = s1 ? raw.clen[1] : raw.clen[0], roc0 = s1 ? raw.oc0[1] : raw.oc0[0];
-    const bool rawhere = raw.out && c >= rc0 && c < rc0 + rlen;
-    QP rq{1.f, 0.f, 1.f, false};
-    if (rawhere) rq = qd_load_qp(s1 ? raw.qp[1] : raw.qp[0]);
-    const float rmin = s1 ? raw.qmin[1] : raw.qmin[0], rmax = s1 ? raw.qmax[1] : raw.qmax[0];
-    const int roff = s1 ? raw.off[1] : raw.off[0];
-    const QB qb = qd_bytes_setup(q, qmin, qmax, off), rqb = qd_bytes_setup(rq, rmin, rmax, roff);
+    const RawSel rs = gn_raw_select(raw, c);
+    const QB qb = qd_bytes_setup(q, qmin, qmax, off), rqb = qd_bytes_setup(rs.q, rs.qmin, rs.qmax, rs.off);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         v4f lo, hi;
@@ -339,14 +344,14 @@ __global__ __launch_bounds__(256) void gn_apply_rows_h8_kernel(const __half* __r
         };
         QD_FAST_DISPATCH(q.fast, body);
         *reinterpret_cast<uint2*>(out + row * ldo + c) = make_uint2(w0, w1);
-        if (rawhere) {
+        if (rs.here) {
             unsigned r0 = 0, r1 = 0;
             auto rbody = [&](auto ft) __attribute__((always_inline)) {
-                r0 = qd_pack4_t<decltype(ft)::value>(v[0], v[1], v[2], v[3], rq, rqb);
-                r1 = qd_pack4_t<decltype(ft)::value>(v[4], v[5], v[6], v[7], rq, rqb);
+                r0 = qd_pack4_t<decltype(ft)::value>(v[0], v[1], v[2], v[3], rs.q, rqb);
+                r1 = qd_pack4_t<decltype(ft)::value>(v[4], v[5], v[6], v[7], rs.q, rqb);
             };
-            QD_FAST_DISPATCH(rq.fast, rbody);
-            *reinterpret_cast<uint2*>(raw.out + row * raw.ldo + roc0 + (c - rc0)) = make_uint2(r0, r1);
+            QD_FAST_DISPATCH(rs.q.fast, rbody);
+            *reinterpret_cast<uint2*>(raw.out + row * raw.ldo + rs.col) = make_uint2(r0, r1);
         }
     }
 }
@@ -655,79 +660,91 @@ void dispatch_ln(int nvl, hipStream_t st, const void* x, long M, int C, long ldx
     }
 }
 
-// First-stage decoder (bf16 convolutions, fp32 residual stream): the apply pass with a bf16 output — thread = 8 consecutive
-// channels of one row (two 16-byte loads, one 16-byte store), same statistics passes and per-(sample, channel) affine.
-__global__ __launch_bounds__(256) void gn_apply_bf16_kernel(const float* __restrict__ x, long rows, long S, int C, long ldx,
-                                                            const float* __restrict__ ab, int apply_silu,
-                                                            unsigned short* __restrict__ out, long ldo, int fh) {
-    const int chunks = C >> 3;
-    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= rows * chunks) return;
-    const long row = gid / chunks;
-    const int c = (int)(gid - row * chunks) * 8;
-    const long b = row / S;
-    const float4 x0 = *reinterpret_cast<const float4*>(x + row * ldx + c);
-    const float4 x1 = *reinterpret_cast<const float4*>(x + row * ldx + c + 4);
-    const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-    float y[8];
-    const float* abp = ab + (b * C + c) * 2;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const float4 t = *reinterpret_cast<const float4*>(abp + 4 * j);
-        y[2 * j] = v[2 * j] * t.x + t.y;
-        y[2 * j + 1] = v[2 * j + 1] * t.z + t.w;
+// 16-bit row streams (first-stage decoder, weights-only producers): a lane owns 8 consecutive channels — fp16 input one
+// 16-byte load, fp32 input two; one 16-byte store of fp16 (fh) or bf16, ONE round-to-nearest-even at the store.
+template <typename T>
+__device__ __forceinline__ void h16_ld8(const T* p, float (&v)[8]) {
+    if constexpr (sizeof(T) == 4) {
+        const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    } else {
+        qd_ld8h(p, v);
     }
-    if (apply_silu) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) y[j] = y[j] * (1.0f / (1.0f + expf(-y[j])));
-    }
+}
+__device__ __forceinline__ v4i h16_pack8(const float (&y)[8], int fh) {
     v4i pk;
 #pragma unroll
     for (int j = 0; j < 4; ++j) pk[j] = fh ? (int)qd_pack2h(y[2 * j], y[2 * j + 1]) : (int)qd_pack2bf(y[2 * j], y[2 * j + 1]);
-    *reinterpret_cast<v4i*>(out + row * ldo + c) = pk;
+    return pk;
+}
+
+// GroupNorm apply with a 16-bit output: thread = (row, 8-channel chunk), y = x * a + sh with the per-(sample, channel) affine of
+// gn_finalize_kernel, optional SiLU.  PAD: an operand row of the weights-only layers — ldo / 8 chunks per row, those past C / 8
+// written as zeros, grid-stride over total = rows * (ldo / 8).  !PAD: C / 8 chunks per row and [C, ldo) left untouched (out may
+// be a column range of wider rows), one thread per chunk of total = rows * (C / 8): no pad test and no loop on that path.
+template <typename T, bool PAD>
+__global__ __launch_bounds__(256) void gn_apply_h16_kernel(const T* __restrict__ x, long total, long S, int C, long ldx,
+                                                           const float* __restrict__ ab, int apply_silu,
+                                                           unsigned short* __restrict__ out, long ldo, int fh) {
+    const int nch = C >> 3, nout = PAD ? (int)(ldo >> 3) : nch;
+    auto chunk = [&](long gid) __attribute__((always_inline)) {
+        const long row = gid / nout;
+        const int c8 = (int)(gid - row * nout);
+        v4i pk = {0, 0, 0, 0};
+        if (!PAD || c8 < nch) {
+            float v[8], y[8];
+            h16_ld8(x + row * ldx + c8 * 8, v);
+            const float* abp = ab + ((row / S) * C + c8 * 8) * 2;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float4 t = *reinterpret_cast<const float4*>(abp + 4 * j);
+                y[2 * j] = v[2 * j] * t.x + t.y;
+                y[2 * j + 1] = v[2 * j + 1] * t.z + t.w;
+            }
+            if (apply_silu) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) y[j] = y[j] * (1.0f / (1.0f + expf(-y[j])));
+            }
+            pk = h16_pack8(y, fh);
+        }
+        *reinterpret_cast<v4i*>(out + row * ldo + c8 * 8) = pk;
+    };
+    const long gid0 = (long)blockIdx.x * 256 + threadIdx.x;
+    if constexpr (PAD) {
+        for (long gid = gid0; gid < total; gid += (long)gridDim.x * 256) chunk(gid);
+    } else {
+        if (gid0 < total) chunk(gid0);
+    }
 }
 
 }  // namespace
 
-// GroupNorm (+ SiLU) of fp32 NHWC rows into bf16 rows: the producer of the bf16 convolutions of the first-stage decoder
-// (reference ldm/modules/diffusionmodules/model.py:38-45 Normalize / nonlinearity in front of every convolution).
-// gamma / beta may be null (x * rstd - mean * rstd).
-extern "C" int qd_groupnorm_silu_h16(const float* x, int64_t B, int64_t S, int C, int64_t ldx, int groups, float eps,
-                                     const float* gamma, const float* beta, int apply_silu, int out_dtype, void* out, int64_t ldo, void* ws,
-                                     const float* part_in, int nchunk_in, int64_t part_ld, void* stream);
-extern "C" int qd_groupnorm_silu_bf16(const float* x, int64_t B, int64_t S, int C, int64_t ldx, int groups, float eps,
-                                      const float* gamma, const float* beta, int apply_silu, void* out, int64_t ldo, void* ws,
-                                      const float* part_in, int nchunk_in, int64_t part_ld, void* stream) {
-    return qd_groupnorm_silu_h16(x, B, S, C, ldx, groups, eps, gamma, beta, apply_silu, QD_BF16, out, ldo, ws, part_in, nchunk_in, part_ld, stream);
-}
-
-// the same with the output type as a parameter: QD_BF16 or QD_F16 (the reference decodes under fp16 autocast, scripts/txt2img.py:231-236)
+// GroupNorm (+ SiLU) of fp32 NHWC rows into bf16 / fp16 rows (out_dtype: QD_BF16 or QD_F16 — the reference decodes under fp16
+// autocast, scripts/txt2img.py:231-236): the producer of the 16-bit convolutions of the first-stage decoder (reference
+// ldm/modules/diffusionmodules/model.py:38-45 Normalize / nonlinearity in front of every convolution).  gamma / beta may be
+// null (x * rstd - mean * rstd).  out may be a column range of wider rows: [C, ldo) is not written.
 extern "C" int qd_groupnorm_silu_h16(const float* x, int64_t B, int64_t S, int C, int64_t ldx, int groups, float eps,
                                      const float* gamma, const float* beta, int apply_silu, int out_dtype, void* out, int64_t ldo, void* ws,
                                      const float* part_in, int nchunk_in, int64_t part_ld, void* stream) {
     QD_REQUIRE(out_dtype == QD_BF16 || out_dtype == QD_F16, "qd_groupnorm_silu_h16: out_dtype must be bf16 or f16");
-    QD_REQUIRE(x && out && ws, "qd_groupnorm_silu_bf16: null pointer");
-    QD_REQUIRE(B > 0 && S > 0 && C > 0 && groups > 0 && C % groups == 0 && C % 8 == 0, "qd_groupnorm_silu_bf16: C=%d must be a multiple of 8 and of groups=%d", C, groups);
-    QD_REQUIRE(ldx >= C && ldx % 4 == 0 && qd_aligned(x, 16) && ldo >= C && ldo % 8 == 0 && qd_aligned(out, 16), "qd_groupnorm_silu_bf16: rows must be 16-byte aligned");
-    QD_REQUIRE(B < 65536, "qd_groupnorm_silu_bf16: batch too large");
+    QD_REQUIRE(x && out && ws, "qd_groupnorm_silu_h16: null pointer");
+    QD_REQUIRE(B > 0 && S > 0 && C > 0 && groups > 0 && C % groups == 0 && C % 8 == 0, "qd_groupnorm_silu_h16: C=%d must be a multiple of 8 and of groups=%d", C, groups);
+    QD_REQUIRE(ldx >= C && ldx % 4 == 0 && qd_aligned(x, 16) && ldo >= C && ldo % 8 == 0 && qd_aligned(out, 16), "qd_groupnorm_silu_h16: rows must be 16-byte aligned");
+    QD_REQUIRE(B < 65536, "qd_groupnorm_silu_h16: batch too large");
+    QD_REQUIRE(!part_in || (nchunk_in > 0 && (part_ld == 0 || part_ld >= C)), "qd_groupnorm_silu_h16: part_in needs nchunk_in > 0 and part_ld >= C");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int nchunk_own = (int)((S + gn_rows(S) - 1) / gn_rows(S));
-    float* part = reinterpret_cast<float*>(ws);
-    float* ab = part + (size_t)B * nchunk_own * C * 2;
-    QD_REQUIRE(!part_in || (nchunk_in > 0 && (part_ld == 0 || part_ld >= C)), "qd_groupnorm_silu_bf16: part_in needs nchunk_in > 0 and part_ld >= C");
-    const long ldp = part_in && part_ld ? (long)part_ld : (long)C;
-    const int nchunk = part_in ? nchunk_in : nchunk_own;
-    if (!part_in)
-        hipLaunchKernelGGL(gn_partial_kernel<float>, dim3(nchunk, (unsigned)B), dim3(256), 0, st, x, (long)S, C, (long)ldx, part, nchunk, 1);
-    if ((long)nchunk * (C / groups) >= 2048)
-        hipLaunchKernelGGL(gn_finalize_wide_kernel, dim3(groups, (unsigned)B), dim3(256), 0, st, part_in ? part_in : part, nchunk, ldp, (long)S, C, groups, eps, gamma, beta, ab);
-    else
-        hipLaunchKernelGGL(gn_finalize_kernel, dim3(groups, (unsigned)B), dim3(64), 0, st, part_in ? part_in : part, nchunk, ldp, (long)S, C, groups, eps, gamma, beta, ab);
-    const long rows = B * S, total = rows * (C / 8);
-    hipLaunchKernelGGL(gn_apply_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, rows, (long)S, C, (long)ldx, ab, apply_silu,
+    const float* ab = gn_stats(x, QD_F32, B, S, C, ldx, groups, eps, gamma, beta, ws, part_in, nchunk_in, part_ld, true, nullptr, 0, st);
+    const long total = B * S * (C / 8);      // one thread per chunk, no block cap
+    hipLaunchKernelGGL((gn_apply_h16_kernel<float, false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, total, (long)S, C, (long)ldx, ab, apply_silu,
                        reinterpret_cast<unsigned short*>(out), (long)ldo, out_dtype == QD_F16 ? 1 : 0);
-    QD_LAUNCH_CHECK("qd_groupnorm_silu_bf16");
+    QD_LAUNCH_CHECK("qd_groupnorm_silu_h16");
     return 0;
+}
+
+extern "C" int qd_groupnorm_silu_bf16(const float* x, int64_t B, int64_t S, int C, int64_t ldx, int groups, float eps,
+                                      const float* gamma, const float* beta, int apply_silu, void* out, int64_t ldo, void* ws,
+                                      const float* part_in, int nchunk_in, int64_t part_ld, void* stream) {
+    return qd_groupnorm_silu_h16(x, B, S, C, ldx, groups, eps, gamma, beta, apply_silu, QD_BF16, out, ldo, ws, part_in, nchunk_in, part_ld, stream);
 }
 
 extern "C" int64_t qd_groupnorm_ws_bytes(int64_t B, int64_t C, int64_t S) {
@@ -746,30 +763,12 @@ static int groupnorm_impl(const void* x, int x_dtype, int64_t B, int64_t S, int 
     QD_REQUIRE(B > 0 && S > 0 && C > 0 && groups > 0 && C % groups == 0 && C % 16 == 0, "qd_groupnorm_silu_quant: C=%d must be a multiple of 16 and of groups=%d", C, groups);
     QD_REQUIRE(ldx >= C && (!out || (ldo >= C && ldo % 16 == 0 && qd_aligned(out, 16))), "qd_groupnorm_silu_quant: bad leading dimensions");
     QD_REQUIRE(B < 65536, "qd_groupnorm_silu_quant: batch too large");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int nchunk_own = (int)((S + gn_rows(S) - 1) / gn_rows(S));
-    const int vec = qd_aligned(x, x_dtype == QD_F32 ? 16 : 8) && ldx % 4 == 0;
-    // fp16 rows that take 16-byte (8-half) lanes
-    const bool vec8 = x_dtype == QD_F16 && qd_aligned(x, 16) && ldx % 8 == 0;      // C % 16 == 0 is required above
-    float* part = reinterpret_cast<float*>(ws);
-    float* ab = part + (size_t)B * nchunk_own * C * 2;
     QD_REQUIRE(!part_in || (nchunk_in > 0 && (part_ld == 0 || part_ld >= C)), "qd_groupnorm_silu_quant: part_in needs nchunk_in > 0 and part_ld >= C");
-    const long ldp = part_in && part_ld ? (long)part_ld : (long)C;
-    const int nchunk = part_in ? nchunk_in : nchunk_own;
-    if (part_in) {
-        // first statistics level came with the tensor (written by the producing GEMM's epilogue)
-    } else if (x_dtype == QD_F32)
-        hipLaunchKernelGGL(gn_partial_kernel<float>, dim3(nchunk, (unsigned)B), dim3(256), 0, st, (const float*)x, (long)S, C, (long)ldx, part, nchunk, vec);
-    else if (vec8)
-        hipLaunchKernelGGL(gn_partial_h8_kernel, dim3(nchunk, (unsigned)B), dim3(256), 0, st, (const __half*)x, (long)S, C, (long)ldx, part, nchunk);
-    else
-        hipLaunchKernelGGL(gn_partial_kernel<__half>, dim3(nchunk, (unsigned)B), dim3(256), 0, st, (const __half*)x, (long)S, C, (long)ldx, part, nchunk, vec);
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3(groups, (unsigned)B), dim3(64), 0, st, part_in ? part_in : part, nchunk, ldp, (long)S, C, groups, eps, gamma, beta, ab);
-    if (mod) {
-        QD_REQUIRE(mod_ld >= 2 * (int64_t)C, "qd_groupnorm_mod_silu_quant: modulation rows hold scale | shift: mod_ld >= 2 C");
-        const long tot = (long)B * C;
-        hipLaunchKernelGGL(gn_modulate_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, ab, mod, (long)mod_ld, C, tot);
-    }
+    QD_REQUIRE(!mod || mod_ld >= 2 * (int64_t)C, "qd_groupnorm_mod_silu_quant: modulation rows hold scale | shift: mod_ld >= 2 C");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const int vec = gn_vec4(x, x_dtype, ldx);         // int: the kernels' `vec` argument
+    const bool vec8 = gn_vec8(x, x_dtype, ldx);      // C % 16 == 0 is required above
+    const float* ab = gn_stats(x, x_dtype, B, S, C, ldx, groups, eps, gamma, beta, ws, part_in, nchunk_in, part_ld, false, mod, mod_ld, st);
     RawQ rq{};
     if (raw && raw->out) {
         QD_REQUIRE(raw->nseg == 1 || raw->nseg == 2, "qd_groupnorm_silu_quant: raw output takes 1 or 2 segments");
@@ -875,26 +874,10 @@ extern "C" int qd_layernorm_quant(const void* x, int x_dtype, int64_t M, int C, 
 // ---------------------------------------------------------------------------------------------
 // Weights-only producers (state (weight_quant, act_quant) = (True, False)): LayerNorm, GroupNorm(+SiLU)
 // and GEGLU written straight as the fp16 / bf16 operand rows [M][ldo] of qd_conv2d_wq_h16 — no fp32 intermediate and no
-// qd_rows_to_h16 pass.  HBM-bound streams: a lane owns 8 consecutive channels (16-byte stores; fp16 input one 16-byte load,
-// fp32 input two), fp32 arithmetic, ONE round-to-nearest-even at the store, pad channels [C, ldo) written as zeros.
+// qd_rows_to_h16 pass.  HBM-bound 16-bit row streams (h16_ld8 / h16_pack8 above; GroupNorm's apply pass is gn_apply_h16_kernel),
+// fp32 arithmetic, pad channels [C, ldo) written as zeros.
 // ---------------------------------------------------------------------------------------------
 namespace {
-
-template <typename T>
-__device__ __forceinline__ void h16_ld8(const T* p, float (&v)[8]) {
-    if constexpr (sizeof(T) == 4) {
-        const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    } else {
-        qd_ld8h(p, v);
-    }
-}
-__device__ __forceinline__ v4i h16_pack8(const float (&y)[8], int fh) {
-    v4i pk;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) pk[j] = fh ? (int)qd_pack2h(y[2 * j], y[2 * j + 1]) : (int)qd_pack2bf(y[2 * j], y[2 * j + 1]);
-    return pk;
-}
 
 // LayerNorm: a wave owns RPW rows at a time (their loads and reduction chains interleave, as in ln_quant_kernel), lane =
 // 8-channel chunks lane + 64 k (k < NV); mean, then the centred sum of squares, both from registers.  Grid-stride over rows.
@@ -1010,37 +993,6 @@ __global__ __launch_bounds__(256) void geglu_h16_kernel(const T* __restrict__ h,
     }
 }
 
-// GroupNorm apply: thread = (row, 8-channel chunk of the output row), y = x * a + sh with the per-(sample, channel) affine of
-// gn_finalize_kernel, optional SiLU (the expression of gn_apply_bf16_kernel).  Grid-stride.
-template <typename T>
-__global__ __launch_bounds__(256) void gn_apply_h16_kernel(const T* __restrict__ x, long total, long S, int C, long ldx,
-                                                           const float* __restrict__ ab, int apply_silu,
-                                                           unsigned short* __restrict__ out, long ldo, int fh) {
-    const int nch = C >> 3, nout = (int)(ldo >> 3);
-    for (long gid = (long)blockIdx.x * 256 + threadIdx.x; gid < total; gid += (long)gridDim.x * 256) {
-        const long row = gid / nout;
-        const int c8 = (int)(gid - row * nout);
-        v4i pk = {0, 0, 0, 0};
-        if (c8 < nch) {
-            float v[8], y[8];
-            h16_ld8(x + row * ldx + c8 * 8, v);
-            const float* abp = ab + ((row / S) * C + c8 * 8) * 2;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float4 t = *reinterpret_cast<const float4*>(abp + 4 * j);
-                y[2 * j] = v[2 * j] * t.x + t.y;
-                y[2 * j + 1] = v[2 * j + 1] * t.z + t.w;
-            }
-            if (apply_silu) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) y[j] = y[j] * (1.0f / (1.0f + expf(-y[j])));
-            }
-            pk = h16_pack8(y, fh);
-        }
-        *reinterpret_cast<v4i*>(out + row * ldo + c8 * 8) = pk;
-    }
-}
-
 inline unsigned h16_stream_grid(long total) {
     const long nblk = (total + 255) / 256;
     return (unsigned)(nblk < 8192 ? nblk : 8192);
@@ -1095,24 +1047,14 @@ extern "C" int qd_groupnorm_h16(const void* x, int x_dtype, int64_t B, int64_t S
     QD_REQUIRE(ldx >= C && ldx % (x_dtype == QD_F32 ? 4 : 8) == 0 && qd_aligned(x, 16), "qd_groupnorm_h16: input rows must be 16-byte aligned");
     QD_REQUIRE(ldo >= C && ldo % 8 == 0 && qd_aligned(out, 16), "qd_groupnorm_h16: output rows must be 16-byte aligned (ldo %% 8 == 0)");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int nchunk = (int)((S + gn_rows(S) - 1) / gn_rows(S));
-    float* part = reinterpret_cast<float*>(ws);
-    float* ab = part + (size_t)B * nchunk * C * 2;
-    if (x_dtype == QD_F32)
-        hipLaunchKernelGGL(gn_partial_kernel<float>, dim3(nchunk, (unsigned)B), dim3(256), 0, st, (const float*)x, (long)S, C, (long)ldx, part, nchunk, 1);
-    else
-        hipLaunchKernelGGL(gn_partial_h8_kernel, dim3(nchunk, (unsigned)B), dim3(256), 0, st, (const __half*)x, (long)S, C, (long)ldx, part, nchunk);
-    if ((long)nchunk * (C / groups) >= 2048)
-        hipLaunchKernelGGL(gn_finalize_wide_kernel, dim3(groups, (unsigned)B), dim3(256), 0, st, part, nchunk, (long)C, (long)S, C, groups, eps, gamma, beta, ab);
-    else
-        hipLaunchKernelGGL(gn_finalize_kernel, dim3(groups, (unsigned)B), dim3(64), 0, st, part, nchunk, (long)C, (long)S, C, groups, eps, gamma, beta, ab);
+    const float* ab = gn_stats(x, x_dtype, B, S, C, ldx, groups, eps, gamma, beta, ws, nullptr, 0, 0, true, nullptr, 0, st);
     const long total = (long)B * S * (ldo / 8);
     const int fh = out_dtype == QD_F16 ? 1 : 0;
     if (x_dtype == QD_F32)
-        hipLaunchKernelGGL(gn_apply_h16_kernel<float>, dim3(h16_stream_grid(total)), dim3(256), 0, st, (const float*)x, total, (long)S, C, (long)ldx, ab, apply_silu,
+        hipLaunchKernelGGL((gn_apply_h16_kernel<float, true>), dim3(h16_stream_grid(total)), dim3(256), 0, st, (const float*)x, total, (long)S, C, (long)ldx, ab, apply_silu,
                            reinterpret_cast<unsigned short*>(out), (long)ldo, fh);
     else
-        hipLaunchKernelGGL(gn_apply_h16_kernel<__half>, dim3(h16_stream_grid(total)), dim3(256), 0, st, (const __half*)x, total, (long)S, C, (long)ldx, ab, apply_silu,
+        hipLaunchKernelGGL((gn_apply_h16_kernel<__half, true>), dim3(h16_stream_grid(total)), dim3(256), 0, st, (const __half*)x, total, (long)S, C, (long)ldx, ab, apply_silu,
                            reinterpret_cast<unsigned short*>(out), (long)ldo, fh);
     QD_LAUNCH_CHECK("qd_groupnorm_h16");
     return 0;

@@ -232,7 +232,11 @@ def test_conv2d_bf16_equals_fp64_on_the_rounded_operands(cuda, case, dtype):
 @pytest.mark.gpu
 @pytest.mark.parametrize("B,S,C,silu,own_stats", [(2, 64, 64, True, True), (2, 1024, 128, True, False), (1, 4096, 512, False, False),
                                                   (3, 256, 32, True, True),
-                                                  (2, 65536, 128, True, False)])     # 512 chunks x 4 channels: the 256-thread finalise
+                                                  (2, 65536, 128, True, False),      # 512 chunks x 4 channels: the 256-thread finalise
+                                                  # nchunk * (C / 32) on both sides of the finalise threshold (2048): own statistics
+                                                  # (32-row chunks) 1024 and 2048, the producer's (128-row chunks) 1024 — its 2048
+                                                  # is the case above
+                                                  (1, 16384, 64, True, True), (1, 32768, 64, True, True), (1, 65536, 64, True, False)])
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_groupnorm_silu_bf16(cuda, B, S, C, silu, own_stats, dtype):
     """GroupNorm(32, C, eps=1e-6) (+ swish) of fp32 rows, written as bf16 / fp16: the fp32 result of torch rounded once"""
@@ -253,6 +257,28 @@ def test_groupnorm_silu_bf16(cuda, B, S, C, silu, own_stats, dtype):
     ws = torch.empty(hip.groupnorm_ws_bytes(B, C, S), dtype=torch.uint8, device=cuda)
     hip.groupnorm_silu_bf16(x.to(cuda), B, S, C, 32, 1e-6, gamma.to(cuda), beta.to(cuda), silu, out, ws, part=part)
     err = (out.cpu().double() - ref).abs()
+    assert (err <= ULP[dtype] / 2 * ref.abs() + 2e-5 * ref.abs().max()).all(), err.max().item()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_groupnorm_silu_bf16_leaves_the_pad_columns_alone(cuda, dtype):
+    """`out` as the column range [:, :32] of 48-wide rows (the decoder hands column ranges of wider rows; ldo = 48 > C): columns
+    32-47 keep their sentinel bit for bit, columns 0-31 are held to the bound of test_groupnorm_silu_bf16"""
+    from qdiff import hip
+    B, S, C, W = 2, 64, 32, 48
+    g = torch.Generator().manual_seed(C + S + W)
+    x = torch.randn(B * S, C, generator=g) * 3 + 0.5
+    gamma, beta = torch.randn(C, generator=g), torch.randn(C, generator=g)
+    y = F.group_norm(x.reshape(B, S, C).permute(0, 2, 1).double(), 32, gamma.double(), beta.double(), eps=1e-6)
+    ref = (y * torch.sigmoid(y)).permute(0, 2, 1).reshape(B * S, C)
+    sentinel = torch.full((B * S, W), -1234.0, dtype=dtype)
+    wide = sentinel.to(cuda)
+    ws = torch.empty(hip.groupnorm_ws_bytes(B, C, S), dtype=torch.uint8, device=cuda)
+    hip.groupnorm_silu_bf16(x.to(cuda), B, S, C, 32, 1e-6, gamma.to(cuda), beta.to(cuda), True, wide[:, :C], ws)
+    got = wide.cpu()
+    assert np.array_equal(_bits(got[:, C:]), _bits(sentinel[:, C:]))
+    err = (got[:, :C].double() - ref).abs()
     assert (err <= ULP[dtype] / 2 * ref.abs() + 2e-5 * ref.abs().max()).all(), err.max().item()
 
 

@@ -779,10 +779,10 @@ def test_conv_groupnorm_statistics_at_offsets(cuda, offset, record_property):
 # ------------------------------------------------------------------------------------------------
 # (B, H, C, statistics from qd_conv2d_bf16's gn_part): the finalise pass each reaches (wide when nchunk * C / 32 >= 2048)
 FS_STATS = {
-    "narrow_own": (2, 16, 128, False),      # own partials: nchunk = 256 / gn_rows(256) = 32, 4 channels per group -> gn_finalize_kernel
-    "narrow_conv_part": (2, 16, 128, True),  # the conv's 128-row partials: nchunk = 2 -> gn_finalize_kernel
-    "wide_own": (1, 64, 512, False),        # 64x64 map, 512 channels: nchunk = 4096 / 32 = 128, x 16 -> gn_finalize_wide_kernel
-    "wide_conv_part": (1, 128, 512, True),   # 128x128 map: the conv's nchunk = 128, x 16 -> gn_finalize_wide_kernel
+    "narrow_own": (2, 16, 128, False),      # own partials: nchunk = 256 / gn_rows(256) = 32, 4 channels per group -> gn_finalize_kernel<64>
+    "narrow_conv_part": (2, 16, 128, True),  # the conv's 128-row partials: nchunk = 2 -> gn_finalize_kernel<64>
+    "wide_own": (1, 64, 512, False),        # 64x64 map, 512 channels: nchunk = 4096 / 32 = 128, x 16 -> gn_finalize_kernel<256>
+    "wide_conv_part": (1, 128, 512, True),   # 128x128 map: the conv's nchunk = 128, x 16 -> gn_finalize_kernel<256>
 }
 
 
