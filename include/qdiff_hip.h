@@ -462,7 +462,16 @@ int qd_groupnorm_silu_h16(const float* x, int64_t B, int64_t S, int C, int64_t l
  *         nseg 1 or 2 (split shortcut, quant_layer.py:257-269: each segment its own delta / z), epilogue = QD_EPI_LINEAR
  *         (or QD_EPI_GEGLU_H16, below), out_dtype QD_F32 or QD_F16 (the residual has the type of the output), kh/kw/stride/pad_t/pad_l as for
  *         qd_conv2d_i8; out-of-image taps, K tails and M tails read zeros.  gn_part, upsample2x must be unset;
- *         split-K, oq_* / hd_* are ignored.
+ *         oq_* / hd_* are ignored.
+ *         splitk_ws  optional fp32 scratch (16-byte aligned).  The launch is contracted split-K only when
+ *                    splitk_ws is non-NULL, splitk_ws_bytes >= nsplit * M * Cout * 4 and the policy returns nsplit >= 2
+ *                    (qd_conv2d_wq_h16_splitk_ws_bytes(d) != 0); otherwise it is the one launch it always was, the same
+ *                    bytes.  Split: grid = tiles x nsplit, slice s contracts the K-steps [s * it_per, (s + 1) * it_per) of
+ *                    the order segment, tap, 64-channel step and writes its scaled fp32 partial to ws[s][m][n]; a second
+ *                    launch sums the slices in index order (no atomics: the same bits from run to run) and adds bias,
+ *                    rowbias and residual as the unsplit epilogue does.  Both segment counts; QD_EPI_GEGLU_H16 never splits.
+ *                    The fp32 sum is associated differently from the unsplit launch: results agree to rounding, not bit
+ *                    for bit.
  *         rowbias    optional fp32 [B][ld_rowbias] (ld_rowbias >= Cout): row b is added to every output row of sample b
  *                    after the bias and before the residual, as in qd_conv2d_i8 (the timestep-embedding add
  *                    `h + emb_out` of qdiff/quant_block.py:92-98).  NULL leaves the output bytes as they were.
@@ -481,6 +490,14 @@ int qd_groupnorm_silu_h16(const float* x, int64_t B, int64_t S, int C, int64_t l
  *         One call per segment; clen_pad, oc0 and ldo are multiples of 8.
  * ------------------------------------------------------------------------------------------ */
 int qd_conv2d_wq_h16(const qd_conv_desc* d, int act_dtype, void* stream);
+/* Scratch bytes qd_conv2d_wq_h16 would use for a split-K contraction of this descriptor, nsplit * M * Cout * 4 with nsplit <= 32
+ * under the policy; 0 when the layer is launched unsplit.  Pure host function: shape fields, nseg, seg[].clen and epilogue only
+ * are read, no pointer is followed, no GPU is needed. */
+int64_t qd_conv2d_wq_h16_splitk_ws_bytes(const qd_conv_desc* d);
+/* qd_wq_h16_config (additive in ABI 20): splitk -1 = the policy (default); 0 = never split; n >= 2 = force n slices (clamped to
+ * the K-step count so that no slice is empty; QD_EPI_GEGLU_H16 still unsplit); 1 = one slice, the same as 0.  qd_conv2d_wq_h16_splitk_ws_bytes honours it.
+ * For tests and measurements. */
+void qd_wq_h16_config(int splitk);
 int qd_rows_to_h16(const void* x, int x_dtype, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc, int64_t ss,
                    int c0, int clen, int clen_pad, void* out, int out_dtype, int64_t ldo, int oc0, void* stream);
 

@@ -1902,7 +1902,12 @@ struct WqD {
     const void* residual;
     const float* bias;
     const float* rowbias;                 // [B][ldrb] fp32, one row per sample (the timestep-embedding projection), or NULL
-    long ldx, ldo, ldr, ldrb;
+    long ldx, ldo;
+    // A split-K partial (O_PART) has no residual and no row bias: their leading dimensions carry the slice geometry under names
+    // of their own.  The struct keeps its size, so the hidden kernel arguments behind it keep their offsets and the kernels of
+    // the unsplit launch their code.
+    union { long ldr;  long part_it_per; };                   // O_PART: K-steps per slice
+    union { long ldrb; long part_tiles; };                    // O_PART: output tiles per slice
     int H, W, Ho, Wo, Cout, kw, stride, pad_t, pad_l, taps;
     int M, nseg, ntiles, nblk_n;
     WqSeg seg[2];
@@ -1936,9 +1941,14 @@ __device__ __forceinline__ v4i wq_frag(const v4i& mag, const v2h nz) {
     return r;
 }
 
+// OUT == O_PART is the split-K form: grid = tiles x nsplit, slice s = block / tiles contracts the global K-steps
+// [s * it_per, min((s + 1) * it_per, total)) (order: segment, tap, 64-channel step, as advance() walks them) and writes its
+// SCALED partial facc + acc * delta, fp32 without bias / rowbias / residual, to ws[s][m][n] (p.out, row-major [nsplit][M][Cout]);
+// wq_splitk_finalize_kernel sums the slices in index order and applies the rest of the epilogue.  No slice is empty (host).
 template <int WB, bool FH, bool SPLIT, int OUT>
 __global__ __launch_bounds__(256, 2) void wq_h16_kernel(const WqD p) {
     constexpr int MT = 2, NT = 2, BM = 128;
+    constexpr bool PART = OUT == O_PART;
     constexpr int TB = 256 * WB;                               // bytes of one (K-step, 32-channel) weight tile
     constexpr int A_BYTES = BM * 128, B_BYTES = 4 * TB, STAGE = A_BYTES + B_BYTES;
     constexpr int NBL = B_BYTES / 4096;                        // 16-byte weight loads per thread per stage
@@ -1946,7 +1956,10 @@ __global__ __launch_bounds__(256, 2) void wq_h16_kernel(const WqD p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int frow = lane & 31, fhalf = lane >> 5;
-    const int logical = qd_xcd_remap(blockIdx.x, gridDim.x);
+    const int lblk = qd_xcd_remap(blockIdx.x, gridDim.x);
+    const int it_per = PART ? (int)p.part_it_per : 0, tiles = PART ? (int)p.part_tiles : 1;
+    const int slice = PART ? lblk / tiles : 0;
+    const int logical = PART ? lblk - slice * tiles : lblk;
     const int mb = logical / p.nblk_n, nb = logical % p.nblk_n;
     const int m0 = mb * BM, n0 = nb * 128;
 
@@ -1968,6 +1981,14 @@ __global__ __launch_bounds__(256, 2) void wq_h16_kernel(const WqD p) {
         a_dst[i] = r * 128 + ((lq ^ (r & 7)) * 16);
     }
     int ls = 0, lt = 0, lr = 0, lc = 0, lcs = 0;                // loader position: segment, tap (row, column), K-step
+    if constexpr (PART) {                                       // ... of the slice's first global K-step
+        int g = slice * it_per;
+        const int n0steps = p.taps * p.seg[0].nst;
+        if (SPLIT && g >= n0steps) { ls = 1; g -= n0steps; }
+        const int nst = p.seg[SPLIT ? ls : 0].nst;
+        lt = g / nst; lcs = g - lt * nst;
+        lr = lt / p.kw; lc = lt - lr * p.kw;
+    }
     v4i ra[4], rb[NBL];
     auto fetch = [&]() __attribute__((always_inline)) {
         const WqSeg& sg = p.seg[SPLIT ? ls : 0];
@@ -2082,13 +2103,17 @@ __global__ __launch_bounds__(256, 2) void wq_h16_kernel(const WqD p) {
         }
     };
 
+    // the slice's K range — computed HERE, ahead of the prologue fetch: next to `cur` / `nxt` below, hipcc allocates the scalar
+    // registers of the fp16-output unsplit instantiations differently (tools/isa_diff.py against the parent then lists them)
+    const int it0 = PART ? slice * it_per : 0;
+    const int it1 = PART ? (it0 + it_per < total ? it0 + it_per : total) : total;
     fetch();
     store(0);
     advance();
     __syncthreads();
     unsigned cur = 0, nxt = STAGE;
-    for (int it = 0; it < total; ++it) {
-        const bool more = it + 1 < total;
+    for (int it = it0; it < it1; ++it) {
+        const bool more = it + 1 < it1;
         if (more) fetch();
         compute(cur, SPLIT && it >= nst0 ? 1 : 0);
         if (more) {
@@ -2161,6 +2186,25 @@ __global__ __launch_bounds__(256, 2) void wq_h16_kernel(const WqD p) {
                 if (m < p.M) *reinterpret_cast<v4i*>(outp + m * p.ldo + F + q * 8) = v4i{0, 0, 0, 0};
             }
         }
+    } else if constexpr (PART) {
+    // ---- split-K partial in the C layout.  The live accumulator belongs to segment 1 only when the slice reaches past the
+    // boundary; a slice that ends at or before it scales with delta_0 (after a flush acc is 0 and facc is the whole partial).
+    float* const ws = reinterpret_cast<float*>(p.out) + (long)slice * p.M * p.Cout;
+    const bool seg1 = SPLIT && it1 > nst0;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int n = n0 + wn * 64 + j * 32 + frow;
+        if (n >= p.Cout) continue;
+        const float d = seg1 ? dl[1][j] : dl[0][j];
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const long m = m0 + wm * 64 + i * 32 + crow(r) + 4 * fhalf;
+                if (m >= p.M) continue;
+                ws[m * p.Cout + n] = qd_wq_affine(acc[i][j][r], d, SPLIT ? facc[SPLIT ? i : 0][SPLIT ? j : 0][r] : 0.f, 0.f);
+            }
+    }
     } else {
     // ---- epilogue in the C layout: lane = column, 16 rows per lane; 32 lanes write 32 consecutive columns of a row ----
     const int sl = SPLIT ? 1 : 0;
@@ -2220,6 +2264,101 @@ __global__ __launch_bounds__(256) void rows_h16_kernel(const TI* __restrict__ x,
     *reinterpret_cast<v4i*>(out + (b * S + s) * ldo + oc0 + g * 8) = pk;
 }
 
+// split-K second pass of the weights-only contraction: sums the scaled fp32 partials ws[s][m][n] in slice order (no atomics:
+// the same bits from run to run), then bias, rowbias[m / HoWo] and residual in the order and through the functions of the
+// unsplit epilogue.  VEC: thread = 4 consecutive columns (16-byte partial / bias / rowbias lanes; fp32 rows leave as 16 bytes,
+// fp16 rows as 8), chosen by the host when Cout, the leading dimensions and every pointer allow; else thread = one element.
+template <int OUT, bool VEC>
+__global__ __launch_bounds__(256) void wq_splitk_finalize_kernel(const float* __restrict__ ws, int nsplit, long M, int Cout, int HoWo,
+                                                                 const float* __restrict__ bias, const float* __restrict__ rowbias,
+                                                                 long ldrb, const void* __restrict__ residual, long ldr,
+                                                                 void* __restrict__ out, long ldo) {
+    constexpr int V = VEC ? 4 : 1;
+    const long MN = M * Cout;
+    const long e = ((long)blockIdx.x * 256 + threadIdx.x) * V;
+    if (e >= MN) return;
+    const long m = e / Cout;
+    const int  n = (int)(e - m * Cout);
+    float v[V];
+    if constexpr (VEC) {
+        const float4 a = *reinterpret_cast<const float4*>(ws + e);
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+        for (int s = 1; s < nsplit; ++s) {
+            const float4 b = *reinterpret_cast<const float4*>(ws + (long)s * MN + e);
+            v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
+        }
+    } else {
+        v[0] = ws[e];
+        for (int s = 1; s < nsplit; ++s) v[0] += ws[(long)s * MN + e];
+    }
+    const float* rb = rowbias ? rowbias + (m / HoWo) * ldrb + n : nullptr;
+#pragma unroll
+    for (int c = 0; c < V; ++c) {
+        v[c] = qd_wq_affine(v[c], 1.f, 0.f, bias ? bias[n + c] : 0.f);
+        if (rb) v[c] += rb[c];
+    }
+    if constexpr (OUT == O_F32) {
+        const float* r = reinterpret_cast<const float*>(residual);
+        float* o = reinterpret_cast<float*>(out) + m * ldo + n;
+        if (r) {
+#pragma unroll
+            for (int c = 0; c < V; ++c) v[c] += r[m * ldr + n + c];
+        }
+        if constexpr (VEC) *reinterpret_cast<float4*>(o) = float4{v[0], v[1], v[2], v[3]};
+        else *o = v[0];
+    } else {
+        const __half* r = reinterpret_cast<const __half*>(residual);
+        __half* o = reinterpret_cast<__half*>(out) + m * ldo + n;
+        if (r) {
+#pragma unroll
+            for (int c = 0; c < V; ++c) v[c] += __half2float(r[m * ldr + n + c]);
+        }
+        if constexpr (VEC) {
+            union { __half h[4]; uint2 u; } pk;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) pk.h[c] = __float2half(v[c]);
+            *reinterpret_cast<uint2*>(o) = pk.u;
+        } else {
+            *o = __float2half(v[0]);
+        }
+    }
+}
+
+// qd_wq_h16_config: -1 = policy, 0 = never split, n >= 2 = force n slices
+static int& wq_splitk_knob() {
+    static int v = -1;
+    return v;
+}
+
+// Split-K policy of qd_conv2d_wq_h16, next to choose_splitk of the integer path.  Both segment counts; never
+// the GEGLU epilogue (its M x 2F grids fill the chip, and a finalise could not keep its one rounding).  No slice is empty:
+// nsplit = ceil(total / it_per).
+int choose_wq_splitk(const qd_conv_desc* d, int* it_per) {
+    // blocks the split should reach and the fewest K-steps a slice may hold.  PROVISIONAL: the integer path's target of one block per
+    // CU and a guess at the slice length; no timing backs either yet
+    constexpr long kTarget = 256, kMinSteps = 8;
+    *it_per = 0;
+    const int forced = wq_splitk_knob();
+    if (forced == 0 || d->epilogue != QD_EPI_LINEAR || (d->nseg != 1 && d->nseg != 2)) return 1;
+    const long M = (long)d->B * d->Ho * d->Wo;
+    const long tiles = ((M + 127) / 128) * (((long)d->Cout + 127) / 128);
+    long total = 0;
+    for (int s = 0; s < d->nseg; ++s) total += (long)d->kh * d->kw * ((d->seg[s].clen + 63) / 64);
+    if (M <= 0 || d->Cout <= 0 || total < 2) return 1;
+    long S;
+    if (forced >= 2) {
+        S = forced < total ? forced : total;
+    } else {
+        if (total < 4 * kMinSteps) return 1;                       // a second launch is a fixed cost a short K loop cannot pay back
+        S = kTarget / tiles;                                       // < 2: the plain launch already reaches half the target
+        if (S > total / kMinSteps) S = total / kMinSteps;
+        if (S > 32) S = 32;
+    }
+    if (S < 2 || tiles * S >= (1L << 31)) return 1;
+    *it_per = (int)((total + S - 1) / S);
+    return (int)((total + *it_per - 1) / *it_per);
+}
+
 int run_wq_h16(const qd_conv_desc* d, int act_dtype, void* stream) {
     QD_REQUIRE(d != nullptr, "qd_conv2d_wq_h16: null descriptor");
     QD_REQUIRE(d->x && d->w && d->out, "qd_conv2d_wq_h16: null tensor pointer");
@@ -2264,8 +2403,35 @@ int run_wq_h16(const qd_conv_desc* d, int act_dtype, void* stream) {
     QD_REQUIRE(nbm * nbn < (1L << 31), "qd_conv2d_wq_h16: too many tiles");
     k.nblk_n = (int)nbn;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)(nbm * nbn)), block(256);
     const bool fh = act_dtype == QD_F16, split = d->nseg == 2, o16 = d->out_dtype == QD_F16;
+    int it_per = 0;
+    const int nsplit = d->splitk_ws ? choose_wq_splitk(d, &it_per) : 1;
+    if (nsplit >= 2 && d->splitk_ws_bytes >= (int64_t)nsplit * M * d->Cout * 4) {
+        QD_REQUIRE(qd_aligned(d->splitk_ws, 16), "qd_conv2d_wq_h16: splitk_ws must be 16-byte aligned");
+        float* const ws = reinterpret_cast<float*>(d->splitk_ws);
+        k.out = ws; k.part_it_per = it_per; k.part_tiles = nbm * nbn; k.residual = nullptr; k.rowbias = nullptr; k.bias = nullptr;
+        const dim3 grid((unsigned)(nbm * nbn * nsplit)), block(256);
+#define QD_WQ_PART(WB, FH) { if (split) hipLaunchKernelGGL((wq_h16_kernel<WB, FH, true, O_PART>), grid, block, 0, st, k); \
+                             else hipLaunchKernelGGL((wq_h16_kernel<WB, FH, false, O_PART>), grid, block, 0, st, k); }
+        if (d->wbits == 4) { if (fh) QD_WQ_PART(4, true) else QD_WQ_PART(4, false) }
+        else { if (fh) QD_WQ_PART(8, true) else QD_WQ_PART(8, false) }
+#undef QD_WQ_PART
+        QD_LAUNCH_CHECK("qd_conv2d_wq_h16 (split-K)");
+        const int N = d->Cout, esz = o16 ? 2 : 4;
+        const bool vec = N % 4 == 0 && d->ldo % 4 == 0 && qd_aligned(d->out, 4 * esz) && (!d->bias || qd_aligned(d->bias, 16)) &&
+                         (!d->rowbias || (qd_aligned(d->rowbias, 16) && d->ld_rowbias % 4 == 0)) &&
+                         (!d->residual || (qd_aligned(d->residual, 4 * esz) && d->ldr % 4 == 0));
+        const long threads = vec ? M * N / 4 : M * N;
+        const dim3 fgrid((unsigned)((threads + 255) / 256));
+#define QD_WQ_FIN(O, V) hipLaunchKernelGGL((wq_splitk_finalize_kernel<O, V>), fgrid, block, 0, st, ws, nsplit, M, N, d->Ho * d->Wo, d->bias, \
+                                           d->rowbias, (long)d->ld_rowbias, d->residual, (long)d->ldr, d->out, (long)d->ldo)
+        if (o16) { if (vec) QD_WQ_FIN(O_F16, true); else QD_WQ_FIN(O_F16, false); }
+        else { if (vec) QD_WQ_FIN(O_F32, true); else QD_WQ_FIN(O_F32, false); }
+#undef QD_WQ_FIN
+        QD_LAUNCH_CHECK("qd_conv2d_wq_h16 (split-K finalise)");
+        return 0;
+    }
+    const dim3 grid((unsigned)(nbm * nbn)), block(256);
 #define QD_WQ(WB, FH, SP, O) hipLaunchKernelGGL((wq_h16_kernel<WB, FH, SP, O>), grid, block, 0, st, k)
 #define QD_WQ_OUT(WB, FH, SP) { if (o16) QD_WQ(WB, FH, SP, O_F16); else QD_WQ(WB, FH, SP, O_F32); }
 #define QD_WQ_SPLIT(WB, FH) { if (geglu) QD_WQ(WB, FH, false, O_GEGLU_H); else if (split) QD_WQ_OUT(WB, FH, true) else QD_WQ_OUT(WB, FH, false) }
@@ -2281,6 +2447,15 @@ int run_wq_h16(const qd_conv_desc* d, int act_dtype, void* stream) {
 }  // namespace
 
 extern "C" int qd_conv2d_wq_h16(const qd_conv_desc* d, int act_dtype, void* stream) { return run_wq_h16(d, act_dtype, stream); }
+
+extern "C" int64_t qd_conv2d_wq_h16_splitk_ws_bytes(const qd_conv_desc* d) {
+    if (!d) return 0;
+    int it_per;
+    const int S = choose_wq_splitk(d, &it_per);
+    return S < 2 ? 0 : (int64_t)S * d->B * d->Ho * d->Wo * d->Cout * 4;
+}
+
+extern "C" void qd_wq_h16_config(int splitk) { wq_splitk_knob() = splitk < 0 ? -1 : (splitk == 1 ? 0 : splitk); }
 
 extern "C" int qd_rows_to_h16(const void* x, int x_dtype, int64_t B, int64_t C, int64_t S, int64_t sb, int64_t sc, int64_t ss,
                               int c0, int clen, int clen_pad, void* out, int out_dtype, int64_t ldo, int oc0, void* stream) {

@@ -490,6 +490,35 @@ def set_weight_only_kernel(dtype):
     WEIGHT_ONLY_KERNEL = dtype
 
 
+def _parse_flag(v, name):
+    v = (v or "").strip().lower()
+    if v in ("", "0", "off", "false", "no"):
+        return False
+    if v in ("1", "on", "true", "yes"):
+        return True
+    raise ValueError(f"{name}={v!r}: expected 1 or 0")
+
+
+# Weights-only split-K: False (default) = every qd_conv2d_wq_h16 launch is the one launch it always was; True =
+# wonly_forward lends the launch the shared split-K scratch, and the library contracts layers that leave CUs idle in K slices
+# (its policy: qd_conv2d_wq_h16_splitk_ws_bytes).  The GEGLU epilogue never splits.  Effective only while WEIGHT_ONLY_KERNEL is
+# set.  QDIFF_WEIGHT_ONLY_SPLITK=1, or engine.set_weight_only_splitk().
+WEIGHT_ONLY_SPLITK = _parse_flag(os.environ.get("QDIFF_WEIGHT_ONLY_SPLITK"), "QDIFF_WEIGHT_ONLY_SPLITK")
+
+# launches that were contracted split-K (tests read it)
+WONLY_SPLITK = [0]
+
+
+def set_weight_only_splitk(on):
+    """True / False (or the strings QDIFF_WEIGHT_ONLY_SPLITK accepts)."""
+    global WEIGHT_ONLY_SPLITK
+    if isinstance(on, str):
+        on = _parse_flag(on, "QDIFF_WEIGHT_ONLY_SPLITK")
+    if not isinstance(on, bool):
+        raise ValueError("weight-only split-K must be True or False")
+    WEIGHT_ONLY_SPLITK = on
+
+
 def wonly_device_ok(t):
     """The weights-only kernel runs on GPU tensors only; anything else keeps the library path."""
     return t.is_cuda
@@ -578,7 +607,8 @@ def wonly_forward(plan, xh, B, H, W, Ho, Wo, out_dtype=torch.float32, residual=N
                         ldk=plan.pack.ldk, ldo=out.stride(0), ldr=(residual.stride(0) if residual is not None else 0),
                         ld_rowbias=(rowbias.stride(0) if rowbias is not None else 0),
                         B=B, H=H, W=W, Ho=Ho, Wo=Wo, Cout=plan.Cout, kh=plan.kh, kw=plan.kw, stride=plan.stride,
-                        pad_t=plan.pad, pad_l=plan.pad, wbits=plan.pack.wbits, w_tiled=True, segs=plan.segs)
+                        pad_t=plan.pad, pad_l=plan.pad, wbits=plan.pack.wbits, w_tiled=True, segs=plan.segs,
+                        splitk=True if WEIGHT_ONLY_SPLITK else None)
     hip.conv2d_wq_h16(call, plan.act_dtype)
     return out
 
@@ -605,15 +635,6 @@ def wonly_forward_geglu(gplan, xh, M, next_plan):
 # weights-only block fusion: the norms, GEGLU, the embedding add and the residual adds of a weights-only block as producers
 # and epilogues of the kernels above (qd_groupnorm_h16, qd_layernorm_h16, qd_geglu_h16, rowbias / residual of qd_conv2d_wq_h16)
 # ------------------------------------------------------------------------------------------------
-def _parse_flag(v, name):
-    v = (v or "").strip().lower()
-    if v in ("", "0", "off", "false", "no"):
-        return False
-    if v in ("1", "on", "true", "yes"):
-        return True
-    raise ValueError(f"{name}={v!r}: expected 1 or 0")
-
-
 # Weights-only fusion: False (default) = a weights-only block runs the reference's composition, every QuantModule entered
 # through its own forward (library norms, qd_rows_to_h16 per consumer, separate adds); True = the plain residual blocks and
 # the transformer blocks run QuantResBlock._forward_wonly / QuantBasicTransformerBlock._forward_wonly.  Effective only while

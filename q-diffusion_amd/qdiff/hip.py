@@ -69,6 +69,7 @@ EXPORTS = ["qd_abi_version", "qd_last_error", "qd_device_ok", "qd_box_probe", "q
            "qd_fakequant_blocks", "qd_fakequant_fwd", "qd_fakequant_bwd",
            "qd_conv2d_bf16", "qd_pack_weights_bf16_bytes", "qd_pack_weights_bf16", "qd_groupnorm_silu_bf16",
            "qd_pack_weights_h16", "qd_groupnorm_silu_h16", "qd_conv2d_wq_h16", "qd_rows_to_h16",
+           "qd_conv2d_wq_h16_splitk_ws_bytes", "qd_wq_h16_config",
            "qd_attn_h16", "qd_layernorm_h16", "qd_geglu_h16", "qd_groupnorm_h16"]
 
 _lib = None
@@ -131,6 +132,10 @@ def load():
     lib.qd_groupnorm_silu_h16.argtypes = [vp, i64, i64, i32, i64, i32, f32, vp, vp, i32, i32, vp, i64, vp, vp, i32, i64, vp]
     lib.qd_conv2d_wq_h16.argtypes = [ctypes.POINTER(ConvDesc), i32, vp]
     lib.qd_rows_to_h16.argtypes = [vp, i32, i64, i64, i64, i64, i64, i64, i32, i32, i32, vp, i32, i64, i32, vp]
+    lib.qd_conv2d_wq_h16_splitk_ws_bytes.argtypes = [ctypes.POINTER(ConvDesc)]
+    lib.qd_conv2d_wq_h16_splitk_ws_bytes.restype = ctypes.c_int64
+    lib.qd_wq_h16_config.argtypes = [i32]
+    lib.qd_wq_h16_config.restype = None
     lib.qd_attn_h16.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32] + [i64] * 12 + [f32, i32, vp, i32, i64, vp]
     lib.qd_layernorm_h16.argtypes = [vp, i32, i64, i32, i64, f32, vp, vp, vp, i32, i64, vp]
     lib.qd_geglu_h16.argtypes = [vp, i32, i64, i32, i64, vp, i32, i64, vp]
@@ -411,7 +416,27 @@ def conv2d_wq_h16(c, act_dtype):
     elif c.epilogue not in (None, EPI_LINEAR):
         raise HipEngineError("conv2d_wq_h16: epilogue must be EPI_LINEAR or EPI_GEGLU_H16")
     d = _conv_desc(c)
+    split = False
+    if c.splitk:                                    # engine.WEIGHT_ONLY_SPLITK: the library decides, the host lends the scratch
+        need = int(load().qd_conv2d_wq_h16_splitk_ws_bytes(ctypes.byref(d)))
+        if need:
+            ws = _splitk_scratch(c.x.device, need)
+            d.splitk_ws, d.splitk_ws_bytes = ws.data_ptr(), ws.numel()
+            split = True
     _check(load().qd_conv2d_wq_h16(ctypes.byref(d), _H16[act_dtype], _stream()), "qd_conv2d_wq_h16")
+    if split:
+        from . import engine
+        engine.WONLY_SPLITK[0] += 1
+
+
+def wq_h16_splitk_ws_bytes(c):
+    """Scratch bytes the library would use to contract weights-only ConvCall `c` split-K (0 = launched unsplit)."""
+    return int(load().qd_conv2d_wq_h16_splitk_ws_bytes(ctypes.byref(_conv_desc(c))))
+
+
+def wq_h16_config(splitk=-1):
+    """qd_wq_h16_config: -1 = the library's split-K policy, 0 (or 1: one slice) = never split, n >= 2 = force n slices."""
+    load().qd_wq_h16_config(int(splitk))
 
 
 def attn_h16(q, k, v, B, T, S, H, d, q_strides, k_strides, v_strides, scale, op_dtype, out):

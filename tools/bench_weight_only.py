@@ -22,6 +22,14 @@ apart.  --fuse-shapes prints the three producers alone at SD's shapes: microseco
 next to a plain device copy of the same bytes and the ~6.3 TB/s streaming ceiling.
 
     python tools/bench_weight_only.py --attn --fuse [--models sd,ldm] [--rounds 3] [--fuse-shapes]
+
+--splitk: every other weights-only knob on (layer and attention kernels at fp16, fusion, wide fusion) and
+engine.WEIGHT_ONLY_SPLITK off / on alternated --rounds times in one process: best, all values and spread of each side, the
+launches that split, the distance of the outputs.  --splitk-shapes: the under-filled contraction shapes of SD-v1.4 and LDM-4
+at batch 16 alone (HIP events, median and min..max of 3 repeats of 20 launches): the unsplit launch against forced slice counts
+(hip.wq_h16_config, finalise included) and against the library's policy.
+
+    python tools/bench_weight_only.py --splitk [--models sd,ldm,cifar] [--rounds 3] [--splitk-shapes]
 """
 import argparse
 import json
@@ -289,6 +297,120 @@ def run_wide(kind, batch, k, dev, attn, rounds):
     return res
 
 
+def run_splitk(kind, batch, k, dev, rounds):
+    """Layer and attention kernels at fp16, fusion and wide fusion on; engine.WEIGHT_ONLY_SPLITK off / on alternated."""
+    import bench
+    from qdiff import engine, hip, synthetic
+    qnn, _ = bench.build_quantised_unet(kind, dev)
+    x, t, c = synthetic.synthetic_inputs(kind, batch, seed=0)
+    args = [a.to(dev) for a in (x, t, c) if a is not None]
+    qnn.set_quant_state(True, False)
+    one = lambda: qnn(*args)
+    res = {"model": kind, "batch": batch, "layer_knob": "fp16", "attn_knob": "fp16", "fuse": True, "wide": True, "evals_timed": k, "rounds": rounds}
+    prev = (engine.WEIGHT_ONLY_KERNEL, engine.WEIGHT_ONLY_ATTN, engine.WEIGHT_ONLY_FUSE, engine.WEIGHT_ONLY_FUSE_WIDE, engine.WEIGHT_ONLY_SPLITK)
+    try:
+        engine.set_weight_only_kernel(torch.float16)
+        engine.set_weight_only_attention(torch.float16)
+        engine.set_weight_only_fusion(True)
+        engine.set_weight_only_fusion_wide(True)
+        ms, ticks = hip.box_probe(dev, 0, 512, 60000)
+        res["box_probe_mfma_ms"] = round(ms, 3)
+        off, on = [], []
+        for _ in range(rounds):                                  # alternated A/B
+            engine.set_weight_only_splitk(False)
+            off.append(_timed(one, k))
+            engine.set_weight_only_splitk(True)
+            on.append(_timed(one, k))
+        res["splitk_off_ms"], res["splitk_on_ms"] = round(min(off), 3), round(min(on), 3)
+        res["splitk_off_ms_all"], res["splitk_on_ms_all"] = [round(v, 3) for v in off], [round(v, 3) for v in on]
+        res["splitk_off_spread_ms"], res["splitk_on_spread_ms"] = round(max(off) - min(off), 3), round(max(on) - min(on), 3)
+        res["faster_by_more_than_spread"] = bool(min(off) - max(on) > 0 and min(off) - min(on) > max(max(off) - min(off), max(on) - min(on)))
+        outs = {}
+        for name, flag in (("off", False), ("on", True)):
+            engine.set_weight_only_splitk(flag)
+            engine.WONLY_SPLITK[0] = 0
+            ms, tflop, n = _contraction_class(one)
+            res[f"splitk_{name}_contraction_ms"], res[f"splitk_{name}_contraction_launches"] = round(ms, 3), n
+            res[f"splitk_{name}_split_launches"] = engine.WONLY_SPLITK[0]
+            with torch.no_grad():
+                outs[name] = one()
+        res["splitk_on_vs_off_of_range"] = float((outs["on"] - outs["off"]).abs().max() / outs["off"].abs().max())
+    finally:
+        engine.set_weight_only_kernel(prev[0])
+        engine.set_weight_only_attention(prev[1])
+        engine.set_weight_only_fusion(prev[2])
+        engine.set_weight_only_fusion_wide(prev[3])
+        engine.set_weight_only_splitk(prev[4])
+    return res
+
+
+# Under-filled contractions at batch 16: (name, H = W, kernel, input segments, Cout); M = 16 * H * W unless given
+SPLITK_SHAPES = [
+    ("sd 8x8 3x3 1280->1280", 8, 3, [1280], 1280), ("sd 8x8 3x3 2560->1280 shortcut", 8, 3, [1280, 1280], 1280),
+    ("sd 16x16 3x3 1280->1280", 16, 3, [1280], 1280), ("sd 16x16 3x3 640->1280", 16, 3, [640], 1280),
+    ("sd 16x16 3x3 2560->1280 shortcut", 16, 3, [1280, 1280], 1280), ("sd 16x16 3x3 1920->1280 shortcut", 16, 3, [1280, 640], 1280),
+    ("sd 16x16 1x1 1280->1280", 16, 1, [1280], 1280), ("sd 16x16 ff out 5120->1280", 16, 1, [5120], 1280),
+    ("sd 8x8 1x1 2560->1280 skip", 8, 1, [1280, 1280], 1280),
+    ("sd 32x32 3x3 640->640", 32, 3, [640], 640), ("sd 32x32 3x3 1920->640 shortcut", 32, 3, [1280, 640], 640),
+    ("sd to_k / to_v M=1232 768->1280", (1, 1232), 1, [768], 1280), ("sd to_k / to_v M=1232 768->640", (1, 1232), 1, [768], 640),
+    ("sd temb M=16 1280->1280", (1, 16), 1, [1280], 1280),
+    ("ldm 8x8 3x3 896->896", 8, 3, [896], 896), ("ldm 8x8 3x3 1792->896 shortcut", 8, 3, [896, 896], 896),
+    ("ldm 16x16 3x3 672->672", 16, 3, [672], 672), ("ldm 16x16 3x3 1568->672 shortcut", 16, 3, [896, 672], 672),
+    ("ldm 32x32 3x3 448->448", 32, 3, [448], 448),
+]
+
+
+def splitk_shape_table(dev, counts=(2, 3, 4, 6, 8, 12, 16)):
+    from types import SimpleNamespace as NS
+    from qdiff import engine, hip
+    g = torch.Generator(device=dev).manual_seed(0)
+    prev = engine.WEIGHT_ONLY_SPLITK
+    engine.set_weight_only_splitk(True)
+
+    def quant(w):
+        flat = w.reshape(w.shape[0], -1)
+        mn, mx = flat.min(1)[0].clamp(max=0), flat.max(1)[0].clamp(min=0)
+        d = ((mx - mn) / 15).clamp(min=1e-8)
+        return NS(delta=d, zero_point=torch.round(-mn / d), n_bits=4, n_levels=16, sym=False, alpha=None, soft_targets=False)
+
+    def med(fn):
+        v = sorted(1000 * _events_ms(fn, 20) for _ in range(3))
+        return [round(v[1], 1), round(v[0], 1), round(v[2], 1)]       # median, min, max
+
+    try:
+        for name, hw, k, segs, Cout in SPLITK_SHAPES:
+            B, H, W = (16, hw, hw) if isinstance(hw, int) else (1,) + hw
+            Cin = sum(segs)
+            w = torch.randn(Cout, Cin, k, k, device=dev, generator=g) * 0.05
+            bounds = [(0, segs[0])] + ([(segs[0], Cin)] if len(segs) == 2 else [])
+            pack = engine.pack_module_weights(w if k > 1 else w.view(Cout, Cin, 1, 1), [quant(w[:, a:b]) for a, b in bounds], segs[0] if len(segs) == 2 else 0)
+            bias = torch.randn(Cout, device=dev, generator=g)
+            for dname, dt in (("fp16", torch.float16), ("bf16", torch.bfloat16)):
+                plan = engine.build_wonly_plan(pack, k, k, 1, k // 2, bias, dt)
+                M = B * H * W
+                xh = torch.randn(M, plan.ldx, device=dev, generator=g).to(dt)
+                fn = lambda: engine.wonly_forward(plan, xh, B, H, W, H, W)
+                call = hip.ConvCall(x=xh, w=pack.wq, out=bias, ldx=plan.ldx, ldk=pack.ldk, ldo=Cout, B=B, H=H, W=W, Ho=H, Wo=W, Cout=Cout, kh=k, kw=k,
+                                    stride=1, pad_t=k // 2, pad_l=k // 2, wbits=pack.wbits, w_tiled=True, segs=plan.segs)
+                row = {"layer": name, "operands": dname, "M": M, "N": Cout, "tiles": ((M + 127) // 128) * ((Cout + 127) // 128),
+                       "ksteps": k * k * sum((s["clen"] + 63) // 64 for s in plan.segs)}
+                hip.wq_h16_config(0)
+                row["unsplit_us"] = med(fn)
+                for n in counts:
+                    hip.wq_h16_config(n)
+                    got = hip.wq_h16_splitk_ws_bytes(call) // (M * Cout * 4)
+                    if got == n:
+                        row[f"n{n}_us"] = med(fn)
+                hip.wq_h16_config(-1)
+                row["policy_nsplit"] = hip.wq_h16_splitk_ws_bytes(call) // (M * Cout * 4) or 1
+                row["policy_us"] = med(fn)
+                print(json.dumps(row), flush=True)
+            del w, pack, plan, xh
+    finally:
+        hip.wq_h16_config(-1)
+        engine.set_weight_only_splitk(prev)
+
+
 def wide_shape_table(dev):
     """The GEGLU projection alone at SD's three shapes (W4, fp16): one launch with the GEGLU epilogue on the interleaved pack
     against the linear launch (fp32 [M][2F]) + qd_geglu_h16 on the same weights."""
@@ -403,6 +525,8 @@ def main():
     ap.add_argument("--fuse-shapes", action="store_true", help="the three producers alone at SD's shapes")
     ap.add_argument("--wide", action="store_true", help="with --fuse: the wide-fusion column (fusion on, wide off / on alternated) and the "
                                                         "GEGLU projection alone at SD's three shapes")
+    ap.add_argument("--splitk", action="store_true", help="the split-K column: every other weights-only knob on, split-K off / on alternated")
+    ap.add_argument("--splitk-shapes", action="store_true", help="the under-filled contraction shapes alone: unsplit against forced slice counts")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     from qdiff import hip
@@ -414,8 +538,12 @@ def main():
         fuse_shape_table(dev)
     if a.wide:
         wide_shape_table(dev)
-    for kind in a.models.split(","):
-        if a.wide:
+    if a.splitk_shapes:
+        splitk_shape_table(dev)
+    for kind in [m for m in a.models.split(",") if m]:           # --models "" = the shape tables alone
+        if a.splitk:
+            res = run_splitk(kind, a.batch, a.evals, dev, a.rounds)
+        elif a.wide:
             res = run_wide(kind, a.batch, a.evals, dev, a.attn, a.rounds)
         elif a.fuse:
             res = run_fuse(kind, a.batch, a.evals, dev, a.attn, a.rounds)
