@@ -538,6 +538,23 @@ int qd_attn_h16(const void* q, const void* k, const void* v, int in_dtype, int B
  *         `out_layers` norm + SiLU of ResBlock (ldm/modules/diffusionmodules/openaimodel.py:201-232, qdiff/quant_block.py:
  *         83-111); apply_silu = 0 is the plain Normalize in front of an attention block or a SpatialTransformer's proj_in.
  *         gamma / beta may be NULL.  C a multiple of 8 and of groups.  ws: qd_groupnorm_ws_bytes(B, C, S) bytes.
+ *     qd_groupnorm_mod_h16 (additive in ABI 20): `out_norm(h) * (1 + scale) + shift` (+ SiLU) of a
+ *         use_scale_shift_norm ResBlock (qdiff/quant_block.py:99-103) -> operand rows.  mod: fp32 [B][mod_ld >= 2C] rows
+ *         scale | shift, one per sample (the two halves of the embedding projection), as in qd_groupnorm_mod_silu_quant; it
+ *         is folded into the per-(sample, channel) affine, a' = a (1 + scale), sh' = sh (1 + scale) + shift in fp32, so with
+ *         mod all zeros the rows are value-equal to qd_groupnorm_h16's.  Otherwise the arguments and checks of
+ *         qd_groupnorm_h16; mod must not be NULL.
+ *     qd_groupnorm_resample_h16 (additive in ABI 20): GroupNorm (+ SiLU) of a channels-last [B][H][W][C] map
+ *         resampled BEFORE the one rounding: `in_layers[:-1]` and `h_upd` of an `updown` ResBlock (qdiff/quant_block.py:84-90)
+ *         -> the operand rows of `in_layers[-1]`.  Statistics over the full-resolution input; ws: qd_groupnorm_ws_bytes(B, C, H*W).
+ *         resample = 1: the 2x2 average of ResBlock(down=True) (openaimodel.py:134-160: Downsample(channels, False) =
+ *             AvgPool2d(2, 2)); out rows [B * H/2 * W/2][ldo]; each output is ((y00 + y01) + (y10 + y11)) * 0.25f of the four
+ *             fp32 post-SiLU values y(2h+dy, 2w+dx) = y_dydx, in exactly that order, then one round-to-nearest-even.  H and W
+ *             must be even.
+ *         resample = 2: nearest 2x of ResBlock(up=True) (openaimodel.py:91-117: Upsample(channels, False) =
+ *             F.interpolate(scale_factor=2, mode="nearest")); out rows [B * 2H * 2W][ldo]; the rounded result of input pixel
+ *             (h, w) is written to the four rows (2h + dy, 2w + dx): value-equal to qd_groupnorm_h16's rows replicated.
+ *         Any other resample is refused.
  * ------------------------------------------------------------------------------------------ */
 int qd_layernorm_h16(const void* x, int x_dtype, int64_t M, int C, int64_t ldx, float eps, const float* gamma,
                      const float* beta, void* out, int out_dtype, int64_t ldo, void* stream);
@@ -546,6 +563,12 @@ int qd_geglu_h16(const void* h, int h_dtype, int64_t M, int F, int64_t ldh, void
 int qd_groupnorm_h16(const void* x, int x_dtype, int64_t B, int64_t S, int C, int64_t ldx, int groups, float eps,
                      const float* gamma, const float* beta, int apply_silu, void* out, int out_dtype, int64_t ldo,
                      void* ws, void* stream);
+int qd_groupnorm_mod_h16(const void* x, int x_dtype, int64_t B, int64_t S, int C, int64_t ldx, int groups, float eps,
+                         const float* gamma, const float* beta, const float* mod, int64_t mod_ld, int apply_silu, void* out,
+                         int out_dtype, int64_t ldo, void* ws, void* stream);
+int qd_groupnorm_resample_h16(const void* x, int x_dtype, int64_t B, int H, int W, int C, int64_t ldx, int groups, float eps,
+                              const float* gamma, const float* beta, int apply_silu, int resample, void* out, int out_dtype,
+                              int64_t ldo, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,8 @@
 // atomics) and one apply pass that reads the activation once and writes one byte per element.
 // GroupNorm has ONE statistics driver (gn_stats: partial sums, gn_finalize_kernel<64 | 256>, optional modulation) behind its
 // three kinds of entry, which differ in the apply pass alone: int8 codes (gn_apply_kernel, gn_apply_rows_kernel,
-// gn_apply_rows_h8_kernel), and fp16 / bf16 rows (gn_apply_h16_kernel) for the first-stage decoder and the weights-only blocks.
+// gn_apply_rows_h8_kernel), and fp16 / bf16 rows (gn_apply_h16_kernel; gn_apply_resample_h16_kernel for the resampling residual
+// blocks) for the first-stage decoder and the weights-only blocks.
 #include "common.h"
 
 namespace {
@@ -998,6 +999,83 @@ inline unsigned h16_stream_grid(long total) {
     return (unsigned)(nblk < 8192 ? nblk : 8192);
 }
 
+// GroupNorm apply of a [B][H][W][C] map resampled on the way to the operand rows (the `updown` residual blocks: reference
+// quant_block.py:84-90 puts h_upd between norm . SiLU and the first convolution).  The per-element arithmetic up to the
+// rounding is gn_apply_h16_kernel's, expression for expression.  Thread = (row, 8-channel chunk of the ldo-wide output row),
+// grid-stride over total, pad chunks written as zeros.
+//   MODE 1  2x2 average (Downsample without convolution = AvgPool2d(2, 2)): row = one OUTPUT pixel of the [B][H/2][W/2] map;
+//           the four 16-byte loads of its window are issued back to back, the four post-SiLU fp32 values are combined as
+//           ((y00 + y01) + (y10 + y11)) * 0.25f and rounded once.  A quarter of the stores of the full-resolution pass.
+//   MODE 2  nearest 2x: row = one INPUT pixel; its rounded chunk goes to the four rows (2h + dy, 2w + dx) of the
+//           [B][2H][2W] map.  One read, the SiLU once per input element instead of four times.
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void gn_apply_resample_h16_kernel(const T* __restrict__ x, long total, int H, int W, int C, long ldx,
+                                                                    const float* __restrict__ ab, int apply_silu,
+                                                                    unsigned short* __restrict__ out, long ldo, int fh) {
+    static_assert(MODE == 1 || MODE == 2, "1 = 2x2 average, 2 = nearest 2x");
+    constexpr int NP = MODE == 1 ? 4 : 1;          // input pixels per thread
+    const int nch = C >> 3, nout = (int)(ldo >> 3);
+    const int Wr = MODE == 1 ? W >> 1 : W, Hr = MODE == 1 ? H >> 1 : H;      // the map the thread index runs over
+    for (long gid = (long)blockIdx.x * 256 + threadIdx.x; gid < total; gid += (long)gridDim.x * 256) {
+        const long row = gid / nout;
+        const int c8 = (int)(gid - row * nout);
+        const long t = row / Wr;                   // b * Hr + h
+        const int w = (int)(row - t * Wr);
+        const long b = t / Hr;
+        const int h = (int)(t - b * Hr);
+        v4i pk = {0, 0, 0, 0};
+        if (c8 < nch) {
+            const long in0 = MODE == 1 ? (b * H + 2 * h) * W + 2 * w : row;
+            float v[NP][8], y[NP][8];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) h16_ld8(x + (in0 + (p >> 1) * (long)W + (p & 1)) * ldx + c8 * 8, v[p]);
+            const float* abp = ab + (b * C + c8 * 8) * 2;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float4 tt = *reinterpret_cast<const float4*>(abp + 4 * j);
+#pragma unroll
+                for (int p = 0; p < NP; ++p) {
+                    y[p][2 * j] = v[p][2 * j] * tt.x + tt.y;
+                    y[p][2 * j + 1] = v[p][2 * j + 1] * tt.z + tt.w;
+                }
+            }
+            if (apply_silu) {
+#pragma unroll
+                for (int p = 0; p < NP; ++p)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) y[p][j] = y[p][j] * (1.0f / (1.0f + expf(-y[p][j])));
+            }
+            if constexpr (MODE == 1) {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) y[0][j] = ((y[0][j] + y[1][j]) + (y[2][j] + y[3][j])) * 0.25f;
+            }
+            pk = h16_pack8(y[0], fh);
+        }
+        if constexpr (MODE == 1) {
+            *reinterpret_cast<v4i*>(out + row * ldo + c8 * 8) = pk;
+        } else {
+            unsigned short* o = out + ((t * 2) * (2L * W) + 2 * w) * ldo + c8 * 8;
+            *reinterpret_cast<v4i*>(o) = pk;
+            *reinterpret_cast<v4i*>(o + ldo) = pk;
+            *reinterpret_cast<v4i*>(o + 2L * W * ldo) = pk;
+            *reinterpret_cast<v4i*>(o + (2L * W + 1) * ldo) = pk;
+        }
+    }
+}
+
+// the argument checks every GroupNorm -> operand rows entry shares (qd_groupnorm_h16's)
+inline int gn_h16_args(const char* who, const void* x, int x_dtype, int64_t B, int64_t S, int C, int64_t ldx, int groups, const void* out,
+                       int out_dtype, int64_t ldo, const void* ws) {
+    QD_REQUIRE(x && out && ws, "%s: null pointer", who);
+    QD_REQUIRE(x_dtype == QD_F32 || x_dtype == QD_F16, "%s: x_dtype must be f32/f16", who);
+    QD_REQUIRE(out_dtype == QD_F16 || out_dtype == QD_BF16, "%s: out_dtype must be f16/bf16", who);
+    QD_REQUIRE(B > 0 && B < 65536 && S > 0 && C > 0 && groups > 0 && C % groups == 0 && C % 8 == 0,
+               "%s: C=%d must be a multiple of 8 and of groups=%d", who, C, groups);
+    QD_REQUIRE(ldx >= C && ldx % (x_dtype == QD_F32 ? 4 : 8) == 0 && qd_aligned(x, 16), "%s: input rows must be 16-byte aligned", who);
+    QD_REQUIRE(ldo >= C && ldo % 8 == 0 && qd_aligned(out, 16), "%s: output rows must be 16-byte aligned (ldo %% 8 == 0)", who);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int qd_layernorm_h16(const void* x, int x_dtype, int64_t M, int C, int64_t ldx, float eps, const float* gamma,
@@ -1057,5 +1135,58 @@ extern "C" int qd_groupnorm_h16(const void* x, int x_dtype, int64_t B, int64_t S
         hipLaunchKernelGGL((gn_apply_h16_kernel<__half, true>), dim3(h16_stream_grid(total)), dim3(256), 0, st, (const __half*)x, total, (long)S, C, (long)ldx, ab, apply_silu,
                            reinterpret_cast<unsigned short*>(out), (long)ldo, fh);
     QD_LAUNCH_CHECK("qd_groupnorm_h16");
+    return 0;
+}
+
+// `out_norm(h) * (1 + scale) + shift` (+ SiLU) of a use_scale_shift_norm residual block (reference quant_block.py:99-103) as
+// operand rows: qd_groupnorm_h16 with the modulation of qd_groupnorm_mod_silu_quant folded into the per-(sample, channel)
+// affine (gn_stats' mod), so the apply pass is the same launch.  mod: fp32 [B][mod_ld >= 2C] rows scale | shift.
+extern "C" int qd_groupnorm_mod_h16(const void* x, int x_dtype, int64_t B, int64_t S, int C, int64_t ldx, int groups, float eps,
+                                    const float* gamma, const float* beta, const float* mod, int64_t mod_ld, int apply_silu,
+                                    void* out, int out_dtype, int64_t ldo, void* ws, void* stream) {
+    if (int rc = gn_h16_args("qd_groupnorm_mod_h16", x, x_dtype, B, S, C, ldx, groups, out, out_dtype, ldo, ws)) return rc;
+    QD_REQUIRE(mod, "qd_groupnorm_mod_h16: null modulation rows");
+    QD_REQUIRE(mod_ld >= 2 * (int64_t)C, "qd_groupnorm_mod_h16: modulation rows hold scale | shift: mod_ld >= 2 C");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const float* ab = gn_stats(x, x_dtype, B, S, C, ldx, groups, eps, gamma, beta, ws, nullptr, 0, 0, true, mod, mod_ld, st);
+    const long total = (long)B * S * (ldo / 8);
+    const int fh = out_dtype == QD_F16 ? 1 : 0;
+    if (x_dtype == QD_F32)
+        hipLaunchKernelGGL((gn_apply_h16_kernel<float, true>), dim3(h16_stream_grid(total)), dim3(256), 0, st, (const float*)x, total, (long)S, C, (long)ldx, ab, apply_silu,
+                           reinterpret_cast<unsigned short*>(out), (long)ldo, fh);
+    else
+        hipLaunchKernelGGL((gn_apply_h16_kernel<__half, true>), dim3(h16_stream_grid(total)), dim3(256), 0, st, (const __half*)x, total, (long)S, C, (long)ldx, ab, apply_silu,
+                           reinterpret_cast<unsigned short*>(out), (long)ldo, fh);
+    QD_LAUNCH_CHECK("qd_groupnorm_mod_h16");
+    return 0;
+}
+
+// GroupNorm (+ SiLU) of a [B][H][W][C] map, resampled before the one rounding: the `in_layers` norm . SiLU and h_upd of an
+// `updown` residual block (reference quant_block.py:84-90; openaimodel.py:134-160 Downsample(channels, False) = AvgPool2d(2, 2),
+// :91-117 Upsample(channels, False) = nearest 2x) as the operand rows of the block's first convolution.  Statistics over the
+// full-resolution input (gn_stats unchanged).  resample 1: rows [B * H/2 * W/2][ldo]; 2: rows [B * 2H * 2W][ldo].
+extern "C" int qd_groupnorm_resample_h16(const void* x, int x_dtype, int64_t B, int H, int W, int C, int64_t ldx, int groups, float eps,
+                                         const float* gamma, const float* beta, int apply_silu, int resample, void* out,
+                                         int out_dtype, int64_t ldo, void* ws, void* stream) {
+    QD_REQUIRE(H > 0 && W > 0, "qd_groupnorm_resample_h16: empty map");
+    if (int rc = gn_h16_args("qd_groupnorm_resample_h16", x, x_dtype, B, (int64_t)H * W, C, ldx, groups, out, out_dtype, ldo, ws)) return rc;
+    QD_REQUIRE(resample == 1 || resample == 2, "qd_groupnorm_resample_h16: resample=%d must be 1 (2x2 average) or 2 (nearest 2x)", resample);
+    QD_REQUIRE(resample != 1 || (H % 2 == 0 && W % 2 == 0), "qd_groupnorm_resample_h16: the 2x2 average needs even H, W (got %d x %d)", H, W);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const long S = (long)H * W;
+    const float* ab = gn_stats(x, x_dtype, B, S, C, ldx, groups, eps, gamma, beta, ws, nullptr, 0, 0, true, nullptr, 0, st);
+    const long total = (resample == 1 ? (long)B * (H / 2) * (W / 2) : (long)B * S) * (ldo / 8);     // threads: output / input pixels
+    const int fh = out_dtype == QD_F16 ? 1 : 0;
+    unsigned short* o = reinterpret_cast<unsigned short*>(out);
+    const dim3 grid(h16_stream_grid(total));
+    if (x_dtype == QD_F32 && resample == 1)
+        hipLaunchKernelGGL((gn_apply_resample_h16_kernel<float, 1>), grid, dim3(256), 0, st, (const float*)x, total, H, W, C, (long)ldx, ab, apply_silu, o, (long)ldo, fh);
+    else if (x_dtype == QD_F32)
+        hipLaunchKernelGGL((gn_apply_resample_h16_kernel<float, 2>), grid, dim3(256), 0, st, (const float*)x, total, H, W, C, (long)ldx, ab, apply_silu, o, (long)ldo, fh);
+    else if (resample == 1)
+        hipLaunchKernelGGL((gn_apply_resample_h16_kernel<__half, 1>), grid, dim3(256), 0, st, (const __half*)x, total, H, W, C, (long)ldx, ab, apply_silu, o, (long)ldo, fh);
+    else
+        hipLaunchKernelGGL((gn_apply_resample_h16_kernel<__half, 2>), grid, dim3(256), 0, st, (const __half*)x, total, H, W, C, (long)ldx, ab, apply_silu, o, (long)ldo, fh);
+    QD_LAUNCH_CHECK("qd_groupnorm_resample_h16");
     return 0;
 }

@@ -674,6 +674,29 @@ def wonly_wide_state():
     return WEIGHT_ONLY_FUSE_WIDE and wonly_fuse_state()
 
 
+# Modulated / resampling residual blocks, on top of WEIGHT_ONLY_FUSE (effective only while wonly_fuse_state() holds; DESIGN.md
+# §4.17): False (default) = a weights-only QuantResBlock with `use_scale_shift_norm` or `updown` keeps the reference's
+# composition; True = it runs QuantResBlock._forward_wonly_mod on qd_groupnorm_resample_h16 / qd_groupnorm_mod_h16.
+# WONLY_FUSED gets the key "resblock_mod" when a block takes the route, never while the knob is off.
+# QDIFF_WEIGHT_ONLY_FUSE_MOD=1, or engine.set_weight_only_fusion_mod().
+WEIGHT_ONLY_FUSE_MOD = _parse_flag(os.environ.get("QDIFF_WEIGHT_ONLY_FUSE_MOD"), "QDIFF_WEIGHT_ONLY_FUSE_MOD")
+
+
+def set_weight_only_fusion_mod(on):
+    """True / False (or the strings QDIFF_WEIGHT_ONLY_FUSE_MOD accepts)."""
+    global WEIGHT_ONLY_FUSE_MOD
+    if isinstance(on, str):
+        on = _parse_flag(on, "QDIFF_WEIGHT_ONLY_FUSE_MOD")
+    if not isinstance(on, bool):
+        raise ValueError("weight-only fusion of modulated / resampling blocks must be True or False")
+    WEIGHT_ONLY_FUSE_MOD = on
+
+
+def wonly_mod_state():
+    """The route of the modulated / resampling residual blocks engages: the knob, and everything wonly_fuse_state() asks."""
+    return WEIGHT_ONLY_FUSE_MOD and wonly_fuse_state()
+
+
 def wonly_count(kind):
     """One more block forward of `kind` on a fused route (a default: tests replace WONLY_FUSED by a dict without the new keys)."""
     WONLY_FUSED[kind] = WONLY_FUSED.get(kind, 0) + 1
@@ -725,6 +748,31 @@ def wonly_groupnorm_rows(x_rows, B, S, C, gn, silu, plan):
     out = torch.empty((B * S, plan.ldx), dtype=plan.act_dtype, device=x_rows.device)
     ws = _workspace(hip.groupnorm_ws_bytes(B, C, S), x_rows.device)
     hip.groupnorm_h16(x_rows, B, S, C, x_rows.stride(0), gn.num_groups, gn.eps, gn.weight, gn.bias, silu, out, plan.ldx, ws)
+    return out
+
+
+def wonly_groupnorm_mod_rows(x_rows, B, S, C, gn, mod, silu, plan):
+    """GroupNorm * (1 + scale) + shift (+ SiLU) of channels-last fp32 rows [B*S][>= C] -> the operand rows [B*S][plan.ldx] of
+    `plan`.  mod: fp32 rows [B][>= 2C] scale | shift with unit column stride (the embedding projection of the block)."""
+    x_rows = _h16_input_rows(x_rows)
+    if mod.dtype != torch.float32 or mod.dim() != 2 or mod.shape[0] != B or mod.shape[1] < 2 * C or mod.stride(1) != 1:
+        raise hip.HipEngineError("wonly_groupnorm_mod_rows: mod must be fp32 rows [B][>= 2C] with unit column stride")
+    out = torch.empty((B * S, plan.ldx), dtype=plan.act_dtype, device=x_rows.device)
+    ws = _workspace(hip.groupnorm_ws_bytes(B, C, S), x_rows.device)
+    hip.groupnorm_mod_h16(x_rows, B, S, C, x_rows.stride(0), gn.num_groups, gn.eps, gn.weight, gn.bias, mod,
+                          mod.stride(0) if B > 1 else mod.shape[1], silu, out, plan.ldx, ws)
+    return out
+
+
+def wonly_groupnorm_resample_rows(x_rows, B, H, W, C, gn, silu, resample, plan):
+    """GroupNorm (+ SiLU) of the channels-last fp32 map [B*H*W][>= C], resampled (1: 2x2 average, 2: nearest 2x) -> the operand
+    rows of `plan` at the resampled size."""
+    x_rows = _h16_input_rows(x_rows)
+    Mo = B * (H // 2) * (W // 2) if resample == 1 else B * 4 * H * W
+    out = torch.empty((Mo, plan.ldx), dtype=plan.act_dtype, device=x_rows.device)
+    ws = _workspace(hip.groupnorm_ws_bytes(B, C, H * W), x_rows.device)
+    hip.groupnorm_resample_h16(x_rows, B, H, W, C, x_rows.stride(0), gn.num_groups, gn.eps, gn.weight, gn.bias, silu, resample,
+                               out, plan.ldx, ws)
     return out
 
 

@@ -70,7 +70,7 @@ EXPORTS = ["qd_abi_version", "qd_last_error", "qd_device_ok", "qd_box_probe", "q
            "qd_conv2d_bf16", "qd_pack_weights_bf16_bytes", "qd_pack_weights_bf16", "qd_groupnorm_silu_bf16",
            "qd_pack_weights_h16", "qd_groupnorm_silu_h16", "qd_conv2d_wq_h16", "qd_rows_to_h16",
            "qd_conv2d_wq_h16_splitk_ws_bytes", "qd_wq_h16_config",
-           "qd_attn_h16", "qd_layernorm_h16", "qd_geglu_h16", "qd_groupnorm_h16"]
+           "qd_attn_h16", "qd_layernorm_h16", "qd_geglu_h16", "qd_groupnorm_h16", "qd_groupnorm_mod_h16", "qd_groupnorm_resample_h16"]
 
 _lib = None
 
@@ -140,6 +140,8 @@ def load():
     lib.qd_layernorm_h16.argtypes = [vp, i32, i64, i32, i64, f32, vp, vp, vp, i32, i64, vp]
     lib.qd_geglu_h16.argtypes = [vp, i32, i64, i32, i64, vp, i32, i64, vp]
     lib.qd_groupnorm_h16.argtypes = [vp, i32, i64, i64, i32, i64, i32, f32, vp, vp, i32, vp, i32, i64, vp, vp]
+    lib.qd_groupnorm_mod_h16.argtypes = [vp, i32, i64, i64, i32, i64, i32, f32, vp, vp, vp, i64, i32, vp, i32, i64, vp, vp]
+    lib.qd_groupnorm_resample_h16.argtypes = [vp, i32, i64, i32, i32, i32, i64, i32, f32, vp, vp, i32, i32, vp, i32, i64, vp, vp]
     lib.qd_box_probe.argtypes = [i32, i32, i32, vp, vp, vp]
     lib.qd_attn_ws_bytes.argtypes = [i32, i32, i32, i32]
     lib.qd_attn_ws_bytes.restype = ctypes.c_int64
@@ -490,6 +492,35 @@ def groupnorm_h16(x, B, S, C, ldx, groups, eps, gamma, beta, silu, out, ldo, ws)
     _check(load().qd_groupnorm_h16(_ptr(x, "x"), _H16[x.dtype], B, S, C, ldx, groups, float(eps), _ptr(gamma), _ptr(beta),
                                    1 if silu else 0, _ptr(out, "out"), _H16[out.dtype], ldo, _ptr(ws, "ws"), _stream()),
            "qd_groupnorm_h16")
+
+
+def groupnorm_mod_h16(x, B, S, C, ldx, groups, eps, gamma, beta, mod, mod_ld, silu, out, ldo, ws):
+    """groupnorm_h16 with the modulation of a use_scale_shift_norm block: GroupNorm(x) * (1 + scale) + shift (+ SiLU), mod the
+    fp32 rows [B][mod_ld >= 2C] scale | shift (qd_groupnorm_mod_h16)."""
+    _h16_rows_check("groupnorm_mod_h16", x, ldx, C, out, ldo, C)
+    if C % 8 or C % groups:
+        raise HipEngineError(f"groupnorm_mod_h16: C={C} must be a multiple of 8 and of groups={groups}")
+    if mod is None or mod.dtype != torch.float32 or mod_ld < 2 * C:
+        raise HipEngineError(f"groupnorm_mod_h16: modulation rows must be fp32 scale | shift with mod_ld >= 2 C (mod_ld {mod_ld}, C {C})")
+    _check(load().qd_groupnorm_mod_h16(_ptr(x, "x"), _H16[x.dtype], B, S, C, ldx, groups, float(eps), _ptr(gamma), _ptr(beta),
+                                       _ptr(mod, "mod"), mod_ld, 1 if silu else 0, _ptr(out, "out"), _H16[out.dtype], ldo,
+                                       _ptr(ws, "ws"), _stream()), "qd_groupnorm_mod_h16")
+
+
+def groupnorm_resample_h16(x, B, H, W, C, ldx, groups, eps, gamma, beta, silu, resample, out, ldo, ws):
+    """fp32 / fp16 channels-last rows [B*H*W][ldx] -> GroupNorm (+ SiLU) -> resampled -> fp16 / bf16 operand rows, pad channels
+    zero (qd_groupnorm_resample_h16).  resample 1: the 2x2 average, rows [B*H/2*W/2][ldo] (even H, W); 2: nearest 2x, rows
+    [B*2H*2W][ldo].  ws: groupnorm_ws_bytes(B, C, H * W) bytes."""
+    _h16_rows_check("groupnorm_resample_h16", x, ldx, C, out, ldo, C)
+    if C % 8 or C % groups:
+        raise HipEngineError(f"groupnorm_resample_h16: C={C} must be a multiple of 8 and of groups={groups}")
+    if resample not in (1, 2):
+        raise HipEngineError(f"groupnorm_resample_h16: resample={resample} must be 1 (2x2 average) or 2 (nearest 2x)")
+    if resample == 1 and (H % 2 or W % 2):
+        raise HipEngineError(f"groupnorm_resample_h16: the 2x2 average needs even H, W (got {H} x {W})")
+    _check(load().qd_groupnorm_resample_h16(_ptr(x, "x"), _H16[x.dtype], B, H, W, C, ldx, groups, float(eps), _ptr(gamma), _ptr(beta),
+                                            1 if silu else 0, resample, _ptr(out, "out"), _H16[out.dtype], ldo, _ptr(ws, "ws"),
+                                            _stream()), "qd_groupnorm_resample_h16")
 
 
 def groupnorm_silu_bf16(x, B, S, C, groups, eps, gamma, beta, silu, out, ws, part=None):

@@ -158,6 +158,15 @@ def _wonly_fuse_gate(block, layers, tensors):
             and _no_hooks(*list(block.modules())[1:]))
 
 
+def _out_features(m):
+    """Output features of a Linear / QuantModule (its weights-only plan when the fp32 weight was released), or None."""
+    plan = m.wonly_plan() if isinstance(m, QuantModule) else None
+    if plan is not None:
+        return plan.Cout
+    w = getattr(m, "weight", None)
+    return w.shape[0] if torch.is_tensor(w) and w.dim() >= 2 and w.numel() else None
+
+
 def _wonly_wide_edges(block, x, first, last, C, Cmid):
     """engine.WEIGHT_ONLY_FUSE_WIDE takes the edges of a SpatialTransformer / QuantAttentionBlock: the gate of the fused route
     (_wonly_fuse_gate on the two projections: knobs, fp32 GPU input, unsplit, wonly_ready, no hook below the block), an
@@ -685,6 +694,8 @@ class QuantResBlock(BaseQuantBlock, ldm_unet.TimestepBlock):
             return self._forward_int(x, emb, split, conv1, conv2, out_slot)
         if self._wonly_fusable(x, emb, conv1, conv2):
             return self._forward_wonly(x, emb, split, conv1, conv2)
+        if self._wonly_mod_fusable(x, emb, conv1, conv2):
+            return self._forward_wonly_mod(x, emb, split, conv1, conv2)
         return self._forward_sim(x, emb, split)
 
     def _wonly_fusable(self, x, emb, conv1, conv2):
@@ -722,6 +733,82 @@ class QuantResBlock(BaseQuantBlock, ldm_unet.TimestepBlock):
             res = _nhwc_rows(self.skip_connection(x, split=split) if split != 0 else self.skip_connection(x))
         out = conv2.forward_rows(hh, B, H, W, residual=res)
         engine.WONLY_FUSED["resblock"] += 1
+        return _rows_to_nchw(out, B, H, W)
+
+    def _wonly_resample(self):
+        """0: no `updown`; 1: h_upd / x_upd are the 2x2 average (Downsample without convolution); 2: nearest 2x (Upsample
+        without convolution); None: an `updown` block of any other make."""
+        if not self.updown:
+            return 0
+        hu, xu = self.h_upd, self.x_upd
+        if type(hu) is not type(xu) or getattr(hu, "use_conv", True) or getattr(xu, "use_conv", True) or getattr(hu, "dims", 2) != 2:
+            return None
+        ops = [getattr(m, "op", None) for m in (hu, xu)]
+        if all(op is None for op in ops):
+            return 2 if type(hu).__name__ == "Upsample" and not hasattr(hu, "conv") else None
+        pool = lambda op: isinstance(op, nn.AvgPool2d) and op.kernel_size in (2, (2, 2)) and op.stride in (2, (2, 2)) \
+            and op.padding in (0, (0, 0)) and not op.ceil_mode and op.divisor_override is None
+        return 1 if all(pool(op) for op in ops) else None
+
+    def _wonly_mod_fusable(self, x, emb, conv1, conv2):
+        """engine.WEIGHT_ONLY_FUSE_MOD takes this call: asked only after _wonly_fusable refused.  A block with
+        `use_scale_shift_norm`, `updown` or both, with the reference's layer lists (norm, SiLU, conv / norm, SiLU, dropout, conv;
+        an `updown` block applies in_layers[:-1], h_upd / x_upd, in_layers[-1]), h_upd / x_upd the 2x2 average (even H, W) or
+        nearest 2x, everything _wonly_fuse_gate demands, both convolutions reading all their C % 8 == 0 channels as one segment
+        at the resampled size, and for scale-shift an embedding projection of 2 Cout features."""
+        if not engine.WEIGHT_ONLY_FUSE_MOD or not engine.WEIGHT_ONLY_FUSE or not (self.updown or self.use_scale_shift_norm) or x.dim() != 4:
+            return False
+        if not (len(self.in_layers) == 3 and len(self.out_layers) == 4 and isinstance(self.in_layers[0], nn.GroupNorm)
+                and isinstance(self.out_layers[0], nn.GroupNorm) and isinstance(self.in_layers[1], nn.SiLU)
+                and isinstance(self.out_layers[1], nn.SiLU) and isinstance(self.out_layers[2], nn.Dropout)):
+            return False
+        mode = self._wonly_resample()
+        H, W = x.shape[2], x.shape[3]
+        if mode is None or (mode == 1 and (H % 2 or W % 2)) or x.shape[1] % 8 or self.out_channels % 8:
+            return False
+        if not _wonly_fuse_gate(self, (conv1, conv2), (x, emb)):
+            return False
+        Hr, Wr = (H // 2, W // 2) if mode == 1 else (2 * H, 2 * W) if mode == 2 else (H, W)
+        if self.use_scale_shift_norm and _out_features(self.emb_layers[-1]) != 2 * self.out_channels:
+            return False
+        return (conv1.kind == 'conv2d' and conv2.kind == 'conv2d' and engine.wonly_plain_plan(conv1.wonly_plan(), x.shape[1])
+                and engine.wonly_plain_plan(conv2.wonly_plan(), self.out_channels) and conv2.wonly_plan().Cout == self.out_channels
+                and conv1.wonly_plan().Cout == self.out_channels
+                and engine.conv_out_hw(Hr, Wr, conv1.wonly_plan()) == (Hr, Wr)
+                and engine.conv_out_hw(Hr, Wr, conv2.wonly_plan()) == (Hr, Wr))
+
+    def _forward_wonly_mod(self, x, emb, split, conv1, conv2):
+        """Reference :83-111 in the weights-only state for `updown` / `use_scale_shift_norm` blocks: GN.SiLU (and h_upd, before
+        the one rounding: qd_groupnorm_resample_h16) -> operand rows of conv1; conv1 with the embedding projection as a row bias
+        unless the block is scale-shift; GN * (1 + scale) + shift . SiLU (qd_groupnorm_mod_h16, the projection as `mod`) ->
+        operand rows of conv2; conv2 with the skip rows as the residual.  x_upd on the fp32 skip tensor stays in torch."""
+        B, C, H, W = x.shape
+        mode = self._wonly_resample()
+        rows = _nhwc_rows(x)
+        if mode:
+            xh = engine.wonly_groupnorm_resample_rows(rows, B, H, W, C, self.in_layers[0], True, mode, conv1.wonly_plan())
+            H, W = (H // 2, W // 2) if mode == 1 else (2 * H, 2 * W)
+        else:
+            xh = engine.wonly_groupnorm_rows(rows, B, H * W, C, self.in_layers[0], True, conv1.wonly_plan())
+        S = H * W
+        e = self.emb_layers(emb).float()
+        if e.stride(1) != 1:
+            e = e.contiguous()
+        if self.use_scale_shift_norm:
+            h = conv1.forward_rows(xh, B, H, W)
+            hh = engine.wonly_groupnorm_mod_rows(h, B, S, self.out_channels, self.out_layers[0], e, True, conv2.wonly_plan())
+        else:
+            h = conv1.forward_rows(xh, B, H, W, rowbias=e)
+            hh = engine.wonly_groupnorm_rows(h, B, S, self.out_channels, self.out_layers[0], True, conv2.wonly_plan())
+        if mode:
+            x = self.x_upd(x)
+            rows = _nhwc_rows(x)
+        if isinstance(self.skip_connection, nn.Identity):
+            res = rows
+        else:
+            res = _nhwc_rows(self.skip_connection(x, split=split) if split != 0 else self.skip_connection(x))
+        out = conv2.forward_rows(hh, B, H, W, residual=res)
+        engine.wonly_count("resblock_mod")
         return _rows_to_nchw(out, B, H, W)
 
     def _forward_sim(self, x, emb, split=0):

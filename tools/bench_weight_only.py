@@ -30,6 +30,14 @@ at batch 16 alone (HIP events, median and min..max of 3 repeats of 20 launches):
 (hip.wq_h16_config, finalise included) and against the library's policy.
 
     python tools/bench_weight_only.py --splitk [--models sd,ldm,cifar] [--rounds 3] [--splitk-shapes]
+
+--mod: layer kernel at fp16 and fusion on (with --attn the attention kernel, with --wide the wide fusion too), and
+engine.WEIGHT_ONLY_FUSE_MOD off / on alternated --rounds times in one process: best, all values and spread of each side, the
+blocks on the route, the distance of the outputs, peak memory, a box probe.  --mod-shapes: the three new launch forms alone at
+LSUN-Churches' shapes at batch 16 (scale-shift norm; norm + 2x2 average; norm + nearest 2x) next to today's passes over the same
+tensors and a device copy of the same bytes.
+
+    python tools/bench_weight_only.py --attn --fuse --wide --mod --models churches [--rounds 3] [--mod-shapes]
 """
 import argparse
 import json
@@ -344,6 +352,118 @@ def run_splitk(kind, batch, k, dev, rounds):
     return res
 
 
+def run_mod(kind, batch, k, dev, attn, wide, rounds):
+    """Layer knob fp16, block fusion on; engine.WEIGHT_ONLY_FUSE_MOD off / on alternated `rounds` times in one process."""
+    import bench
+    from qdiff import engine, hip, synthetic
+    qnn, _ = bench.build_quantised_unet(kind, dev)
+    x, t, c = synthetic.synthetic_inputs(kind, batch, seed=0)
+    args = [a.to(dev) for a in (x, t, c) if a is not None]
+    qnn.set_quant_state(True, False)
+    one = lambda: qnn(*args)
+    res = {"model": kind, "batch": batch, "layer_knob": "fp16", "attn_knob": "fp16" if attn else "off", "fuse": True, "wide": bool(wide),
+           "evals_timed": k, "rounds": rounds}
+    prev = (engine.WEIGHT_ONLY_KERNEL, engine.WEIGHT_ONLY_ATTN, engine.WEIGHT_ONLY_FUSE, engine.WEIGHT_ONLY_FUSE_WIDE, engine.WEIGHT_ONLY_FUSE_MOD)
+    try:
+        engine.set_weight_only_kernel(torch.float16)
+        engine.set_weight_only_attention(torch.float16 if attn else None)
+        engine.set_weight_only_fusion(True)
+        engine.set_weight_only_fusion_wide(bool(wide))
+        res["box_probe_mfma_ms"] = round(hip.box_probe(dev, 0, 512, 60000)[0], 3)
+        off, on = [], []
+        for _ in range(rounds):                                  # alternated A/B
+            engine.set_weight_only_fusion_mod(False)
+            off.append(_timed(one, k))
+            engine.set_weight_only_fusion_mod(True)
+            on.append(_timed(one, k))
+        res["box_probe_mfma_ms_after"] = round(hip.box_probe(dev, 0, 512, 60000)[0], 3)
+        res["mod_off_ms"], res["mod_on_ms"] = round(min(off), 3), round(min(on), 3)
+        res["mod_off_ms_all"], res["mod_on_ms_all"] = [round(v, 3) for v in off], [round(v, 3) for v in on]
+        res["mod_off_spread_ms"], res["mod_on_spread_ms"] = round(max(off) - min(off), 3), round(max(on) - min(on), 3)
+        res["faster_by_more_than_spread"] = bool(min(off) - max(on) > 0 and min(off) - min(on) > max(max(off) - min(off), max(on) - min(on)))
+        outs = {}
+        for name, flag in (("off", False), ("on", True)):
+            engine.set_weight_only_fusion_mod(flag)
+            for key in ("resblock_mod", "spatial", "attnblock"):
+                engine.WONLY_FUSED.pop(key, None)
+            for k2 in engine.WONLY_FUSED:
+                engine.WONLY_FUSED[k2] = 0
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats(dev)
+            with torch.no_grad():
+                outs[name] = one()
+            torch.cuda.synchronize()
+            res[f"mod_{name}_max_mem_mib"] = round(torch.cuda.max_memory_allocated(dev) / 2 ** 20, 1)
+            res[f"mod_{name}_blocks"] = dict(engine.WONLY_FUSED)
+        res["mod_on_vs_off_of_range"] = float((outs["on"] - outs["off"]).abs().max() / outs["off"].abs().max())
+    finally:
+        engine.set_weight_only_kernel(prev[0])
+        engine.set_weight_only_attention(prev[1])
+        engine.set_weight_only_fusion(prev[2])
+        engine.set_weight_only_fusion_wide(prev[3])
+        engine.set_weight_only_fusion_mod(prev[4])
+        for key in ("resblock_mod", "spatial", "attnblock"):
+            engine.WONLY_FUSED.pop(key, None)
+    return res
+
+
+# LSUN-Churches LDM-8 at batch 16: (H = W, channels) of the maps its residual blocks normalise
+CHURCHES_GN_SHAPES = [(32, 192), (32, 384), (16, 384), (16, 768), (8, 384), (8, 768), (4, 768), (4, 1536), (2, 768), (2, 1536)]
+
+
+def mod_shape_table(dev, B=16):
+    """The three launch forms alone against today's passes over the same tensors (library GroupNorm, SiLU, modulation / resampling
+    in fp32 NCHW-logical tensors, then qd_rows_to_h16) and a device copy of the bytes the new form moves."""
+    import torch.nn.functional as F
+    from types import SimpleNamespace as NS
+    from qdiff import engine, hip
+    g = torch.Generator(device=dev).manual_seed(0)
+
+    def med(fn):
+        v = sorted(1000 * _events_ms(fn, 20) for _ in range(3))
+        return [round(v[1], 1), round(v[0], 1), round(v[2], 1)]       # median, min, max
+
+    def copy_us(nbytes):
+        src = torch.empty(max(nbytes // 2, 16), dtype=torch.uint8, device=dev)
+        dst = torch.empty_like(src)
+        return med(lambda: dst.copy_(src))[0]
+
+    for hw, C in CHURCHES_GN_SHAPES:
+        S = hw * hw
+        x = torch.randn(B * S, C, device=dev, generator=g)
+        xn = x.view(B, hw, hw, C).permute(0, 3, 1, 2)                  # the channels-last NCHW tensor today's path sees
+        gn = torch.nn.GroupNorm(32, C).to(dev)
+        mod = torch.randn(B, 2 * C, device=dev, generator=g)
+        plan = NS(ldx=C, act_dtype=torch.float16, pack=NS(segs=[dict(c0w=0, clen=C, clen_pad=C)]), segs=[dict(c0=0)])
+        ws = torch.empty(hip.groupnorm_ws_bytes(B, C, S), dtype=torch.uint8, device=dev)
+
+        def today(kind):
+            h = F.silu(gn(xn)) if kind != "mod" else gn(xn)
+            if kind == "mod":
+                h = F.silu(h * (1 + mod[:, :C, None, None]) + mod[:, C:, None, None])
+            elif kind == "down":
+                h = F.avg_pool2d(h, 2)
+            elif kind == "up":
+                h = F.interpolate(h, scale_factor=2, mode="nearest")
+            sb, sc, sh, sw = h.stride()
+            if sh != h.shape[3] * sw:
+                h = h.contiguous(memory_format=torch.channels_last)
+                sb, sc, sh, sw = h.stride()
+            return engine.wonly_rows(h, plan, h.shape[0], C, h.shape[2] * h.shape[3], (sb, sc, sw))
+
+        forms = [("mod", lambda: engine.wonly_groupnorm_mod_rows(x, B, S, C, gn, mod, True, plan), B * S * C * 10),
+                 ("up", lambda: engine.wonly_groupnorm_resample_rows(x, B, hw, hw, C, gn, True, 2, plan), B * S * C * 16)]
+        if hw % 2 == 0:
+            forms.append(("down", lambda: engine.wonly_groupnorm_resample_rows(x, B, hw, hw, C, gn, True, 1, plan), B * S * C * 8 + B * S * C // 2))
+        with torch.no_grad():
+            for kind, fn, nbytes in forms:
+                new, old = med(fn), med(lambda: today(kind))
+                print(json.dumps({"op": "groupnorm_" + kind + "_h16", "shape": [B, hw, hw, C], "us_med_min_max": new, "today_us_med_min_max": old,
+                                  "speedup": round(old[0] / new[0], 2), "gbs": round(nbytes / new[0] / 1e3, 1),
+                                  "device_copy_same_bytes_us": copy_us(nbytes)}), flush=True)
+        del x, ws
+
+
 # Under-filled contractions at batch 16: (name, H = W, kernel, input segments, Cout); M = 16 * H * W unless given
 SPLITK_SHAPES = [
     ("sd 8x8 3x3 1280->1280", 8, 3, [1280], 1280), ("sd 8x8 3x3 2560->1280 shortcut", 8, 3, [1280, 1280], 1280),
@@ -527,6 +647,8 @@ def main():
                                                         "GEGLU projection alone at SD's three shapes")
     ap.add_argument("--splitk", action="store_true", help="the split-K column: every other weights-only knob on, split-K off / on alternated")
     ap.add_argument("--splitk-shapes", action="store_true", help="the under-filled contraction shapes alone: unsplit against forced slice counts")
+    ap.add_argument("--mod", action="store_true", help="the column of the scale-shift / resampling residual blocks: fusion on, FUSE_MOD off / on alternated")
+    ap.add_argument("--mod-shapes", action="store_true", help="the three launch forms of --mod alone at LSUN-Churches' shapes")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     from qdiff import hip
@@ -536,12 +658,16 @@ def main():
         attn_shape_table(dev, SD_SHAPES + LDM_SHAPES)
     if a.fuse_shapes:
         fuse_shape_table(dev)
-    if a.wide:
+    if a.wide and not a.mod:
         wide_shape_table(dev)
+    if a.mod_shapes:
+        mod_shape_table(dev)
     if a.splitk_shapes:
         splitk_shape_table(dev)
     for kind in [m for m in a.models.split(",") if m]:           # --models "" = the shape tables alone
-        if a.splitk:
+        if a.mod:
+            res = run_mod(kind, a.batch, a.evals, dev, a.attn, a.wide, a.rounds)
+        elif a.splitk:
             res = run_splitk(kind, a.batch, a.evals, dev, a.rounds)
         elif a.wide:
             res = run_wide(kind, a.batch, a.evals, dev, a.attn, a.rounds)
