@@ -1076,6 +1076,27 @@ inline int gn_h16_args(const char* who, const void* x, int x_dtype, int64_t B, i
     return 0;
 }
 
+// One 256-thread grid-stride launch over `total` threads of the instance for the input type: kf reads fp32 rows, kh fp16 rows.
+// Both take (x, total, rest...).
+template <typename KF, typename KH, typename... A>
+inline void h16_launch(KF kf, KH kh, int x_dtype, const void* x, long total, hipStream_t st, A... rest) {
+    if (x_dtype == QD_F32) hipLaunchKernelGGL(kf, dim3(h16_stream_grid(total)), dim3(256), 0, st, (const float*)x, total, rest...);
+    else hipLaunchKernelGGL(kh, dim3(h16_stream_grid(total)), dim3(256), 0, st, (const __half*)x, total, rest...);
+}
+
+// qd_groupnorm_h16 (mod == nullptr) and qd_groupnorm_mod_h16 behind their argument checks: the statistics, the modulation folded
+// into the per-(sample, channel) affine (gn_stats' mod), then the one apply pass.
+int groupnorm_h16_run(const char* who, const void* x, int x_dtype, int64_t B, int64_t S, int C, int64_t ldx, int groups, float eps,
+                      const float* gamma, const float* beta, const float* mod, int64_t mod_ld, int apply_silu, void* out, int out_dtype,
+                      int64_t ldo, void* ws, void* stream) {
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const float* ab = gn_stats(x, x_dtype, B, S, C, ldx, groups, eps, gamma, beta, ws, nullptr, 0, 0, true, mod, mod_ld, st);
+    h16_launch(gn_apply_h16_kernel<float, true>, gn_apply_h16_kernel<__half, true>, x_dtype, x, (long)B * S * (ldo / 8), st, (long)S, C,
+               (long)ldx, ab, apply_silu, reinterpret_cast<unsigned short*>(out), (long)ldo, out_dtype == QD_F16 ? 1 : 0);
+    QD_LAUNCH_CHECK(who);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int qd_layernorm_h16(const void* x, int x_dtype, int64_t M, int C, int64_t ldx, float eps, const float* gamma,
@@ -1117,25 +1138,9 @@ extern "C" int qd_geglu_h16(const void* h, int h_dtype, int64_t M, int F, int64_
 extern "C" int qd_groupnorm_h16(const void* x, int x_dtype, int64_t B, int64_t S, int C, int64_t ldx, int groups, float eps,
                                 const float* gamma, const float* beta, int apply_silu, void* out, int out_dtype, int64_t ldo,
                                 void* ws, void* stream) {
-    QD_REQUIRE(x && out && ws, "qd_groupnorm_h16: null pointer");
-    QD_REQUIRE(x_dtype == QD_F32 || x_dtype == QD_F16, "qd_groupnorm_h16: x_dtype must be f32/f16");
-    QD_REQUIRE(out_dtype == QD_F16 || out_dtype == QD_BF16, "qd_groupnorm_h16: out_dtype must be f16/bf16");
-    QD_REQUIRE(B > 0 && B < 65536 && S > 0 && C > 0 && groups > 0 && C % groups == 0 && C % 8 == 0,
-               "qd_groupnorm_h16: C=%d must be a multiple of 8 and of groups=%d", C, groups);
-    QD_REQUIRE(ldx >= C && ldx % (x_dtype == QD_F32 ? 4 : 8) == 0 && qd_aligned(x, 16), "qd_groupnorm_h16: input rows must be 16-byte aligned");
-    QD_REQUIRE(ldo >= C && ldo % 8 == 0 && qd_aligned(out, 16), "qd_groupnorm_h16: output rows must be 16-byte aligned (ldo %% 8 == 0)");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const float* ab = gn_stats(x, x_dtype, B, S, C, ldx, groups, eps, gamma, beta, ws, nullptr, 0, 0, true, nullptr, 0, st);
-    const long total = (long)B * S * (ldo / 8);
-    const int fh = out_dtype == QD_F16 ? 1 : 0;
-    if (x_dtype == QD_F32)
-        hipLaunchKernelGGL((gn_apply_h16_kernel<float, true>), dim3(h16_stream_grid(total)), dim3(256), 0, st, (const float*)x, total, (long)S, C, (long)ldx, ab, apply_silu,
-                           reinterpret_cast<unsigned short*>(out), (long)ldo, fh);
-    else
-        hipLaunchKernelGGL((gn_apply_h16_kernel<__half, true>), dim3(h16_stream_grid(total)), dim3(256), 0, st, (const __half*)x, total, (long)S, C, (long)ldx, ab, apply_silu,
-                           reinterpret_cast<unsigned short*>(out), (long)ldo, fh);
-    QD_LAUNCH_CHECK("qd_groupnorm_h16");
-    return 0;
+    if (int rc = gn_h16_args("qd_groupnorm_h16", x, x_dtype, B, S, C, ldx, groups, out, out_dtype, ldo, ws)) return rc;
+    return groupnorm_h16_run("qd_groupnorm_h16", x, x_dtype, B, S, C, ldx, groups, eps, gamma, beta, nullptr, 0, apply_silu, out, out_dtype,
+                             ldo, ws, stream);
 }
 
 // `out_norm(h) * (1 + scale) + shift` (+ SiLU) of a use_scale_shift_norm residual block (reference quant_block.py:99-103) as
@@ -1147,18 +1152,8 @@ extern "C" int qd_groupnorm_mod_h16(const void* x, int x_dtype, int64_t B, int64
     if (int rc = gn_h16_args("qd_groupnorm_mod_h16", x, x_dtype, B, S, C, ldx, groups, out, out_dtype, ldo, ws)) return rc;
     QD_REQUIRE(mod, "qd_groupnorm_mod_h16: null modulation rows");
     QD_REQUIRE(mod_ld >= 2 * (int64_t)C, "qd_groupnorm_mod_h16: modulation rows hold scale | shift: mod_ld >= 2 C");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const float* ab = gn_stats(x, x_dtype, B, S, C, ldx, groups, eps, gamma, beta, ws, nullptr, 0, 0, true, mod, mod_ld, st);
-    const long total = (long)B * S * (ldo / 8);
-    const int fh = out_dtype == QD_F16 ? 1 : 0;
-    if (x_dtype == QD_F32)
-        hipLaunchKernelGGL((gn_apply_h16_kernel<float, true>), dim3(h16_stream_grid(total)), dim3(256), 0, st, (const float*)x, total, (long)S, C, (long)ldx, ab, apply_silu,
-                           reinterpret_cast<unsigned short*>(out), (long)ldo, fh);
-    else
-        hipLaunchKernelGGL((gn_apply_h16_kernel<__half, true>), dim3(h16_stream_grid(total)), dim3(256), 0, st, (const __half*)x, total, (long)S, C, (long)ldx, ab, apply_silu,
-                           reinterpret_cast<unsigned short*>(out), (long)ldo, fh);
-    QD_LAUNCH_CHECK("qd_groupnorm_mod_h16");
-    return 0;
+    return groupnorm_h16_run("qd_groupnorm_mod_h16", x, x_dtype, B, S, C, ldx, groups, eps, gamma, beta, mod, mod_ld, apply_silu, out,
+                             out_dtype, ldo, ws, stream);
 }
 
 // GroupNorm (+ SiLU) of a [B][H][W][C] map, resampled before the one rounding: the `in_layers` norm . SiLU and h_upd of an
@@ -1178,15 +1173,10 @@ extern "C" int qd_groupnorm_resample_h16(const void* x, int x_dtype, int64_t B, 
     const long total = (resample == 1 ? (long)B * (H / 2) * (W / 2) : (long)B * S) * (ldo / 8);     // threads: output / input pixels
     const int fh = out_dtype == QD_F16 ? 1 : 0;
     unsigned short* o = reinterpret_cast<unsigned short*>(out);
-    const dim3 grid(h16_stream_grid(total));
-    if (x_dtype == QD_F32 && resample == 1)
-        hipLaunchKernelGGL((gn_apply_resample_h16_kernel<float, 1>), grid, dim3(256), 0, st, (const float*)x, total, H, W, C, (long)ldx, ab, apply_silu, o, (long)ldo, fh);
-    else if (x_dtype == QD_F32)
-        hipLaunchKernelGGL((gn_apply_resample_h16_kernel<float, 2>), grid, dim3(256), 0, st, (const float*)x, total, H, W, C, (long)ldx, ab, apply_silu, o, (long)ldo, fh);
-    else if (resample == 1)
-        hipLaunchKernelGGL((gn_apply_resample_h16_kernel<__half, 1>), grid, dim3(256), 0, st, (const __half*)x, total, H, W, C, (long)ldx, ab, apply_silu, o, (long)ldo, fh);
+    if (resample == 1)
+        h16_launch(gn_apply_resample_h16_kernel<float, 1>, gn_apply_resample_h16_kernel<__half, 1>, x_dtype, x, total, st, H, W, C, (long)ldx, ab, apply_silu, o, (long)ldo, fh);
     else
-        hipLaunchKernelGGL((gn_apply_resample_h16_kernel<__half, 2>), grid, dim3(256), 0, st, (const __half*)x, total, H, W, C, (long)ldx, ab, apply_silu, o, (long)ldo, fh);
+        h16_launch(gn_apply_resample_h16_kernel<float, 2>, gn_apply_resample_h16_kernel<__half, 2>, x_dtype, x, total, st, H, W, C, (long)ldx, ab, apply_silu, o, (long)ldo, fh);
     QD_LAUNCH_CHECK("qd_groupnorm_resample_h16");
     return 0;
 }

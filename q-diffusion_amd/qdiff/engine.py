@@ -480,14 +480,18 @@ def _parse_weight_only(v):
 WEIGHT_ONLY_KERNEL = _parse_weight_only(os.environ.get("QDIFF_WEIGHT_ONLY"))
 
 
+def _set_dtype(name, dtype, parse, what):
+    """Assign the module's operand-type knob `name`: None, torch.float16 or torch.bfloat16, or a string `parse` accepts."""
+    if isinstance(dtype, str):
+        dtype = parse(dtype)
+    if dtype not in (None, torch.float16, torch.bfloat16):
+        raise ValueError(f"{what} dtype must be None, torch.float16 or torch.bfloat16")
+    globals()[name] = dtype
+
+
 def set_weight_only_kernel(dtype):
     """None, torch.float16 or torch.bfloat16 (or the strings QDIFF_WEIGHT_ONLY accepts)."""
-    global WEIGHT_ONLY_KERNEL
-    if isinstance(dtype, str):
-        dtype = _parse_weight_only(dtype)
-    if dtype not in (None, torch.float16, torch.bfloat16):
-        raise ValueError("weight-only kernel dtype must be None, torch.float16 or torch.bfloat16")
-    WEIGHT_ONLY_KERNEL = dtype
+    _set_dtype("WEIGHT_ONLY_KERNEL", dtype, _parse_weight_only, "weight-only kernel")
 
 
 def _parse_flag(v, name):
@@ -497,6 +501,15 @@ def _parse_flag(v, name):
     if v in ("1", "on", "true", "yes"):
         return True
     raise ValueError(f"{name}={v!r}: expected 1 or 0")
+
+
+def _set_flag(name, on, what):
+    """Assign the module's on / off knob `name`: True / False, or a string its environment variable QDIFF_<name> accepts."""
+    if isinstance(on, str):
+        on = _parse_flag(on, "QDIFF_" + name)
+    if not isinstance(on, bool):
+        raise ValueError(f"{what} must be True or False")
+    globals()[name] = on
 
 
 # Weights-only split-K (DESIGN.md §4.16): False (default) = every qd_conv2d_wq_h16 launch is the one launch it always was; True =
@@ -511,12 +524,7 @@ WONLY_SPLITK = [0]
 
 def set_weight_only_splitk(on):
     """True / False (or the strings QDIFF_WEIGHT_ONLY_SPLITK accepts)."""
-    global WEIGHT_ONLY_SPLITK
-    if isinstance(on, str):
-        on = _parse_flag(on, "QDIFF_WEIGHT_ONLY_SPLITK")
-    if not isinstance(on, bool):
-        raise ValueError("weight-only split-K must be True or False")
-    WEIGHT_ONLY_SPLITK = on
+    _set_flag("WEIGHT_ONLY_SPLITK", on, "weight-only split-K")
 
 
 def wonly_device_ok(t):
@@ -661,12 +669,7 @@ WONLY_GEGLU_EPI = [0]
 
 def set_weight_only_fusion_wide(on):
     """True / False (or the strings QDIFF_WEIGHT_ONLY_FUSE_WIDE accepts)."""
-    global WEIGHT_ONLY_FUSE_WIDE
-    if isinstance(on, str):
-        on = _parse_flag(on, "QDIFF_WEIGHT_ONLY_FUSE_WIDE")
-    if not isinstance(on, bool):
-        raise ValueError("wide weight-only fusion must be True or False")
-    WEIGHT_ONLY_FUSE_WIDE = on
+    _set_flag("WEIGHT_ONLY_FUSE_WIDE", on, "wide weight-only fusion")
 
 
 def wonly_wide_state():
@@ -676,7 +679,7 @@ def wonly_wide_state():
 
 # Modulated / resampling residual blocks, on top of WEIGHT_ONLY_FUSE (effective only while wonly_fuse_state() holds; DESIGN.md
 # §4.17): False (default) = a weights-only QuantResBlock with `use_scale_shift_norm` or `updown` keeps the reference's
-# composition; True = it runs QuantResBlock._forward_wonly_mod on qd_groupnorm_resample_h16 / qd_groupnorm_mod_h16.
+# composition; True = it runs QuantResBlock._forward_wonly on qd_groupnorm_resample_h16 / qd_groupnorm_mod_h16.
 # WONLY_FUSED gets the key "resblock_mod" when a block takes the route, never while the knob is off.
 # QDIFF_WEIGHT_ONLY_FUSE_MOD=1, or engine.set_weight_only_fusion_mod().
 WEIGHT_ONLY_FUSE_MOD = _parse_flag(os.environ.get("QDIFF_WEIGHT_ONLY_FUSE_MOD"), "QDIFF_WEIGHT_ONLY_FUSE_MOD")
@@ -684,12 +687,7 @@ WEIGHT_ONLY_FUSE_MOD = _parse_flag(os.environ.get("QDIFF_WEIGHT_ONLY_FUSE_MOD"),
 
 def set_weight_only_fusion_mod(on):
     """True / False (or the strings QDIFF_WEIGHT_ONLY_FUSE_MOD accepts)."""
-    global WEIGHT_ONLY_FUSE_MOD
-    if isinstance(on, str):
-        on = _parse_flag(on, "QDIFF_WEIGHT_ONLY_FUSE_MOD")
-    if not isinstance(on, bool):
-        raise ValueError("weight-only fusion of modulated / resampling blocks must be True or False")
-    WEIGHT_ONLY_FUSE_MOD = on
+    _set_flag("WEIGHT_ONLY_FUSE_MOD", on, "weight-only fusion of modulated / resampling blocks")
 
 
 def wonly_mod_state():
@@ -704,12 +702,7 @@ def wonly_count(kind):
 
 def set_weight_only_fusion(on):
     """True / False (or the strings QDIFF_WEIGHT_ONLY_FUSE accepts)."""
-    global WEIGHT_ONLY_FUSE
-    if isinstance(on, str):
-        on = _parse_flag(on, "QDIFF_WEIGHT_ONLY_FUSE")
-    if not isinstance(on, bool):
-        raise ValueError("weight-only fusion must be True or False")
-    WEIGHT_ONLY_FUSE = on
+    _set_flag("WEIGHT_ONLY_FUSE", on, "weight-only fusion")
 
 
 def _autocast_on():
@@ -742,11 +735,17 @@ def _h16_input_rows(rows):
     return rows
 
 
+def _producer_rows(x_rows, M, plan, gn=None):
+    """What every producer below starts from: (the input rows readable with 16-byte loads, empty operand rows [M][plan.ldx] of
+    `plan`, the GroupNorm workspace for gn = (B, C, S) or None)."""
+    x_rows = _h16_input_rows(x_rows)
+    out = torch.empty((M, plan.ldx), dtype=plan.act_dtype, device=x_rows.device)
+    return x_rows, out, (_workspace(hip.groupnorm_ws_bytes(*gn), x_rows.device) if gn else None)
+
+
 def wonly_groupnorm_rows(x_rows, B, S, C, gn, silu, plan):
     """GroupNorm (+ SiLU) of channels-last fp32 rows [B*S][>= C] -> the operand rows [B*S][plan.ldx] of `plan`."""
-    x_rows = _h16_input_rows(x_rows)
-    out = torch.empty((B * S, plan.ldx), dtype=plan.act_dtype, device=x_rows.device)
-    ws = _workspace(hip.groupnorm_ws_bytes(B, C, S), x_rows.device)
+    x_rows, out, ws = _producer_rows(x_rows, B * S, plan, (B, C, S))
     hip.groupnorm_h16(x_rows, B, S, C, x_rows.stride(0), gn.num_groups, gn.eps, gn.weight, gn.bias, silu, out, plan.ldx, ws)
     return out
 
@@ -754,11 +753,9 @@ def wonly_groupnorm_rows(x_rows, B, S, C, gn, silu, plan):
 def wonly_groupnorm_mod_rows(x_rows, B, S, C, gn, mod, silu, plan):
     """GroupNorm * (1 + scale) + shift (+ SiLU) of channels-last fp32 rows [B*S][>= C] -> the operand rows [B*S][plan.ldx] of
     `plan`.  mod: fp32 rows [B][>= 2C] scale | shift with unit column stride (the embedding projection of the block)."""
-    x_rows = _h16_input_rows(x_rows)
     if mod.dtype != torch.float32 or mod.dim() != 2 or mod.shape[0] != B or mod.shape[1] < 2 * C or mod.stride(1) != 1:
         raise hip.HipEngineError("wonly_groupnorm_mod_rows: mod must be fp32 rows [B][>= 2C] with unit column stride")
-    out = torch.empty((B * S, plan.ldx), dtype=plan.act_dtype, device=x_rows.device)
-    ws = _workspace(hip.groupnorm_ws_bytes(B, C, S), x_rows.device)
+    x_rows, out, ws = _producer_rows(x_rows, B * S, plan, (B, C, S))
     hip.groupnorm_mod_h16(x_rows, B, S, C, x_rows.stride(0), gn.num_groups, gn.eps, gn.weight, gn.bias, mod,
                           mod.stride(0) if B > 1 else mod.shape[1], silu, out, plan.ldx, ws)
     return out
@@ -767,10 +764,8 @@ def wonly_groupnorm_mod_rows(x_rows, B, S, C, gn, mod, silu, plan):
 def wonly_groupnorm_resample_rows(x_rows, B, H, W, C, gn, silu, resample, plan):
     """GroupNorm (+ SiLU) of the channels-last fp32 map [B*H*W][>= C], resampled (1: 2x2 average, 2: nearest 2x) -> the operand
     rows of `plan` at the resampled size."""
-    x_rows = _h16_input_rows(x_rows)
     Mo = B * (H // 2) * (W // 2) if resample == 1 else B * 4 * H * W
-    out = torch.empty((Mo, plan.ldx), dtype=plan.act_dtype, device=x_rows.device)
-    ws = _workspace(hip.groupnorm_ws_bytes(B, C, H * W), x_rows.device)
+    x_rows, out, ws = _producer_rows(x_rows, Mo, plan, (B, C, H * W))
     hip.groupnorm_resample_h16(x_rows, B, H, W, C, x_rows.stride(0), gn.num_groups, gn.eps, gn.weight, gn.bias, silu, resample,
                                out, plan.ldx, ws)
     return out
@@ -778,16 +773,14 @@ def wonly_groupnorm_resample_rows(x_rows, B, H, W, C, gn, silu, resample, plan):
 
 def wonly_layernorm_rows(x_rows, M, C, ln, plan):
     """LayerNorm of fp32 rows [M][C] -> ONE buffer of operand rows [M][plan.ldx], shared by every consumer with that layout."""
-    x_rows = _h16_input_rows(x_rows)
-    out = torch.empty((M, plan.ldx), dtype=plan.act_dtype, device=x_rows.device)
+    x_rows, out, _ = _producer_rows(x_rows, M, plan)
     hip.layernorm_h16(x_rows, M, C, x_rows.stride(0), ln.eps, ln.weight, ln.bias, out, plan.ldx)
     return out
 
 
 def wonly_geglu_rows(h_rows, M, F, plan):
     """value * gelu(gate) of rows [M][2F] -> the operand rows [M][plan.ldx] of `plan` (the feed-forward output Linear)."""
-    h_rows = _h16_input_rows(h_rows)
-    out = torch.empty((M, plan.ldx), dtype=plan.act_dtype, device=h_rows.device)
+    h_rows, out, _ = _producer_rows(h_rows, M, plan)
     hip.geglu_h16(h_rows, M, F, h_rows.stride(0), out, plan.ldx)
     return out
 
@@ -817,12 +810,7 @@ WONLY_ATTN_DMIN, WONLY_ATTN_DMAX = 8, 160
 
 def set_weight_only_attention(dtype):
     """None, torch.float16 or torch.bfloat16 (or the strings QDIFF_WEIGHT_ONLY_ATTN accepts)."""
-    global WEIGHT_ONLY_ATTN
-    if isinstance(dtype, str):
-        dtype = _parse_weight_only_attn(dtype)
-    if dtype not in (None, torch.float16, torch.bfloat16):
-        raise ValueError("weight-only attention dtype must be None, torch.float16 or torch.bfloat16")
-    WEIGHT_ONLY_ATTN = dtype
+    _set_dtype("WEIGHT_ONLY_ATTN", dtype, _parse_weight_only_attn, "weight-only attention")
 
 
 def wonly_attn_shape_ok(d):

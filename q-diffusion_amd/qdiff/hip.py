@@ -483,44 +483,42 @@ def geglu_h16(h, M, F, ldh, out, ldo):
            "qd_geglu_h16")
 
 
+def _groupnorm_h16(who, x, shape, C, ldx, groups, eps, gamma, beta, out, ldo, ws):
+    """What the three GroupNorm -> operand rows wrappers share: the checks, made here, and the launch of qd_<who>, returned as a
+    function of the wrapper's own arguments (those between beta and out), for it to call after its own checks."""
+    _h16_rows_check(who, x, ldx, C, out, ldo, C)
+    if C % 8 or C % groups:
+        raise HipEngineError(f"{who}: C={C} must be a multiple of 8 and of groups={groups}")
+    return lambda *own: _check(getattr(load(), "qd_" + who)(
+        _ptr(x, "x"), _H16[x.dtype], *shape, C, ldx, groups, float(eps), _ptr(gamma), _ptr(beta), *own, _ptr(out, "out"),
+        _H16[out.dtype], ldo, _ptr(ws, "ws"), _stream()), "qd_" + who)
+
+
 def groupnorm_h16(x, B, S, C, ldx, groups, eps, gamma, beta, silu, out, ldo, ws):
     """fp32 / fp16 channels-last rows [B*S][ldx] -> GroupNorm (+ SiLU) -> fp16 / bf16 operand rows [B*S][ldo], pad channels
     zero (qd_groupnorm_h16).  ws: groupnorm_ws_bytes(B, C, S) bytes."""
-    _h16_rows_check("groupnorm_h16", x, ldx, C, out, ldo, C)
-    if C % 8 or C % groups:
-        raise HipEngineError(f"groupnorm_h16: C={C} must be a multiple of 8 and of groups={groups}")
-    _check(load().qd_groupnorm_h16(_ptr(x, "x"), _H16[x.dtype], B, S, C, ldx, groups, float(eps), _ptr(gamma), _ptr(beta),
-                                   1 if silu else 0, _ptr(out, "out"), _H16[out.dtype], ldo, _ptr(ws, "ws"), _stream()),
-           "qd_groupnorm_h16")
+    _groupnorm_h16("groupnorm_h16", x, (B, S), C, ldx, groups, eps, gamma, beta, out, ldo, ws)(1 if silu else 0)
 
 
 def groupnorm_mod_h16(x, B, S, C, ldx, groups, eps, gamma, beta, mod, mod_ld, silu, out, ldo, ws):
     """groupnorm_h16 with the modulation of a use_scale_shift_norm block: GroupNorm(x) * (1 + scale) + shift (+ SiLU), mod the
     fp32 rows [B][mod_ld >= 2C] scale | shift (qd_groupnorm_mod_h16)."""
-    _h16_rows_check("groupnorm_mod_h16", x, ldx, C, out, ldo, C)
-    if C % 8 or C % groups:
-        raise HipEngineError(f"groupnorm_mod_h16: C={C} must be a multiple of 8 and of groups={groups}")
+    launch = _groupnorm_h16("groupnorm_mod_h16", x, (B, S), C, ldx, groups, eps, gamma, beta, out, ldo, ws)
     if mod is None or mod.dtype != torch.float32 or mod_ld < 2 * C:
         raise HipEngineError(f"groupnorm_mod_h16: modulation rows must be fp32 scale | shift with mod_ld >= 2 C (mod_ld {mod_ld}, C {C})")
-    _check(load().qd_groupnorm_mod_h16(_ptr(x, "x"), _H16[x.dtype], B, S, C, ldx, groups, float(eps), _ptr(gamma), _ptr(beta),
-                                       _ptr(mod, "mod"), mod_ld, 1 if silu else 0, _ptr(out, "out"), _H16[out.dtype], ldo,
-                                       _ptr(ws, "ws"), _stream()), "qd_groupnorm_mod_h16")
+    launch(_ptr(mod, "mod"), mod_ld, 1 if silu else 0)
 
 
 def groupnorm_resample_h16(x, B, H, W, C, ldx, groups, eps, gamma, beta, silu, resample, out, ldo, ws):
     """fp32 / fp16 channels-last rows [B*H*W][ldx] -> GroupNorm (+ SiLU) -> resampled -> fp16 / bf16 operand rows, pad channels
     zero (qd_groupnorm_resample_h16).  resample 1: the 2x2 average, rows [B*H/2*W/2][ldo] (even H, W); 2: nearest 2x, rows
     [B*2H*2W][ldo].  ws: groupnorm_ws_bytes(B, C, H * W) bytes."""
-    _h16_rows_check("groupnorm_resample_h16", x, ldx, C, out, ldo, C)
-    if C % 8 or C % groups:
-        raise HipEngineError(f"groupnorm_resample_h16: C={C} must be a multiple of 8 and of groups={groups}")
+    launch = _groupnorm_h16("groupnorm_resample_h16", x, (B, H, W), C, ldx, groups, eps, gamma, beta, out, ldo, ws)
     if resample not in (1, 2):
         raise HipEngineError(f"groupnorm_resample_h16: resample={resample} must be 1 (2x2 average) or 2 (nearest 2x)")
     if resample == 1 and (H % 2 or W % 2):
         raise HipEngineError(f"groupnorm_resample_h16: the 2x2 average needs even H, W (got {H} x {W})")
-    _check(load().qd_groupnorm_resample_h16(_ptr(x, "x"), _H16[x.dtype], B, H, W, C, ldx, groups, float(eps), _ptr(gamma), _ptr(beta),
-                                            1 if silu else 0, resample, _ptr(out, "out"), _H16[out.dtype], ldo, _ptr(ws, "ws"),
-                                            _stream()), "qd_groupnorm_resample_h16")
+    launch(1 if silu else 0, resample)
 
 
 def groupnorm_silu_bf16(x, B, S, C, groups, eps, gamma, beta, silu, out, ws, part=None):

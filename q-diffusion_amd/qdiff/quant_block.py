@@ -189,25 +189,40 @@ def spatial_wonly_wide(st, x):
             and _wonly_wide_edges(st, x, st.proj_in, st.proj_out, x.shape[1], st.proj_in.wonly_plan().Cout))
 
 
+def _wide_front(x, norm, first):
+    """Front edge of a wide route: (the channels-last rows of x, made channels-last once here if it is not; the operand rows of
+    `first`, written from them by qd_groupnorm_h16 without SiLU)."""
+    b, c, h, w = x.shape
+    rows = _nhwc_rows(x)
+    return rows, engine.wonly_groupnorm_rows(rows, b, h * w, c, norm, False, first.wonly_plan())
+
+
+def _wide_back(t, bcs, strides, last, rows, x):
+    """Back edge of a wide route: the logical [B][C][S] view bcs = (B, C, S) of `t` at element `strides` -> operand rows of
+    `last`, which adds `rows` (the input rows of the front edge) in its epilogue -> the NCHW view of x's shape."""
+    b, _, h, w = x.shape
+    M = b * h * w
+    th_ = engine.wonly_rows(t, last.wonly_plan(), *bcs, strides)
+    return _rows_to_nchw(last.forward_rows(th_, 1, 1, M, 1, M, residual=rows), b, h, w)
+
+
 def spatial_forward_wonly(st, x, context):
-    """attention.py:262-287 in the weights-only state with the wide knob: qd_groupnorm_h16 (no SiLU) writes proj_in's operand
-    rows from the channels-last rows of x (made channels-last once here if it is not), the blocks see the token rows, and
-    proj_out adds x's rows in its epilogue.  A Linear proj_in / proj_out (`use_linear`) is the same on rows."""
+    """attention.py:262-287 in the weights-only state with the wide knob: the front edge writes proj_in's operand rows, the
+    blocks see the token rows, and the back edge has proj_out add x's rows in its epilogue.  A Linear proj_in / proj_out
+    (`use_linear`) is the same on rows."""
     b, c, h, w = x.shape
     M = b * h * w
-    rows = _nhwc_rows(x)
-    pin, pout = st.proj_in.wonly_plan(), st.proj_out.wonly_plan()
-    xh = engine.wonly_groupnorm_rows(rows, b, h * w, c, st.norm, False, pin)
-    t = st.proj_in.forward_rows(xh, 1, 1, M, 1, M).view(b, h * w, pin.Cout)
+    rows, xh = _wide_front(x, st.norm, st.proj_in)
+    inner = st.proj_in.wonly_plan().Cout
+    t = st.proj_in.forward_rows(xh, 1, 1, M, 1, M).view(b, h * w, inner)
     for blk in st.transformer_blocks:
         t = blk(t, context)
-    t = t.reshape(M, pin.Cout)
+    t = t.reshape(M, inner)
     if t.stride(1) != 1:
         t = t.contiguous()
-    th_ = engine.wonly_rows(t, pout, 1, pin.Cout, M, (0, 1, t.stride(0)))
-    out = st.proj_out.forward_rows(th_, 1, 1, M, 1, M, residual=rows)
+    out = _wide_back(t, (1, inner, M), (0, 1, t.stride(0)), st.proj_out, rows, x)       # the token rows as they lie
     engine.wonly_count("spatial")
-    return _rows_to_nchw(out, b, h, w)
+    return out
 
 
 def _gn_silu_to(conv, rows, B, S, C, gn, silu=True, raw_plan=None, mod=None):
@@ -692,48 +707,10 @@ class QuantResBlock(BaseQuantBlock, ldm_unet.TimestepBlock):
         if (_int_mode(conv1, conv2, self.emb_layers[-1]) and conv1.split == 0 and conv2.split == 0 and not _dropout_live(self)
                 and (not self.updown or (H_ % 2 == 0 and not getattr(self.h_upd, "use_conv", False)))):
             return self._forward_int(x, emb, split, conv1, conv2, out_slot)
-        if self._wonly_fusable(x, emb, conv1, conv2):
-            return self._forward_wonly(x, emb, split, conv1, conv2)
-        if self._wonly_mod_fusable(x, emb, conv1, conv2):
-            return self._forward_wonly_mod(x, emb, split, conv1, conv2)
+        kind = self._wonly_route(x, emb, conv1, conv2)
+        if kind is not None:
+            return self._forward_wonly(x, emb, split, conv1, conv2, kind)
         return self._forward_sim(x, emb, split)
-
-    def _wonly_fusable(self, x, emb, conv1, conv2):
-        """Plain blocks only (no `updown`, no `use_scale_shift_norm`) with the reference's layer lists (norm, SiLU, conv /
-        norm, SiLU, dropout, conv), both convolutions reading all their channels as one segment."""
-        if not engine.WEIGHT_ONLY_FUSE or self.updown or self.use_scale_shift_norm or x.dim() != 4:
-            return False
-        if not (len(self.in_layers) == 3 and len(self.out_layers) == 4 and isinstance(self.in_layers[0], nn.GroupNorm)
-                and isinstance(self.out_layers[0], nn.GroupNorm) and isinstance(self.in_layers[1], nn.SiLU)
-                and isinstance(self.out_layers[1], nn.SiLU) and isinstance(self.out_layers[2], nn.Dropout)):
-            return False
-        if not _wonly_fuse_gate(self, (conv1, conv2), (x, emb)):
-            return False
-        return (conv1.kind == 'conv2d' and conv2.kind == 'conv2d' and engine.wonly_plain_plan(conv1.wonly_plan(), x.shape[1])
-                and engine.wonly_plain_plan(conv2.wonly_plan(), self.out_channels) and conv2.wonly_plan().Cout == self.out_channels
-                and engine.conv_out_hw(x.shape[2], x.shape[3], conv1.wonly_plan()) == (x.shape[2], x.shape[3])
-                and engine.conv_out_hw(x.shape[2], x.shape[3], conv2.wonly_plan()) == (x.shape[2], x.shape[3]))
-
-    def _forward_wonly(self, x, emb, split, conv1, conv2):
-        """Reference :83-111 in the weights-only state: GN.SiLU -> operand rows (qd_groupnorm_h16), conv1 with the embedding
-        projection as a row bias, GN.SiLU -> operand rows, conv2 with the skip rows as the residual of its epilogue.  The
-        embedding projection and the skip connection keep their own module calls."""
-        B, C, H, W = x.shape
-        S = H * W
-        rows = _nhwc_rows(x)
-        xh = engine.wonly_groupnorm_rows(rows, B, S, C, self.in_layers[0], True, conv1.wonly_plan())
-        e = self.emb_layers(emb).float()
-        if e.stride(1) != 1:
-            e = e.contiguous()
-        h = conv1.forward_rows(xh, B, H, W, rowbias=e)
-        hh = engine.wonly_groupnorm_rows(h, B, S, self.out_channels, self.out_layers[0], True, conv2.wonly_plan())
-        if isinstance(self.skip_connection, nn.Identity):
-            res = rows
-        else:
-            res = _nhwc_rows(self.skip_connection(x, split=split) if split != 0 else self.skip_connection(x))
-        out = conv2.forward_rows(hh, B, H, W, residual=res)
-        engine.WONLY_FUSED["resblock"] += 1
-        return _rows_to_nchw(out, B, H, W)
 
     def _wonly_resample(self):
         """0: no `updown`; 1: h_upd / x_upd are the 2x2 average (Downsample without convolution); 2: nearest 2x (Upsample
@@ -750,38 +727,46 @@ class QuantResBlock(BaseQuantBlock, ldm_unet.TimestepBlock):
             and op.padding in (0, (0, 0)) and not op.ceil_mode and op.divisor_override is None
         return 1 if all(pool(op) for op in ops) else None
 
-    def _wonly_mod_fusable(self, x, emb, conv1, conv2):
-        """engine.WEIGHT_ONLY_FUSE_MOD takes this call: asked only after _wonly_fusable refused.  A block with
-        `use_scale_shift_norm`, `updown` or both, with the reference's layer lists (norm, SiLU, conv / norm, SiLU, dropout, conv;
-        an `updown` block applies in_layers[:-1], h_upd / x_upd, in_layers[-1]), h_upd / x_upd the 2x2 average (even H, W) or
-        nearest 2x, everything _wonly_fuse_gate demands, both convolutions reading all their C % 8 == 0 channels as one segment
-        at the resampled size, and for scale-shift an embedding projection of 2 Cout features."""
-        if not engine.WEIGHT_ONLY_FUSE_MOD or not engine.WEIGHT_ONLY_FUSE or not (self.updown or self.use_scale_shift_norm) or x.dim() != 4:
-            return False
+    def _wonly_route(self, x, emb, conv1, conv2):
+        """The fused weights-only route this call takes, by the name of its engine.WONLY_FUSED counter: "resblock" for a plain
+        block (no `updown`, no `use_scale_shift_norm`) under engine.WEIGHT_ONLY_FUSE, "resblock_mod" for any other block, which
+        needs engine.WEIGHT_ONLY_FUSE_MOD on top, or None.  Both ask for the reference's layer lists (norm, SiLU, conv / norm,
+        SiLU, dropout, conv; an `updown` block applies in_layers[:-1], h_upd / x_upd, in_layers[-1]), everything
+        _wonly_fuse_gate demands, and both convolutions reading all their channels as one segment and keeping the (resampled)
+        size.  "resblock_mod" also asks for h_upd / x_upd being the 2x2 average (even H, W) or nearest 2x, conv1 giving
+        out_channels, and for scale-shift an embedding projection of 2 out_channels features."""
+        plain = not (self.updown or self.use_scale_shift_norm)
+        if not engine.WEIGHT_ONLY_FUSE or not (plain or engine.WEIGHT_ONLY_FUSE_MOD) or x.dim() != 4:
+            return None
         if not (len(self.in_layers) == 3 and len(self.out_layers) == 4 and isinstance(self.in_layers[0], nn.GroupNorm)
                 and isinstance(self.out_layers[0], nn.GroupNorm) and isinstance(self.in_layers[1], nn.SiLU)
                 and isinstance(self.out_layers[1], nn.SiLU) and isinstance(self.out_layers[2], nn.Dropout)):
-            return False
-        mode = self._wonly_resample()
+            return None
+        mode = self._wonly_resample()                      # (0 without `updown`: the next check then asks nothing)
         H, W = x.shape[2], x.shape[3]
-        if mode is None or (mode == 1 and (H % 2 or W % 2)) or x.shape[1] % 8 or self.out_channels % 8:
-            return False
+        if mode is None or (mode == 1 and (H % 2 or W % 2)):
+            return None
         if not _wonly_fuse_gate(self, (conv1, conv2), (x, emb)):
-            return False
+            return None
         Hr, Wr = (H // 2, W // 2) if mode == 1 else (2 * H, 2 * W) if mode == 2 else (H, W)
-        if self.use_scale_shift_norm and _out_features(self.emb_layers[-1]) != 2 * self.out_channels:
-            return False
-        return (conv1.kind == 'conv2d' and conv2.kind == 'conv2d' and engine.wonly_plain_plan(conv1.wonly_plan(), x.shape[1])
-                and engine.wonly_plain_plan(conv2.wonly_plan(), self.out_channels) and conv2.wonly_plan().Cout == self.out_channels
-                and conv1.wonly_plan().Cout == self.out_channels
-                and engine.conv_out_hw(Hr, Wr, conv1.wonly_plan()) == (Hr, Wr)
-                and engine.conv_out_hw(Hr, Wr, conv2.wonly_plan()) == (Hr, Wr))
+        p1, p2 = conv1.wonly_plan(), conv2.wonly_plan()          # (not None: _wonly_fuse_gate asked wonly_ready())
+        if not plain and (p1.Cout != self.out_channels
+                          or (self.use_scale_shift_norm and _out_features(self.emb_layers[-1]) != 2 * self.out_channels)):
+            return None
+        # the producers' C % 8 and out_channels % 8 are not asked again: wonly_plain_plan refuses a C that is no multiple of 8
+        if not (conv1.kind == 'conv2d' and conv2.kind == 'conv2d' and engine.wonly_plain_plan(p1, x.shape[1])
+                and engine.wonly_plain_plan(p2, self.out_channels) and p2.Cout == self.out_channels
+                and engine.conv_out_hw(Hr, Wr, p1) == (Hr, Wr) and engine.conv_out_hw(Hr, Wr, p2) == (Hr, Wr)):
+            return None
+        return "resblock" if plain else "resblock_mod"
 
-    def _forward_wonly_mod(self, x, emb, split, conv1, conv2):
-        """Reference :83-111 in the weights-only state for `updown` / `use_scale_shift_norm` blocks: GN.SiLU (and h_upd, before
-        the one rounding: qd_groupnorm_resample_h16) -> operand rows of conv1; conv1 with the embedding projection as a row bias
-        unless the block is scale-shift; GN * (1 + scale) + shift . SiLU (qd_groupnorm_mod_h16, the projection as `mod`) ->
-        operand rows of conv2; conv2 with the skip rows as the residual.  x_upd on the fp32 skip tensor stays in torch."""
+    def _forward_wonly(self, x, emb, split, conv1, conv2, kind):
+        """Reference :83-111 in the weights-only state: GN.SiLU (and h_upd of an `updown` block, before the one rounding:
+        qd_groupnorm_resample_h16) -> operand rows of conv1; conv1 with the embedding projection as a row bias unless the block
+        is scale-shift; GN.SiLU, for scale-shift GN * (1 + scale) + shift . SiLU (qd_groupnorm_mod_h16, the projection as `mod`)
+        -> operand rows of conv2; conv2 with the skip rows as the residual of its epilogue.  The embedding projection and the
+        skip connection keep their own module calls; x_upd on the fp32 skip tensor stays in torch.  kind: the counter of
+        _wonly_route."""
         B, C, H, W = x.shape
         mode = self._wonly_resample()
         rows = _nhwc_rows(x)
@@ -808,7 +793,7 @@ class QuantResBlock(BaseQuantBlock, ldm_unet.TimestepBlock):
         else:
             res = _nhwc_rows(self.skip_connection(x, split=split) if split != 0 else self.skip_connection(x))
         out = conv2.forward_rows(hh, B, H, W, residual=res)
-        engine.wonly_count("resblock_mod")
+        engine.wonly_count(kind)
         return _rows_to_nchw(out, B, H, W)
 
     def _forward_sim(self, x, emb, split=0):
@@ -1022,22 +1007,20 @@ class QuantAttentionBlock(BaseQuantBlock, _AttnQuant):
         return (xf + h).reshape(b, c, *spatial)
 
     def _forward_wonly_wide(self, x):
-        """Reference :175-187 in the weights-only state with engine.WEIGHT_ONLY_FUSE_WIDE: qd_groupnorm_h16 (no SiLU) writes
-        qkv's operand rows from the channels-last rows of x, the attention is qd_attn_h16 when its gate holds (else the library
-        attention), and proj_out adds x's rows in its epilogue."""
+        """Reference :175-187 in the weights-only state with engine.WEIGHT_ONLY_FUSE_WIDE: the front edge writes qkv's operand
+        rows, the attention is qd_attn_h16 when its gate holds (else the library attention), and the back edge has proj_out add
+        x's rows in its epilogue."""
         b, c, H, W = x.shape
         T = H * W
-        rows = _nhwc_rows(x)
-        xh = engine.wonly_groupnorm_rows(rows, b, T, c, self.norm, False, self.qkv.wonly_plan())
+        rows, xh = _wide_front(x, self.norm, self.qkv)
         q = self.qkv.forward_rows(xh, 1, 1, b * T, 1, b * T)
         qkv = q.view(b, T, q.shape[1]).permute(0, 2, 1)
         a = self._attention_h16(qkv) if self._wonly_attention_ok(qkv) else self.attention(qkv)
         if a.dtype not in (torch.float32, torch.float16, torch.bfloat16):
             a = a.float()
-        ah = engine.wonly_rows(a, self.proj_out.wonly_plan(), b, c, T, a.stride())
-        out = self.proj_out.forward_rows(ah, 1, 1, b * T, 1, b * T, residual=rows)
+        out = _wide_back(a, (b, c, T), a.stride(), self.proj_out, rows, x)             # the attention's own [b][c][T] layout
         engine.wonly_count("attnblock")
-        return _rows_to_nchw(out, b, H, W)
+        return out
 
     def _wonly_attention_ok(self, qkv):
         """engine.attention_h16 replaces self.attention(qkv): the repo's (or the reference's) QKVAttentionLegacy whose two
@@ -1296,7 +1279,7 @@ class QuantBasicTransformerBlock(BaseQuantBlock, _AttnQuant):
             hcat = proj.forward_rows(xh, 1, 1, M)
             gh = engine.wonly_geglu_rows(hcat, M, hcat.shape[1] // 2, ff_out.wonly_plan())
         rows = ff_out.forward_rows(gh, 1, 1, M, residual=rows)
-        engine.WONLY_FUSED["transformer"] += 1
+        engine.wonly_count("transformer")
         return rows.view(B, T, C)
 
     def _attn_int(self, att, rows, B, T, C, ln, ctx_rows, S, kv=None, pre_attention=None):

@@ -250,15 +250,15 @@ def test_resblock_with_scale_shift_norm_or_updown_keeps_todays_path(emu):
         assert emu.WONLY_FUSED["resblock"] == 1
         blk.updown = True
         try:
-            assert not blk._wonly_fusable(a[0], a[1], blk.in_layers[-1], blk.out_layers[-1])
+            assert blk._wonly_route(a[0], a[1], blk.in_layers[-1], blk.out_layers[-1]) != "resblock"
         finally:
             blk.updown = False
         blk.use_scale_shift_norm = True
         try:
-            assert not blk._wonly_fusable(a[0], a[1], blk.in_layers[-1], blk.out_layers[-1])
+            assert blk._wonly_route(a[0], a[1], blk.in_layers[-1], blk.out_layers[-1]) != "resblock"
         finally:
             blk.use_scale_shift_norm = False
-        assert blk._wonly_fusable(a[0], a[1], blk.in_layers[-1], blk.out_layers[-1])
+        assert blk._wonly_route(a[0], a[1], blk.in_layers[-1], blk.out_layers[-1]) == "resblock"
 
 
 # ---- 3. argument checks before any launch -------------------------------------------------------------------------------------

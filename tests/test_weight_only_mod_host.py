@@ -128,14 +128,14 @@ def test_every_resblock_takes_the_route(emu, monkeypatch, name):
     assert any(b.updown for b in res) and any(b.use_scale_shift_norm for b in res)
     y0, c0, f0 = _run(emu, qnn, args, False)
     from qdiff.quant_block import QuantResBlock
-    inside, route = {}, QuantResBlock._forward_wonly_mod
+    inside, route = {}, QuantResBlock._forward_wonly
 
     def spy(self, *a, **k):                                    # (not a hook: a hooked block falls back)
         n0 = len(emu.calls)
         y = route(self, *a, **k)
         inside[self] = Counter(emu.calls[n0:])
         return y
-    monkeypatch.setattr(QuantResBlock, "_forward_wonly_mod", spy)
+    monkeypatch.setattr(QuantResBlock, "_forward_wonly", spy)
     y1, c1, f1 = _run(emu, qnn, args, True)
     c0, c1 = Counter(c0), Counter(c1)
     assert "resblock_mod" not in f0 and f0["resblock"] == 0
@@ -173,7 +173,7 @@ def test_gate_refusals(emu):
     conv1, conv2 = down.in_layers[-1], down.out_layers[-1]
     engine.set_weight_only_fusion(True)
     engine.set_weight_only_fusion_mod(True)
-    gate = lambda x=a[0]: down._wonly_mod_fusable(x, a[1], conv1, conv2)
+    gate = lambda x=a[0]: down._wonly_route(x, a[1], conv1, conv2) == "resblock_mod"
 
     def run(x=a[0]):
         n0, c0 = engine.WONLY_FUSED.get("resblock_mod", 0), len(engine.calls)
@@ -182,7 +182,7 @@ def test_gate_refusals(emu):
         return y, engine.WONLY_FUSED.get("resblock_mod", 0) - n0, sum(new[p] for p in PRODUCERS)
 
     with torch.no_grad():
-        assert gate() and not down._wonly_fusable(a[0], a[1], conv1, conv2)
+        assert gate() and down._wonly_route(a[0], a[1], conv1, conv2) != "resblock"
         y_on, took, prod = run()
         assert (took, prod) == (1, 2)
         engine.set_weight_only_fusion_mod(False)
@@ -237,8 +237,8 @@ def test_wonly_fusable_still_refuses_these_blocks(emu):
     with torch.no_grad():
         for b in res:
             a, k = _block_call(qnn, args, b)
-            assert not b._wonly_fusable(a[0], a[1], b.in_layers[-1], b.out_layers[-1])
-            assert b._wonly_mod_fusable(a[0], a[1], b.in_layers[-1], b.out_layers[-1])
+            assert b._wonly_route(a[0], a[1], b.in_layers[-1], b.out_layers[-1]) != "resblock"
+            assert b._wonly_route(a[0], a[1], b.in_layers[-1], b.out_layers[-1]) == "resblock_mod"
 
 
 def test_plain_blocks_are_not_asked(emu):
@@ -247,6 +247,33 @@ def test_plain_blocks_are_not_asked(emu):
     y0, c0, f0 = _run(emu, qnn, args, False)
     y1, c1, f1 = _run(emu, qnn, args, True)
     assert c1 == c0 and f1 == f0 and "resblock_mod" not in f1 and torch.equal(y0, y1)
+
+
+@pytest.mark.parametrize("name, kind", [("ldm_tiny", "resblock"), ("ldm_updown_tiny", "resblock_mod")])
+def test_route_is_evaluated_once_per_block_forward(emu, monkeypatch, name, kind):
+    """Plain blocks (ldm_tiny) and updown / scale-shift blocks (ldm_updown_tiny), both knobs on: every QuantResBlock forward
+    walks its modules for _wonly_fuse_gate once, whichever route it takes."""
+    from qdiff import quant_block
+    from qdiff.quant_block import QuantResBlock
+    qnn, args = _model(name)
+    res, _ = _blocks(qnn)
+    forwards, gates = Counter(), Counter()
+    inner, gate = QuantResBlock._forward, quant_block._wonly_fuse_gate
+
+    def forward(self, *a, **k):                                # (not a hook: a hooked block falls back)
+        forwards[self] += 1
+        return inner(self, *a, **k)
+
+    def counted(block, layers, tensors):
+        if isinstance(block, QuantResBlock):
+            gates[block] += 1
+        return gate(block, layers, tensors)
+    monkeypatch.setattr(QuantResBlock, "_forward", forward)
+    monkeypatch.setattr(quant_block, "_wonly_fuse_gate", counted)
+    _, _, f = _run(emu, qnn, args, True)
+    assert f.get(kind, 0) == len(res) > 0 and sum(f.values()) == len(res)
+    assert set(forwards) == set(res) and all(n == 1 for n in forwards.values())
+    assert gates == forwards
 
 
 # ---- argument checks before any launch ---------------------------------------------------------------------------------------
