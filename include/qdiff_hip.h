@@ -178,7 +178,14 @@ typedef struct {
      * up-sampling (Upsample: openaimodel.py:105-120, ddim diffusion.py:36-52) — H, W are the up-sampled sizes; the
      * replication happens in the im2col source address, no up-sampled tensor exists.  Needs stride 1, kh*kw > 1, even H, W. */
     int32_t        upsample2x;
-    int32_t        _pad3;
+    /* residual row period (the field that used to be _pad3; size and offsets unchanged): 0 = output row m adds residual row m.
+     * P > 0: output row m adds residual[(m % P) * ldr + n] — the residual holds P rows only, those of the first P / (Ho*Wo)
+     * samples, and every later group of samples re-reads them (the two halves of a classifier-free-guidance batch share
+     * everything up to the first cross-attention: nothing is duplicated in memory).  The mapping is per row: a tile may straddle
+     * the period.  Needs a residual, M % P == 0 and P % (Ho*Wo) == 0.  qd_conv2d_i8 with QD_EPI_LINEAR only (fp32 / fp16 rows,
+     * either block form, one or two segments); such a descriptor is never contracted split-K (qd_conv2d_i8_splitk_ws_bytes = 0),
+     * so the bytes do not depend on splitk_ws.  Every other entry and epilogue refuses a non-zero value. */
+    int32_t        res_period;
 } qd_conv_desc;
 
 int qd_conv2d_i8(const qd_conv_desc* d, void* stream);
@@ -372,6 +379,19 @@ int qd_attn_i8(const int8_t* q, const int8_t* k, const int8_t* vt,
                float* out, int64_t ldo,
                int8_t* out8, int64_t ldo8, const float* oq_params, int oq_min, int oq_max, int oq_off,
                void* ws, int64_t ws_bytes, void* stream);
+/* qd_attn_i8_qp (additive in ABI 20): qd_attn_i8 whose query operand has a head PERIOD.  q (and qsum) hold q_heads heads,
+ * [q_heads][Tpad][dpad]; head bh of the launch reads the q rows of head bh % q_heads.  Everything else stays per bh: k, vt, vsum,
+ * kterm, the workspace, the output rows.  BH % q_heads == 0 and q_heads % H == 0 (whole samples repeat).  q_heads = BH is
+ * qd_attn_i8, which is implemented as exactly that call; every launch form (attn_kernel, the lean kernel, the statistics + P.V
+ * launches) takes the period.  Cross-attention of a classifier-free-guidance batch: both halves share the queries, each half has
+ * its own context. */
+int qd_attn_i8_qp(const int8_t* q, const int8_t* k, const int8_t* vt,
+                  const int32_t* qsum, const int32_t* kterm, const int32_t* vsum,
+                  int BH, int H, int T, int S, int d, int Tpad, int Spad, int dpad,
+                  const float* prm, int wbits, int wmin, int wmax, int q_asym,
+                  float* out, int64_t ldo,
+                  int8_t* out8, int64_t ldo8, const float* oq_params, int oq_min, int oq_max, int oq_off,
+                  void* ws, int64_t ws_bytes, void* stream, int q_heads);
 
 /* ------------------------------------------------------------------------------------------
  * K7s/K8s  the two attention contractions as standalone batched integer GEMMs, for callers that use

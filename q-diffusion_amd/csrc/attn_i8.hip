@@ -35,6 +35,7 @@ struct AttnK {
     int BH, H, T, S, d, Tpad, Spad, dpad;
     float wmin, wmax;
     int iwmin;
+    int qh;                   // query heads: head bh reads the q operand of head bh % qh (qd_attn_i8_qp); BH = every head its own
     // optional quantised output (the act quantiser of the Linear that consumes the attention output)
     int8_t* out8;
     long ldo8;
@@ -46,6 +47,11 @@ struct AttnK {
                               // head share an XCD (block b runs on XCD b % 8: with a (gx, BH) grid every XCD's L2 fetched every head's
                               // K / V — 21 % L2 misses, profiles/r03_pmc_attn.txt)
 };
+
+// q operand head of head bh (block-uniform).  qd_attn_i8_qp: the heads of a batch whose samples come in equal groups (the two
+// halves of a classifier-free-guidance batch up to the first cross-attention) share the query rows of the first group; k, vt,
+// vsum, the key-term table, the workspace and the output rows stay per head.
+__device__ __forceinline__ int attn_q_head(const AttnK& p, int bh) { return bh < p.qh ? bh : bh % p.qh; }
 
 // Epilogue of all three kernels: I = sum_j (u_j - zpw)(v'_j - zv'), restored exactly from the operand-byte accumulators
 // (ol / oh: lo / hi bytes of the codes against v'), the V^T column sums and the code sums us[r] of the lane's 16 queries;
@@ -133,7 +139,7 @@ __global__ __launch_bounds__(256, (DT * (P16 ? 2 : 1) <= 6) ? 2 : 1) void attn_k
     constexpr int   MASKED = -(1 << 30);
 
     v4i qf[DT];
-    const int8_t* qrow = p.q + ((long)bh * p.Tpad + q0 + frow) * p.dpad + half * 16;
+    const int8_t* qrow = p.q + ((long)attn_q_head(p, bh) * p.Tpad + q0 + frow) * p.dpad + half * 16;
 #pragma unroll
     for (int kk = 0; kk < DT; ++kk) qf[kk] = *reinterpret_cast<const v4i*>(qrow + kk * 32);
 
@@ -413,7 +419,7 @@ __device__ __forceinline__ void attn_lean_body(const AttnK& p) {
     constexpr int   MAGICI = QD_MAGICI;
 
     v4i qf[DT];
-    const int8_t* qrow = p.q + ((long)bh * p.Tpad + q0 + frow) * p.dpad + half * 16;
+    const int8_t* qrow = p.q + ((long)attn_q_head(p, bh) * p.Tpad + q0 + frow) * p.dpad + half * 16;
 #pragma unroll
     for (int kk = 0; kk < DT; ++kk) qf[kk] = *reinterpret_cast<const v4i*>(qrow + kk * 32);
     const int8_t* kbase = p.k + (long)bh * p.Spad * p.dpad + (long)frow * p.dpad + half * 16;
@@ -857,7 +863,7 @@ __global__ __launch_bounds__(256, QD_ATTN_STATS_OCC) void attn_stats_kernel(cons
     constexpr int MAGICI = QD_MAGICI;
 
     v4i qf[DT];
-    const int8_t* qrow = p.q + ((long)bh * p.Tpad + q0 + frow) * p.dpad + half * 16;
+    const int8_t* qrow = p.q + ((long)attn_q_head(p, bh) * p.Tpad + q0 + frow) * p.dpad + half * 16;
 #pragma unroll
     for (int kk = 0; kk < DT; ++kk) qf[kk] = *reinterpret_cast<const v4i*>(qrow + kk * 32);
     const int ntile = p.Spad >> 5;
@@ -978,7 +984,7 @@ __global__ __launch_bounds__(256, FULL ? QD_ATTN_PVFULL_OCC : QD_ATTN_PV_OCC) vo
     constexpr float MAGIC = QD_MAGIC;
 
     v4i qf[DT];
-    const int8_t* qrow = p.q + ((long)bh * p.Tpad + q0 + frow) * p.dpad + half * 16;
+    const int8_t* qrow = p.q + ((long)attn_q_head(p, bh) * p.Tpad + q0 + frow) * p.dpad + half * 16;
 #pragma unroll
     for (int kk = 0; kk < DT; ++kk) qf[kk] = *reinterpret_cast<const v4i*>(qrow + kk * 32);
     const AttnStat st = stat[(long)bh * p.Tpad + q0 + frow];
@@ -1301,15 +1307,17 @@ extern "C" int qd_attn_keyterm(const int8_t* k, int BH, int Spad, int dpad, cons
     return 0;
 }
 
-extern "C" int qd_attn_i8(const int8_t* q, const int8_t* k, const int8_t* vt, const int32_t* qsum, const int32_t* kterm,
-                          const int32_t* vsum, int BH, int H, int T, int S, int d, int Tpad, int Spad, int dpad,
-                          const float* prm, int wbits, int wmin, int wmax, int q_asym, float* out, int64_t ldo,
-                          int8_t* out8, int64_t ldo8, const float* oq_params, int oq_min, int oq_max, int oq_off,
-                          void* ws, int64_t ws_bytes, void* stream) {
+extern "C" int qd_attn_i8_qp(const int8_t* q, const int8_t* k, const int8_t* vt, const int32_t* qsum, const int32_t* kterm,
+                             const int32_t* vsum, int BH, int H, int T, int S, int d, int Tpad, int Spad, int dpad,
+                             const float* prm, int wbits, int wmin, int wmax, int q_asym, float* out, int64_t ldo,
+                             int8_t* out8, int64_t ldo8, const float* oq_params, int oq_min, int oq_max, int oq_off,
+                             void* ws, int64_t ws_bytes, void* stream, int q_heads) {
     QD_REQUIRE(q && k && vt && vsum && prm && (out || out8), "qd_attn_i8: null pointer");
     QD_REQUIRE(!out8 || (oq_params && ldo8 >= (int64_t)H * d && oq_max - oq_off <= 127 && oq_min - oq_off >= -128),
                "qd_attn_i8: quantised output needs oq_params, ldo8 >= H*d and a grid that fits int8");
     QD_REQUIRE(BH > 0 && H > 0 && BH % H == 0 && T > 0 && S > 0 && d > 0, "qd_attn_i8: bad shape");
+    QD_REQUIRE(q_heads > 0 && BH % q_heads == 0 && q_heads % H == 0,
+               "qd_attn_i8_qp: q_heads (%d) must divide BH (%d) and be a multiple of H (%d)", q_heads, BH, H);
     QD_REQUIRE(Tpad % 32 == 0 && Spad % 32 == 0 && dpad % 32 == 0 && Tpad >= T && Spad >= S && dpad >= d, "qd_attn_i8: padded dims must be multiples of 32");
     QD_REQUIRE((long)BH * ((T + 127) / 128) < (1L << 31), "qd_attn_i8: too many blocks");
     QD_REQUIRE(wbits == 8 || wbits == 16, "qd_attn_i8: probability bits must be 8 or 16 (got %d)", wbits);
@@ -1319,7 +1327,7 @@ extern "C" int qd_attn_i8(const int8_t* q, const int8_t* k, const int8_t* vt, co
     const bool asym = q_asym != 0;
     const AttnKnobs& kn = attn_knobs();
     AttnK a{q, k, vt, qsum, kterm, vsum, prm, out, (long)ldo, BH, H, T, S, d, Tpad, Spad, dpad, (float)wmin, (float)wmax, wmin,
-            out8, (long)ldo8, oq_params, (float)oq_min, (float)oq_max, oq_off, kn.xcd != 0 ? 1 : 0, (T + 127) / 128};
+            q_heads, out8, (long)ldo8, oq_params, (float)oq_min, (float)oq_max, oq_off, kn.xcd != 0 ? 1 : 0, (T + 127) / 128};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const bool p16 = wbits == 16;
     // lean variant: needs a padding row of V^T (d not a multiple of 32) and |scores| < 2^22 (d < 64)
@@ -1354,4 +1362,13 @@ extern "C" int qd_attn_i8(const int8_t* q, const int8_t* k, const int8_t* vt, co
     }
     QD_LAUNCH_CHECK("qd_attn_i8");
     return 0;
+}
+
+extern "C" int qd_attn_i8(const int8_t* q, const int8_t* k, const int8_t* vt, const int32_t* qsum, const int32_t* kterm,
+                          const int32_t* vsum, int BH, int H, int T, int S, int d, int Tpad, int Spad, int dpad,
+                          const float* prm, int wbits, int wmin, int wmax, int q_asym, float* out, int64_t ldo,
+                          int8_t* out8, int64_t ldo8, const float* oq_params, int oq_min, int oq_max, int oq_off,
+                          void* ws, int64_t ws_bytes, void* stream) {
+    return qd_attn_i8_qp(q, k, vt, qsum, kterm, vsum, BH, H, T, S, d, Tpad, Spad, dpad, prm, wbits, wmin, wmax, q_asym, out, ldo,
+                         out8, ldo8, oq_params, oq_min, oq_max, oq_off, ws, ws_bytes, stream, BH);
 }

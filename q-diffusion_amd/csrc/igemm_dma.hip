@@ -76,6 +76,7 @@ struct ConvD {
     long   gn_ld;             //   channels per chunk row of gnpart (>= Cout: column range of a wider statistics buffer)
     int    pointwise;         // 1x1 convolution / linear layer without padding or stride: output row m is input pixel m
     int    res_f16;           // O_HROWS: the fp residual is fp16 (else fp32)
+    int    res_period;        // O_F32 / O_F16 rows, > 0: output row m adds residual row m % res_period (0: row m)
     int    ups;               // x is the HALF-resolution map [B][H/2][W/2][ldx]; the convolution runs on its nearest-2x up-sampling
 };
 
@@ -905,6 +906,18 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
     constexpr bool H16_OUT = OUT == O_F16, B16_OUT = OUT == O_BF16;
     const bool has_rb = p.rowbias != nullptr, has_res = p.residual != nullptr;
     const bool vec = p.vec != 0;
+    // residual row of output row m: per ROW, a tile may straddle the period (the residual exists for the first res_period rows
+    // only: the half of a classifier-free-guidance batch that was computed once); rows fit 32 bits (host)
+    // One division per block (m0 % period, scalar), then a subtraction per row: a row of this tile lies less than BM behind m0, so
+    // the loop runs at most once whenever the period is at least a tile of rows, BM / period + 1 times otherwise.
+    const unsigned rper = BF ? 0u : (unsigned)p.res_period;
+    const unsigned rbase0 = rper ? (unsigned)m0 % rper : 0u;
+    auto res_row = [&](long m) __attribute__((always_inline)) -> long {
+        if (!rper) return m;
+        unsigned r = rbase0 + (unsigned)(m - m0);
+        while (r >= rper) r -= rper;
+        return (long)r;
+    };
     float*  const of = reinterpret_cast<float*>(p.out);
     __half* const oh = reinterpret_cast<__half*>(p.out);
     const float*  const rf = reinterpret_cast<const float*>(p.residual);
@@ -984,7 +997,7 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
                     }
                     if (has_res) {
                         if (OUT == O_F32) {
-                            const float* src = rf + mrow[ps] * p.ldr + n4c;
+                            const float* src = rf + res_row(mrow[ps]) * p.ldr + n4c;
                             if (vec && nok4) rs[ps] = *reinterpret_cast<const v4f*>(src);
                             else {
 #pragma unroll
@@ -998,7 +1011,7 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
                                 for (int e = 0; e < 4; ++e) rs[ps][e] = n4 + e < p.Cout ? qd_bf2f(src[e]) : 0.f;
                             }
                         } else {
-                            const __half* src = rh + mrow[ps] * p.ldr + n4c;
+                            const __half* src = rh + res_row(mrow[ps]) * p.ldr + n4c;
                             if (vec && nok4) rs[ps] = qd_ld4h(src);
                             else {
 #pragma unroll
@@ -1136,7 +1149,7 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
             for (int u = 0; u < 2; ++u) {
                 const long m = m0 + rbase + (pb + u) * 8 + rr0;
                 mrow[u] = m < p.M ? m : m0;
-                if (has_res) rs[u] = *reinterpret_cast<const v4i*>(rh + mrow[u] * p.ldr + n8c);
+                if (has_res) rs[u] = *reinterpret_cast<const v4i*>(rh + res_row(mrow[u]) * p.ldr + n8c);
             }
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
@@ -1470,6 +1483,7 @@ int nt_for(int N) { return N % 160 == 0 ? 5 : (N % 224 == 0 ? 7 : (N > 64 ? 4 : 
 int choose_splitk(const qd_conv_desc* d, int* it_per) {
     *it_per = 0;
     if (d->nseg != 1 || d->epilogue != QD_EPI_LINEAR) return 1;
+    if (d->res_period != 0) return 1;             // the periodic residual lives in the fused epilogue only: never split (same bytes)
     const long M = (long)d->B * d->Ho * d->Wo;
     const int  N = d->Cout, bn = 32 * (d->wbits == 8 ? (N > 64 ? 4 : 2) : nt_for(N));
     const long blocks0 = ((M + 127) / 128) * ((N + bn - 1) / bn);
@@ -1514,6 +1528,13 @@ int run(const qd_conv_desc* d, int32_t* iout, void* stream) {
     k.M = d->B * d->Ho * d->Wo; k.taps = d->kh * d->kw; k.nseg = d->nseg;
     k.pointwise = k.taps == 1 && d->stride == 1 && d->pad_t == 0 && d->pad_l == 0 && d->H == d->Ho && d->W == d->Wo;
     k.ups = d->upsample2x ? 1 : 0;
+    if (d->res_period != 0) {
+        QD_REQUIRE(d->epilogue == QD_EPI_LINEAR && !iout, "qd_conv2d_i8: res_period needs the linear epilogue (fp32 / fp16 rows)");
+        QD_REQUIRE(d->residual != nullptr, "qd_conv2d_i8: res_period without a residual");
+        QD_REQUIRE(d->res_period > 0 && k.M % d->res_period == 0 && d->res_period % (d->Ho * d->Wo) == 0,
+                   "qd_conv2d_i8: res_period (%d) must divide M (%d) and be a multiple of Ho*Wo (%d)", d->res_period, k.M, d->Ho * d->Wo);
+        k.res_period = d->res_period;
+    }
     k.ntiles = (d->Cout + 31) / 32;
     for (int s = 0; s < d->nseg; ++s) {
         const qd_conv_seg& g = d->seg[s];
@@ -1670,6 +1691,7 @@ int run_bf16(const qd_conv_desc* d, void* stream) {
     const bool fh = d->wbits == 17;                  // operands are IEEE halves
     QD_REQUIRE(d->out_dtype == QD_F32 || d->out_dtype == (fh ? QD_F16 : QD_BF16), "qd_conv2d_bf16: out_dtype must be f32 or the operand type");
     QD_REQUIRE(d->nseg == 1 && d->epilogue == QD_EPI_LINEAR && !d->rowbias, "qd_conv2d_bf16: one segment, linear epilogue, no row bias");
+    QD_REQUIRE(d->res_period == 0, "qd_conv2d_bf16: res_period is not supported (qd_conv2d_i8 with the linear epilogue only)");
     QD_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0 && d->Cout > 0, "qd_conv2d_bf16: bad shape");
     QD_REQUIRE(d->kh > 0 && d->kw > 0 && d->stride > 0 && d->kh * d->kw <= 32, "qd_conv2d_bf16: bad kernel/stride (at most 32 taps)");
     QD_REQUIRE((long)d->B * d->Ho * d->Wo < (1L << 31), "qd_conv2d_bf16: M overflows int32");
@@ -1791,6 +1813,8 @@ void launch_group(const ConvG& g, int n, hipStream_t st) {
 // the n single launches it always was: same bytes either way.
 int run_group(const qd_conv_desc* const* descs, int n, void* stream) {
     QD_REQUIRE(descs && n >= 1 && n <= 3, "qd_conv2d_i8_group: 1..3 descriptors");
+    for (int i = 0; i < n; ++i)
+        QD_REQUIRE(!descs[i] || descs[i]->res_period == 0, "qd_conv2d_i8_group: res_period is not supported (head-layout epilogues)");
     GroupCapture cap[3];
     bool ok = n >= 2;
     for (int i = 0; i < n && ok; ++i) {
@@ -2362,6 +2386,7 @@ int choose_wq_splitk(const qd_conv_desc* d, int* it_per) {
 int run_wq_h16(const qd_conv_desc* d, int act_dtype, void* stream) {
     QD_REQUIRE(d != nullptr, "qd_conv2d_wq_h16: null descriptor");
     QD_REQUIRE(d->x && d->w && d->out, "qd_conv2d_wq_h16: null tensor pointer");
+    QD_REQUIRE(d->res_period == 0, "qd_conv2d_wq_h16: res_period is not supported (qd_conv2d_i8 with the linear epilogue only)");
     QD_REQUIRE(act_dtype == QD_F16 || act_dtype == QD_BF16, "qd_conv2d_wq_h16: act_dtype must be QD_F16 or QD_BF16");
     QD_REQUIRE(d->w_tiled && (d->wbits == 4 || d->wbits == 8), "qd_conv2d_wq_h16: weights must be tile-ordered codes of qd_pack_weights_t4 / _t8 (w_tiled = 1, wbits 4 / 8)");
     QD_REQUIRE(d->out_dtype == QD_F32 || d->out_dtype == QD_F16 || d->epilogue == QD_EPI_GEGLU_H16, "qd_conv2d_wq_h16: out_dtype must be f32/f16");

@@ -178,19 +178,32 @@ class SpatialTransformer(nn.Module):
         """out_slot (engine-internal, optional): engine.CatSlot side that receives the output on the integer path."""
         from .. import quant_block as qb            # lazy: quant_block imports this module's classes
         b, c, h, w = x.shape
-        if qb._int_mode(self.proj_in, self.proj_out) and not (self.proj_in.split or self.proj_out.split):
+        if qb.spatial_int_route(self):
             # quantised: GroupNorm emits proj_in's int8 rows directly (no SiLU here), the 1x1 projections are
             # row GEMMs on the channels-last stream and the `+ x` rides in proj_out's epilogue.
+            from .. import engine
             rows = qb._nhwc_rows(x)
             xq = qb._gn_silu_to(self.proj_in, rows, b, h * w, c, self.norm, silu=False)
             o = self.proj_in.forward_codes(xq, b, h, w)
             t = o.view(b, h * w, -1)
             last = len(self.transformer_blocks) - 1
+            # a guidance pair (qb.pair_block): x holds the n samples both halves of the batch share, the one transformer block
+            # forks at its cross-attention and returns 2n samples, proj_out adds row m % (n h w) of the shared input
+            pair = engine._PAIR_N[0] == b and b > 0
+            pkw = {"pair": True} if pair else {}
             for i, blk in enumerate(self.transformer_blocks):
                 if i == last and self.proj_out.act_quantizer.inited and isinstance(blk, qb.QuantBasicTransformerBlock):
-                    t = blk(t, context, out_plan=self.proj_out.conv_plan())     # may hand back proj_out's int8 rows
+                    t = blk(t, context, out_plan=self.proj_out.conv_plan(), **pkw)     # may hand back proj_out's int8 rows
                 else:
-                    t = blk(t, context)
+                    t = blk(t, context, **pkw)
+            if pair:
+                period = b * h * w
+                if t.dtype == torch.int8:
+                    out = qb._period_rows(self.proj_out.conv_plan(), t, 2 * period, rows, period, gn_stats=True, slot=out_slot)
+                else:
+                    out = qb._linear_rows(self.proj_out, t.reshape(2 * period, t.shape[-1]), residual=rows, gn_stats=True, slot=out_slot,
+                                          res_period=period)
+                return qb._rows_to_nchw(out, 2 * b, h, w)
             if t.dtype == torch.int8:
                 out = self.proj_out.forward_codes(t, 1, 1, b * h * w, residual=rows, gn_stats=True, slot=out_slot)
             else:
@@ -521,8 +534,14 @@ class UNetModel(nn.Module):
                  if (plan is not None and len(plan) == n_in and qb.CAT_SLOTS and not torch.is_grad_enabled()) else None)
         seen = [None] * n_in
         skips = []
+        # a classifier-free-guidance pair: input_blocks[1] runs on the first half of the batch up to its cross-attention
+        # (conv_in stays at full batch: its output is a skip); any other layout evaluates as always
+        pair_n = qb.pair_stretch(self, h, emb, context) if engine._PAIR[0] else 0
         for i, blk in enumerate(self.input_blocks):
-            h = blk(h, emb, context, out_slot=slots[i].side(1) if slots else None)
+            if i == 1 and pair_n:
+                h = qb.pair_block(blk, h, emb, context, pair_n, slots[i].side(1) if slots else None)
+            else:
+                h = blk(h, emb, context, out_slot=slots[i].side(1) if slots else None)
             skips.append(h)
         h = self.middle_block(h, emb, context, out_slot=slots[-1].side(0) if slots else None)
         for blk in self.output_blocks:

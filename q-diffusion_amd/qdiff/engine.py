@@ -343,6 +343,56 @@ def set_stream_dtype(dtype):
     _EFFECTIVE[0] = None
 
 
+# Classifier-free-guidance pairs.  A sampler evaluates the UNet on torch.cat([x] * 2), torch.cat([t] * 2),
+# torch.cat([uncond, cond]) (reference plms.py:184-187): the two halves of the batch are the same samples and differ in the
+# context only, so everything up to the first cross-attention is computed once for both (QuantModel.forward decides,
+# arch/ldm_unet.UNetModel.forward walks, quant_block forks).  QDIFF_CFG_SHARE=0 / set_cfg_share(False): every evaluation as before.
+CFG_SHARE = os.environ.get("QDIFF_CFG_SHARE", "1") != "0"
+_PAIR_MARKS = {}         # id(tensor) -> (weakref, in-place version): "the two halves of this tensor's batch hold the same values"
+_PAIR = [0]              # the evaluation being issued is a pair (set around it by QuantModel.forward, like ContextKV.select)
+_PAIR_N = [0]            # n > 0 while the walk is inside the shared stretch: the block in flight sees the first n samples
+_PAIR_TAKEN = [False]    # the walk of the evaluation in flight entered the shared stretch
+
+
+def set_cfg_share(on):
+    global CFG_SHARE
+    CFG_SHARE = bool(on)
+
+
+def pair_entries_ok(x):
+    """The kernels behind `x` implement the two periods of the fork: a GPU tensor and a library that exports qd_attn_i8_qp.  A
+    library of an earlier revision (QDIFF_HIP_LIB, A/B runs) has the same ABI number but reads qd_conv_desc.res_period as padding:
+    with it every evaluation stays unshared."""
+    return x.is_cuda and hip.has_pair_entries()
+
+
+def mark_pair(x_in, t_in):
+    """The caller built x_in = torch.cat([x] * 2) and t_in = torch.cat([t] * 2): both halves of either batch are equal.  Recorded
+    by identity and in-place version (as ContextKV._alias records a context): an in-place write afterwards voids the mark, and
+    an inference tensor, which has no version counter, is never marked.  No device work, no read-back."""
+    import weakref
+    pair = (x_in, t_in)
+    if not all(torch.is_tensor(t) and t.dim() >= 1 and t.shape[0] % 2 == 0 and tensor_version(t) is not None for t in pair):
+        return False
+    if len(_PAIR_MARKS) > 64:
+        for k in [k for k, (r, _) in _PAIR_MARKS.items() if r() is None]:
+            del _PAIR_MARKS[k]
+        if len(_PAIR_MARKS) > 64:
+            _PAIR_MARKS.clear()
+    for t in pair:
+        _PAIR_MARKS[id(t)] = (weakref.ref(t), t._version)
+    return True
+
+
+def pair_marked(*tensors):
+    """Every tensor carries a mark of mark_pair that still holds (same object, same in-place version)."""
+    for t in tensors:
+        m = _PAIR_MARKS.get(id(t)) if torch.is_tensor(t) else None
+        if m is None or m[0]() is not t or tensor_version(t) != m[1]:
+            return False
+    return True
+
+
 class CatSlot:
     """Planned destination of one skip concatenation `th.cat([h, hs.pop()], dim=1)` (openaimodel.py:776, ddim
     diffusion.py:340): the kernel that produces the decoder-side `h` (side 0) and the kernel that produced the encoder-side
@@ -400,13 +450,14 @@ def upsample_fold_ok(plan, H, W):
 
 
 def conv_forward(plan, xq, B, H, W, Ho=None, Wo=None, out=None, rowbias=None, residual=None, acc_out=None,
-                 out_dtype=None, pad_tl=None, splitk=None, gn_stats=False, slot=None, upsample2x=False):
+                 out_dtype=None, pad_tl=None, splitk=None, gn_stats=False, slot=None, upsample2x=False, res_period=0):
     """Run K3/K4 on quantised rows xq [B*H*W][ldx].  Returns out [B*Ho*Wo][Cout] (row-major).
     splitk=False forbids the split-K schedule (tests compare it with the default, which lets the library decide).
     gn_stats=True: when the layer is eligible (tile-ordered int4, fp32 out, Ho*Wo % 128 == 0, not a split-K layer) the
     kernel also writes the first level of GroupNorm statistics of its output; they are attached to the returned tensor
     as `out.qd_gn_part` ([B][Ho*Wo/128][Cout][2]) for groupnorm_silu_quant to pick up.
-    slot: optional CatSlot side — the output (and its statistics) land in that column range of the concatenation buffer."""
+    slot: optional CatSlot side — the output (and its statistics) land in that column range of the concatenation buffer.
+    res_period: P > 0 = `residual` holds P rows and output row m adds row m % P (qd_conv_desc.res_period)."""
     if Ho is None:
         Ho, Wo = conv_out_hw(H, W, plan)
     M = B * Ho * Wo
@@ -422,6 +473,8 @@ def conv_forward(plan, xq, B, H, W, Ho=None, Wo=None, out=None, rowbias=None, re
             out = torch.empty((M, plan.Cout), dtype=out_dtype, device=xq.device)
     else:
         slot = None
+    if res_period and (residual is None or residual.shape[0] < res_period or xq.shape[0] < M):
+        raise hip.HipEngineError(f"conv_forward: res_period {res_period} needs a residual of that many rows")
     pad = plan.pad if pad_tl is None else pad_tl
     call = hip.ConvCall(x=xq, w=plan.pack.wq, out=out, bias=plan.bias, rowbias=rowbias,
                         residual=residual, ldx=plan.ldx, ldk=plan.pack.ldk,
@@ -430,7 +483,7 @@ def conv_forward(plan, xq, B, H, W, Ho=None, Wo=None, out=None, rowbias=None, re
                         ld_rowbias=(rowbias.stride(0) if rowbias is not None else 0),
                         B=B, H=H, W=W, Ho=Ho, Wo=Wo, Cout=plan.Cout, kh=plan.kh, kw=plan.kw, stride=plan.stride,
                         pad_t=pad, pad_l=pad, wbits=plan.pack.wbits, w_tiled=plan.pack.tiled, segs=plan.segs,
-                        splitk=splitk, upsample2x=upsample2x)
+                        splitk=splitk, upsample2x=upsample2x, res_period=res_period)
     part = None
     if (gn_stats and acc_out is None and plan.pack.tiled and out.dtype in (torch.float32, torch.float16) and (Ho * Wo) % 128 == 0
             and out.stride(1) == 1 and (splitk is False or hip.splitk_ws_bytes(call) == 0)):
@@ -1137,23 +1190,27 @@ def heads_from_float(ap, which, x, B, T, H, d, strides, out8, vsum=None):
                        which == 2, out8, vsum if which == 2 else None, pad32(T), pad32(d))
 
 
-def attention_codes(ap, q8, k8, v8, vsum, B, T, S, H, d, out=None, out_plan=None, kterm=None):
+def attention_codes(ap, q8, k8, v8, vsum, B, T, S, H, d, out=None, out_plan=None, kterm=None, q_heads=None):
     """Fused quantised attention on prepared operand bytes; returns merged-head rows out[B*T][H*d] fp32 —
     or, with out_plan (the ConvPlan of the Linear that consumes the output, one segment, input width H*d), that
     Linear's int8 input rows [B*T][out_plan.ldx], quantised in the attention epilogue.
     kterm: the key-term table of THIS k8 (hip.attn_keyterm) when the caller keeps one (static keys); else hip.attn_i8
-    builds it per call where the head dim takes one."""
+    builds it per call where the head dim takes one.
+    q_heads: q8 holds that many heads and head bh reads head bh % q_heads (qd_attn_i8_qp); None: B * H heads."""
+    if q_heads is not None and (q_heads <= 0 or q8.shape[0] < q_heads or k8.shape[0] < B * H):
+        raise hip.HipEngineError(f"attention_codes: q_heads {q_heads} must be positive and q8 must hold that many heads")
+    qkw = {} if q_heads is None else {"q_heads": q_heads}
     if out_plan is not None:
         if len(out_plan.segs) != 1 or out_plan.ldx != H * d:
             raise hip.HipEngineError("attention_codes: out_plan must take exactly the H*d merged-head features")
         out8 = torch.empty((B * T, out_plan.ldx), dtype=torch.int8, device=q8.device)
         hip.attn_i8(q8, k8, v8, vsum, B * H, H, T, S, d, pad32(T), pad32(S), pad32(d), ap.prm, ap.wbits, ap.wmin, ap.wmax,
-                    ap.asym, None, 0, out8=out8, oq_params=out_plan.qparams[0], oq_grid=out_plan.grids[0], kterm=kterm)
+                    ap.asym, None, 0, out8=out8, oq_params=out_plan.qparams[0], oq_grid=out_plan.grids[0], kterm=kterm, **qkw)
         return out8
     if out is None:
         out = torch.empty((B * T, H * d), dtype=torch.float32, device=q8.device)
     hip.attn_i8(q8, k8, v8, vsum, B * H, H, T, S, d, pad32(T), pad32(S), pad32(d), ap.prm, ap.wbits, ap.wmin, ap.wmax,
-                ap.asym, out, out.stride(0), kterm=kterm)
+                ap.asym, out, out.stride(0), kterm=kterm, **qkw)
     return out
 
 

@@ -44,7 +44,7 @@ class ConvDesc(ctypes.Structure):
                 ("splitk_ws", ctypes.c_void_p), ("splitk_ws_bytes", ctypes.c_int64),
                 ("hd_H", ctypes.c_int32), ("hd_d", ctypes.c_int32), ("hd_T", ctypes.c_int32), ("hd_Tpad", ctypes.c_int32),
                 ("hd_dpad", ctypes.c_int32), ("oq_prescale", ctypes.c_float), ("hd_sum", ctypes.c_void_p),
-                ("gn_part", ctypes.c_void_p), ("gn_ld", ctypes.c_int64), ("upsample2x", ctypes.c_int32), ("_pad3", ctypes.c_int32)]
+                ("gn_part", ctypes.c_void_p), ("gn_ld", ctypes.c_int64), ("upsample2x", ctypes.c_int32), ("res_period", ctypes.c_int32)]
 
 
 class RawSeg(ctypes.Structure):
@@ -65,7 +65,7 @@ EXPORTS = ["qd_abi_version", "qd_last_error", "qd_device_ok", "qd_box_probe", "q
            "qd_pack_weights_t8",
            "qd_conv2d_i8", "qd_conv_config", "qd_conv2d_i8_group", "qd_conv2d_i8_splitk_ws_bytes",
            "qd_conv2d_i8_acc", "qd_groupnorm_ws_bytes", "qd_groupnorm_silu_quant", "qd_groupnorm_mod_silu_quant", "qd_layernorm_quant",
-           "qd_geglu_quant", "qd_quantize_heads", "qd_attn_i8", "qd_attn_keyterm", "qd_attn_uses_keyterm", "qd_attn_config", "qd_attn_ws_bytes", "qd_bmm_qk_i8", "qd_bmm_pv_i8", "qd_temb_mlp",
+           "qd_geglu_quant", "qd_quantize_heads", "qd_attn_i8", "qd_attn_i8_qp", "qd_attn_keyterm", "qd_attn_uses_keyterm", "qd_attn_config", "qd_attn_ws_bytes", "qd_bmm_qk_i8", "qd_bmm_pv_i8", "qd_temb_mlp",
            "qd_fakequant_blocks", "qd_fakequant_fwd", "qd_fakequant_bwd",
            "qd_conv2d_bf16", "qd_pack_weights_bf16_bytes", "qd_pack_weights_bf16", "qd_groupnorm_silu_bf16",
            "qd_pack_weights_h16", "qd_groupnorm_silu_h16", "qd_conv2d_wq_h16", "qd_rows_to_h16",
@@ -112,6 +112,8 @@ def load():
                                       vp, vp, i32, i32, vp]
     lib.qd_attn_i8.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp,
                                i64, vp, i64, vp, i32, i32, i32, vp, i64, vp]
+    if hasattr(lib, "qd_attn_i8_qp"):            # (an A/B library of an earlier revision, QDIFF_HIP_LIB, has none: calling it is an error there)
+        lib.qd_attn_i8_qp.argtypes = lib.qd_attn_i8.argtypes + [i32]
     lib.qd_attn_keyterm.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     lib.qd_attn_uses_keyterm.argtypes = [i32, i32, i32]
     lib.qd_attn_config.argtypes = [i32, i32, i32, i32]
@@ -149,6 +151,14 @@ def load():
         raise HipEngineError("libqdiff_hip.so ABI version mismatch")
     _lib = lib
     return lib
+
+
+def has_pair_entries():
+    """The loaded library implements qd_attn_i8_qp and qd_conv_desc.res_period (they arrived together)."""
+    try:
+        return hasattr(load(), "qd_attn_i8_qp")
+    except (HipEngineError, OSError):
+        return False
 
 
 def available():
@@ -248,7 +258,7 @@ class ConvCall:
     """Python-side description of one qd_conv2d_i8 launch (tensors, not pointers)."""
     __slots__ = ("x", "w", "out", "bias", "rowbias", "residual", "ldx", "ldk", "ldo", "ldr", "ld_rowbias",
                  "B", "H", "W", "Ho", "Wo", "Cout", "kh", "kw", "stride", "pad_t", "pad_l", "wbits", "w_tiled", "segs",
-                 "epilogue", "oq_params", "oq_grid", "splitk", "heads", "gn_part", "upsample2x", "_keep")
+                 "epilogue", "oq_params", "oq_grid", "splitk", "heads", "gn_part", "upsample2x", "res_period", "_keep")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -330,6 +340,7 @@ def _conv_desc(c):
     if c.gn_part is not None:
         d.gn_ld = part_ld(c.gn_part)
     d.upsample2x = 1 if c.upsample2x else 0
+    d.res_period = int(c.res_period or 0)       # residual row period (qd_conv_desc.res_period): 0 = one residual row per output row
     d.nseg = len(c.segs)
     for i, s in enumerate(c.segs):
         g = d.seg[i]
@@ -650,20 +661,25 @@ def attn_workspace(device, BH, T, S, d):
 
 
 def attn_i8(q, k, vt, vsum, BH, H, T, S, d, Tpad, Spad, dpad, prm, wbits, wmin, wmax, q_asym, out, ldo,
-            out8=None, oq_params=None, oq_grid=None, kterm=None):
+            out8=None, oq_params=None, oq_grid=None, kterm=None, q_heads=None):
     """q_asym: the q quantiser has a non-zero stored zero point (the kernel restores -zq'*sum_d k' itself).
     out8 (+ oq_params, oq_grid): write the output as the int8 input rows of the consuming Linear instead of fp32.
     kterm: the table attn_keyterm built for this k operand (a caller with a static k — a prepared cross-attention context —
-    passes its own); None: built here when the head dim takes one."""
+    passes its own); None: built here when the head dim takes one.
+    q_heads: q holds that many heads only and head bh reads head bh % q_heads of it (qd_attn_i8_qp); None: one per head."""
     g = oq_grid
     if kterm is None and attn_uses_keyterm(d, S, q_asym):
         kterm = attn_keyterm(k, BH, Spad, dpad, prm)
     ws = attn_workspace(q.device, BH, T, S, d)
-    _check(load().qd_attn_i8(_ptr(q), _ptr(k), _ptr(vt), None, _ptr(kterm), _ptr(vsum), BH, H, T, S, d, Tpad, Spad,
-                             dpad, _ptr(prm), wbits, wmin, wmax, 1 if q_asym else 0, _ptr(out), ldo,
-                             _ptr(out8), out8.stride(0) if out8 is not None else 0, _ptr(_qp(oq_params)),
-                             g.qmin if g else 0, g.qmax if g else 0, g.off if g else 0,
-                             _ptr(ws), ws.numel() if ws is not None else 0, _stream()), "qd_attn_i8")
+    args = (_ptr(q), _ptr(k), _ptr(vt), None, _ptr(kterm), _ptr(vsum), BH, H, T, S, d, Tpad, Spad,
+            dpad, _ptr(prm), wbits, wmin, wmax, 1 if q_asym else 0, _ptr(out), ldo,
+            _ptr(out8), out8.stride(0) if out8 is not None else 0, _ptr(_qp(oq_params)),
+            g.qmin if g else 0, g.qmax if g else 0, g.off if g else 0,
+            _ptr(ws), ws.numel() if ws is not None else 0, _stream())
+    if q_heads is None:
+        _check(load().qd_attn_i8(*args), "qd_attn_i8")
+    else:
+        _check(load().qd_attn_i8_qp(*args, int(q_heads)), "qd_attn_i8_qp")
 
 
 def bmm_qk_i8(q8, k8, BH, T, S, d, Tpad, Spad, dpad, prm, out):

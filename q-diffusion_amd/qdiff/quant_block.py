@@ -248,13 +248,86 @@ def _ln_to(consumers, rows, M, C, ln):
     return engine.layernorm_quant(rows, M, C, ln, [m.conv_plan() for m in consumers])
 
 
-def _linear_rows(lin, rows, residual=None, gn_stats=False, slot=None):
-    """QuantModule linear on float rows [M,K] -> [M,N] (quantise + integer GEMM)."""
+def _linear_rows(lin, rows, residual=None, gn_stats=False, slot=None, res_period=0):
+    """QuantModule linear on float rows [M,K] -> [M,N] (quantise + integer GEMM).  res_period: see _period_rows."""
     lin._init_act_quantizers(rows)
     plan = lin.conv_plan()
     M, K = rows.shape
     xq = engine.quantize_rows(rows, plan, 1, K, M, (0, rows.stride(1), rows.stride(0)))
+    if res_period:
+        return _period_rows(plan, xq, M, residual, res_period, gn_stats, slot)
     return engine.conv_forward(plan, xq, 1, 1, M, 1, M, residual=residual, gn_stats=gn_stats, slot=slot)
+
+
+def _period_rows(plan, xq, M, residual, period, gn_stats=False, slot=None):
+    """Row GEMM on M int8 rows whose residual holds the first `period` rows only (the half of a guidance pair that was computed
+    once): output row m adds residual row m % period in the epilogue (qd_conv_desc.res_period), nothing is duplicated.  The
+    launch is M / period "samples" of `period` rows, so that the period is a whole number of them."""
+    return engine.conv_forward(plan, xq, M // period, 1, period, 1, period, residual=residual, gn_stats=gn_stats, slot=slot,
+                               res_period=period)
+
+
+def spatial_int_route(st):
+    """SpatialTransformer.forward takes its integer route (GroupNorm -> proj_in's rows, `+ x` in proj_out's epilogue).  The one
+    predicate: that forward and pair_stretch both ask it."""
+    return _int_mode(st.proj_in, st.proj_out) and not (st.proj_in.split or st.proj_out.split)
+
+
+def pair_stretch(unet, h, emb, context):
+    """n > 0: the walk may evaluate unet.input_blocks[1] on the first n = B / 2 samples of `h` (engine._PAIR: the halves of the
+    batch are equal) and fork at its cross-attention; 0: evaluate as always.  The stretch must start and end inside that one
+    block, before its output becomes a skip: a residual block without resampling followed by a SpatialTransformer of depth 1,
+    every layer of both on the integer route with its quantisers initialised — whatever the integer route refuses is refused
+    here, BEFORE anything ran at half batch."""
+    blocks = getattr(unet, "input_blocks", None)
+    if (not engine._PAIR[0] or blocks is None or len(blocks) < 2 or not torch.is_tensor(h) or h.dim() != 4 or h.shape[0] % 2
+            or not torch.is_tensor(emb) or emb.dim() != 2 or emb.shape[0] != h.shape[0]
+            or not torch.is_tensor(context) or context.dim() != 3 or context.shape[0] != h.shape[0] or engine.SIMULATE):
+        return 0
+    layers = list(blocks[1])
+    if len(layers) != 2:
+        return 0
+    res, st = layers
+    tbs = getattr(st, "transformer_blocks", None)
+    if (not isinstance(res, QuantResBlock) or tbs is None or len(tbs) != 1 or not isinstance(tbs[0], QuantBasicTransformerBlock)
+            or not all(hasattr(st, a) for a in ("norm", "proj_in", "proj_out"))
+            or getattr(st.forward, "__func__", None) is not ldm_unet.SpatialTransformer.forward):
+        return 0
+    B, C, H, W = h.shape
+    n = B // 2
+    # the routes' own predicates (the ones their forwards ask): whatever they refuse is refused here
+    if (res.updown or H != W or not res._int_route(H)
+            or not (isinstance(res.skip_connection, nn.Identity) or isinstance(res.skip_connection, QuantModule))):
+        return 0
+    if not spatial_int_route(st) or not tbs[0]._int_route():
+        return 0
+    qms = [m for m in blocks[1].modules() if isinstance(m, QuantModule)]
+    if not all(q.inited for m in qms for q in m._act_quantizers()):
+        return 0                                           # a data-dependent initialisation must see the whole batch
+    part = getattr(h, "qd_gn_part", None)
+    if part is not None and engine._part_view(part, B, H * W, C) is None:
+        return 0
+    return n
+
+
+def pair_block(blk, h, emb, context, n, out_slot=None):
+    """input_blocks[1] of a guidance pair (pair_stretch said n): the block sees views of the first n samples of h, of the
+    GroupNorm statistics that travel with h and of emb; its SpatialTransformer forks at the cross-attention (engine._PAIR_N) and
+    returns all 2n samples."""
+    B, C, H, W = h.shape
+    hn = h[:n]
+    part = engine._part_view(getattr(h, "qd_gn_part", None), B, H * W, C)
+    if part is not None:
+        hn.qd_gn_part = part[:n]
+    en = emb[:n]
+    en.qd_pair_of = emb                                    # EmbGroup: the rows of the launch all blocks share, not a launch of its own
+    engine._PAIR_N[0] = n
+    try:
+        out = blk(hn, en, context, out_slot=out_slot) if out_slot is not None else blk(hn, en, context)
+    finally:
+        engine._PAIR_N[0] = 0
+    engine._PAIR_TAKEN[0] = True
+    return out
 
 
 
@@ -280,6 +353,10 @@ class EmbGroup:
         self._emb, self._out = None, None
 
     def get(self, blk, emb):
+        base = getattr(emb, "qd_pair_of", None)
+        if base is not None:                             # the first rows of the embedding every other block receives (pair_block)
+            e = self.get(blk, base)
+            return None if e is None else e[:emb.shape[0]]
         if self._emb is not emb:
             self._emb, self._out = emb, None
             self._compute(emb)
@@ -356,6 +433,7 @@ class ContextKV:
         self.token = lambda: 0        # QuantModel installs its state token: a pin made under another token is stale
         self.chain_runs = 0           # how often the to_k / to_v chain was issued (tests: a prepared context must not add to it)
         self.value_matches = 0        # prepared contexts recognised by VALUE (a fresh tensor with the pinned bytes)
+        self.probe_flags = None       # answers to the `probe` of the last match() that read flags back (None: it did not)
 
     # ---- operands prepared ONCE per sampling run (QuantModel.prepare_context, or on first sight: QuantModel.forward) --------
     # The reference recomputes k = to_k(context), v = to_v(context) in every evaluation (quant_block.py:193-195) although the
@@ -373,9 +451,11 @@ class ContextKV:
             self._pins = [e for e in self._pins if e["token"] == tok or e["locked"]]
         return tok
 
-    def match(self, context, by_value=True):
+    def match(self, context, by_value=True, probe=None):
         """The entry prepared for `context`, or None.  by_value=False: identity + in-place version only (no device read-back:
-        usable under stream capture)."""
+        usable under stream capture).  probe: a callable returning 0-dim bool device tensors of the caller's own; they are
+        evaluated only when this call reads flags back anyway and travel in that ONE read-back (answers: self.probe_flags)."""
+        self.probe_flags = None
         if not self._pins or not torch.is_tensor(context):
             return None
         tok = self._live()
@@ -392,9 +472,14 @@ class ContextKV:
         if context.is_cuda:
             if torch.cuda.is_current_stream_capturing():
                 return None
-            flags = torch.stack([(context == e["copy"]).all() for e in cands]).tolist()      # ONE read-back for all slots
+            extra = list(probe()) if probe is not None else []
+            flags = torch.stack([(context == e["copy"]).all() for e in cands] + extra).tolist()      # ONE read-back for all slots
+            if extra:
+                flags, self.probe_flags = flags[:len(cands)], flags[len(cands):]
         else:
             flags = [torch.equal(context, e["copy"]) for e in cands]
+            if probe is not None:
+                self.probe_flags = [bool(f) for f in probe()]
         for e, same in zip(cands, flags):
             if same:
                 self.value_matches += 1
@@ -704,13 +789,18 @@ class QuantResBlock(BaseQuantBlock, ldm_unet.TimestepBlock):
         assert x.shape[2] == x.shape[3]
         H_ = x.shape[2]
         conv1, conv2 = self.in_layers[-1], self.out_layers[-1]
-        if (_int_mode(conv1, conv2, self.emb_layers[-1]) and conv1.split == 0 and conv2.split == 0 and not _dropout_live(self)
-                and (not self.updown or (H_ % 2 == 0 and not getattr(self.h_upd, "use_conv", False)))):
+        if self._int_route(H_):
             return self._forward_int(x, emb, split, conv1, conv2, out_slot)
         kind = self._wonly_route(x, emb, conv1, conv2)
         if kind is not None:
             return self._forward_wonly(x, emb, split, conv1, conv2, kind)
         return self._forward_sim(x, emb, split)
+
+    def _int_route(self, H_):
+        """This call (maps of H_ x H_) takes _forward_int.  The one predicate: _forward and pair_stretch both ask it."""
+        conv1, conv2 = self.in_layers[-1], self.out_layers[-1]
+        return (_int_mode(conv1, conv2, self.emb_layers[-1]) and conv1.split == 0 and conv2.split == 0 and not _dropout_live(self)
+                and (not self.updown or (H_ % 2 == 0 and not getattr(self.h_upd, "use_conv", False))))
 
     def _wonly_resample(self):
         """0: no `updown`; 1: h_upd / x_upd are the 2x2 average (Downsample without convolution); 2: nearest 2x (Upsample
@@ -1166,11 +1256,13 @@ class QuantBasicTransformerBlock(BaseQuantBlock, _AttnQuant):
             att.forward = MethodType(cross_attn_forward, att)
             att.use_act_quant = False
 
-    def forward(self, x, context=None, out_plan=None):
+    def forward(self, x, context=None, out_plan=None, pair=False):
         """out_plan (engine-internal, optional): ConvPlan of the module that consumes this block's output and nothing
         else (SpatialTransformer.proj_out).  When the block runs on the integer path and the shape allows it, the FF
-        output GEMM then returns that consumer's int8 input rows [B*T][ldx] instead of the fp32 tokens."""
-        return self._forward(x, context, out_plan)
+        output GEMM then returns that consumer's int8 input rows [B*T][ldx] instead of the fp32 tokens.
+        pair (engine-internal): x holds the first half of a guidance pair's batch, context the whole batch: the block forks at
+        the cross-attention and returns the rows of both halves (integer path only; pair_stretch checked it)."""
+        return self._forward(x, context, out_plan, pair)
 
     def set_quant_state(self, weight_quant: bool = False, act_quant: bool = False):
         self.attn1.use_act_quant = act_quant
@@ -1180,15 +1272,22 @@ class QuantBasicTransformerBlock(BaseQuantBlock, _AttnQuant):
     def _attn_inited(self, att):
         return _aq_ready(att.act_quantizer_q, att.act_quantizer_k, att.act_quantizer_v, att.act_quantizer_w)
 
-    def _forward(self, x, context=None, out_plan=None):
-        if context is None and isinstance(x, (tuple, list)):
-            x, context = x
+    def _int_route(self):
+        """This call takes _forward_int.  The one predicate: _forward and pair_stretch both ask it."""
         a1, a2 = self.attn1, self.attn2
         mods = [a1.to_q, a1.to_k, a1.to_v, a1.to_out[0], a2.to_q, a2.to_k, a2.to_v, a2.to_out[0], self.ff.net[-1]]
         glu = isinstance(self.ff.net[0], ldm_unet.GEGLU) or type(self.ff.net[0]).__name__ == "GEGLU"
-        if (glu and a1.use_act_quant and a2.use_act_quant and not _dropout_live(self) and _int_mode(*mods, self.ff.net[0].proj)
-                and self._attn_inited(a1) and self._attn_inited(a2)):
-            return self._forward_int(x, context, out_plan)
+        return bool(glu and a1.use_act_quant and a2.use_act_quant and not _dropout_live(self) and _int_mode(*mods, self.ff.net[0].proj)
+                    and self._attn_inited(a1) and self._attn_inited(a2))
+
+    def _forward(self, x, context=None, out_plan=None, pair=False):
+        if context is None and isinstance(x, (tuple, list)):
+            x, context = x
+        glu = isinstance(self.ff.net[0], ldm_unet.GEGLU) or type(self.ff.net[0]).__name__ == "GEGLU"
+        if self._int_route():
+            return self._forward_int(x, context, out_plan, pair)
+        if pair:
+            raise engine.hip.HipEngineError("a guidance pair reached a transformer block that is not on the integer path")
         if glu and self._wonly_fusable(x, context):
             return self._forward_wonly(x, context)
         x = self.attn1(self.norm1(x)) + x
@@ -1282,10 +1381,14 @@ class QuantBasicTransformerBlock(BaseQuantBlock, _AttnQuant):
         engine.wonly_count("transformer")
         return rows.view(B, T, C)
 
-    def _attn_int(self, att, rows, B, T, C, ln, ctx_rows, S, kv=None, pre_attention=None):
+    def _attn_int(self, att, rows, B, T, C, ln, ctx_rows, S, kv=None, pre_attention=None, pair=False):
         """norm -> q/k/v projections -> fused quantised attention -> to_out (+ residual rows).
-        kv: (k8, v8, vsum, kterm) prepared ahead of time for this block's context (ContextKV), else they are computed here."""
+        kv: (k8, v8, vsum, kterm) prepared ahead of time for this block's context (ContextKV), else they are computed here.
+        pair: the fork of a guidance pair (cross-attention only).  `rows` are the B samples both halves share, the context holds
+        Bk = 2 B samples: the norm and to_q run on B, the attention on Bk with the query heads of B (qd_attn_i8_qp), to_out on
+        Bk * T rows adding residual row m % (B * T); returns the Bk * T rows."""
         h = att.heads
+        Bk = 2 * B if pair else B
         ap = self._attn_plan(att, float(att.scale), 1.0, rows.device)
         if ctx_rows is None:
             xq, xk, xv = _ln_to([att.to_q, att.to_k, att.to_v], rows, B * T, C, ln)
@@ -1296,23 +1399,26 @@ class QuantBasicTransformerBlock(BaseQuantBlock, _AttnQuant):
         inner = att.to_q.conv_plan().Cout
         d = inner // h
         q8, k8, v8, vsum = engine.head_buffers(rows.device, B * h, T, S, d)
+        if pair and kv is None:
+            _, k8, v8, vsum = engine.head_buffers(rows.device, Bk * h, T, S, d)
         if kv is None:
             vsum = engine.vsum_slice(id(att), rows.device, tuple(vsum.shape))   # this block's own slice of the per-evaluation arena
         kterm = None
         if kv is not None:
             k8, v8, vsum, kterm = kv
-            if k8.shape[0] != B * h or v8.shape[0] != B * h:
+            if k8.shape[0] != Bk * h or v8.shape[0] != Bk * h:
                 # prepared / branch operands of another batch size (a prepared context handed to a latent batch it was not made for)
-                raise engine.hip.HipEngineError(f"cross-attention operands were prepared for {k8.shape[0] // h} samples, the latents have {B}")
+                raise engine.hip.HipEngineError(f"cross-attention operands were prepared for {k8.shape[0] // h} samples, the latents have {Bk}")
 
         def operand(mod, codes, which, n_tok, buf):
             # projection -> attention operand bytes: inside the GEMM epilogue when the shape allows it, else
             # fp32 projection + qd_quantize_heads (ragged token counts; the 77 context tokens of cross-attention)
+            Bo = B if which == 0 else Bk                # (a pair: q of the shared samples, k / v of every sample's context)
             if codes is not None and engine.heads_fusable(mod.conv_plan(), n_tok, h):
-                engine.project_heads(mod.conv_plan(), codes, B, n_tok, h, ap, which, buf, vsum)
+                engine.project_heads(mod.conv_plan(), codes, Bo, n_tok, h, ap, which, buf, vsum)
                 return
-            y = mod.forward_codes(codes, 1, 1, B * n_tok) if codes is not None else _linear_rows(mod, ctx_rows)
-            engine.heads_from_float(ap, which, y, B, n_tok, h, d, (n_tok * inner, inner, d, 1), buf, vsum)
+            y = mod.forward_codes(codes, 1, 1, Bo * n_tok) if codes is not None else _linear_rows(mod, ctx_rows)
+            engine.heads_from_float(ap, which, y, Bo, n_tok, h, d, (n_tok * inner, inner, d, 1), buf, vsum)
 
         if (kv is None and ctx_rows is None
                 and all(engine.heads_fusable(m.conv_plan(), T, h) for m in (att.to_q, att.to_k, att.to_v))):
@@ -1327,15 +1433,20 @@ class QuantBasicTransformerBlock(BaseQuantBlock, _AttnQuant):
         if pre_attention is not None:
             pre_attention()                     # the next launch on this stream is the attention kernel
         out_lin = att.to_out[0]
+        qkw = {"q_heads": B * h} if pair else {}      # (only a pair names the period: every other call is the one it always was)
         if out_lin.act_quantizer.inited and out_lin.conv_plan().ldx == inner and len(out_lin.conv_plan().segs) == 1:
             # the attention epilogue quantises its output for to_out[0]: no fp32 round trip
-            o8 = engine.attention_codes(ap, q8, k8, v8, vsum, B, T, S, h, d, out_plan=out_lin.conv_plan(), kterm=kterm)
+            o8 = engine.attention_codes(ap, q8, k8, v8, vsum, Bk, T, S, h, d, out_plan=out_lin.conv_plan(), kterm=kterm, **qkw)
+            if pair:
+                return _period_rows(out_lin.conv_plan(), o8, Bk * T, rows, B * T)
             return out_lin.forward_codes(o8, 1, 1, B * T, residual=rows)
-        o = engine.attention_codes(ap, q8, k8, v8, vsum, B, T, S, h, d, kterm=kterm)
-        return _linear_rows(out_lin, o, residual=rows)
+        o = engine.attention_codes(ap, q8, k8, v8, vsum, Bk, T, S, h, d, kterm=kterm, **qkw)
+        return _linear_rows(out_lin, o, residual=rows, res_period=B * T if pair else 0)
 
-    def _forward_int(self, x, context, out_plan=None):
+    def _forward_int(self, x, context, out_plan=None, pair=False):
         B, T, C = x.shape
+        if pair and (context is None or context.shape[0] != 2 * B):
+            raise engine.hip.HipEngineError("a guidance pair needs a context of twice the batch of its shared rows")
         rows = x.reshape(B * T, C)
         if rows.stride(1) != 1 or rows.stride(0) != C:
             rows = rows.contiguous()
@@ -1349,10 +1460,12 @@ class QuantBasicTransformerBlock(BaseQuantBlock, _AttnQuant):
             kv = grp.get(self, context) if grp is not None else None
             ctx = None
             if kv is None:
-                ctx = context.reshape(B * S, context.shape[2]).float()
+                ctx = context.reshape(context.shape[0] * S, context.shape[2]).float()
                 if ctx.stride(1) != 1:
                     ctx = ctx.contiguous()
-            rows = self._attn_int(self.attn2, rows, B, T, C, self.norm2, ctx if kv is None else rows, S, kv=kv)
+            rows = self._attn_int(self.attn2, rows, B, T, C, self.norm2, ctx if kv is None else rows, S, kv=kv, pair=pair)
+            if pair:
+                B = 2 * B                                  # forked: from here on every sample has rows of its own
         return self._ff_int(rows, B, T, C, out_plan)
 
     def _ff_int(self, rows, B, T, C, out_plan=None):

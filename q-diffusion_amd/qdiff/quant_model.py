@@ -50,6 +50,7 @@ class QuantModel(nn.Module):
         self._graph_after, self._graph_seen, self._graph_tok = 1, {}, None
         self._own_hooks = self._hook_census()           # a replayed graph runs no Python: foreign forward hooks keep the model eager
         self._quant_state = (False, False)
+        self.pair_evals = 0                             # evaluations whose shared stretch ran once for both halves of a guidance pair
         import weakref
         weakref.finalize(self, engine.release_model, id(self))      # the per-model V-sum arena dies with the model
 
@@ -370,6 +371,7 @@ class QuantModel(nn.Module):
             tok = self._state_token()
         entry = None
         graphs = self._graphs is not None and tok >= 0 and cuda and torch.is_tensor(timesteps)
+        hooks_own = None                                   # "no foreign hook below the model": counted at most once per evaluation
         if graphs:
             from .graph import GraphedUNet, signature
             if self._graph_tok != tok:                     # plans were rebuilt: the captured pointers are stale
@@ -379,19 +381,43 @@ class QuantModel(nn.Module):
                 self.__dict__["_hook_tables"] = None
             # a replay runs no Python: with a foreign hook below the model (calibration capture, recorders — registered at any
             # time, also AFTER a graph of this signature was captured) the evaluation stays eager
-            graphs = self._hook_census(refresh=False) == self._own_hooks
+            hooks_own = self._hook_census(refresh=False) == self._own_hooks
+            graphs = hooks_own
+        # A classifier-free-guidance pair (engine.mark_pair): the halves of x and of timesteps are equal, so the walk evaluates what
+        # they share once.  Candidates only: integer state, even batch, a context of the same batch, the knob, no foreign hook
+        # (a hooked module must keep seeing the calls it always saw).
+        pair = 0
+        cand = (tok >= 0 and engine.CFG_SHARE and torch.is_tensor(x) and torch.is_tensor(timesteps) and torch.is_tensor(context)
+                and x.dim() == 4 and x.shape[0] >= 2 and x.shape[0] % 2 == 0 and timesteps.dim() == 1
+                and timesteps.shape[0] == x.shape[0] and context.dim() == 3 and context.shape[0] == x.shape[0]
+                and x.device == timesteps.device == context.device and engine.pair_entries_ok(x))
+        if cand:
+            if hooks_own is None:                          # (graph replay off: the census was not taken above)
+                if self.__dict__.get("_pair_tok") != tok:
+                    self.__dict__["_pair_tok"], self.__dict__["_hook_tables"] = tok, None
+                hooks_own = self._hook_census(refresh=False) == self._own_hooks
+            cand = hooks_own
+        if cand and engine.pair_marked(x, timesteps):
+            pair = 1
         if tok >= 0 and ckv is not None and torch.is_tensor(context) and qb._CTX_PIN:
             # the run's conditioning: prepared before (same tensor, or the same BYTES in a fresh tensor), or prepared now
             entry = ckv.match(context, by_value=False)
             if entry is None:
-                entry = ckv.match(context)
+                # an unmarked caller (the unmodified sampler builds fresh tensors at every step): when this match reads flags
+                # back anyway, "the halves are equal" rides in the same read-back; never a read-back of its own
+                n = x.shape[0] // 2 if cand else 0
+                probe = (lambda: [(x[:n] == x[n:]).all(), (timesteps[:n] == timesteps[n:]).all()]) if (cand and not pair) else None
+                entry = ckv.match(context, probe=probe)
+                if probe is not None and ckv.probe_flags is not None and all(ckv.probe_flags):
+                    pair = 1
             if entry is None and qb._CTX_AUTO:
                 entry = self._prepare(context)
         if ckv is not None:
             ckv.select(entry, context)
+        engine._PAIR[0], engine._PAIR_TAKEN[0] = pair, False
         try:
             if graphs:
-                key = signature(x, timesteps, context) + (engine.STREAM_DTYPE, None if entry is None else entry["slot"])
+                key = signature(x, timesteps, context) + (engine.STREAM_DTYPE, None if entry is None else entry["slot"], pair)
                 g = self._graphs.get(key)
                 if g is None:
                     if len(self._graph_seen) > 256:
@@ -409,11 +435,15 @@ class QuantModel(nn.Module):
                         if pool is None:
                             pool = self.__dict__["_graph_pool"] = torch.cuda.graph_pool_handle()
                         g = self._graphs[key] = GraphedUNet(self, x, timesteps, context, pinned=entry is not None, pool=pool)
+                        g.pair_taken = engine._PAIR_TAKEN[0]       # the captured walk shared the stretch: so does every replay
                         logger.info("HIP graph captured for signature %s (%d kept)", key[:5], len(self._graphs))
                 if g is not None:
+                    self.pair_evals += 1 if g.pair_taken else 0
                     return g(x, timesteps, context).to(x.dtype, copy=True)
             y = self.model(x, timesteps, context)
+            self.pair_evals += 1 if engine._PAIR_TAKEN[0] else 0
         finally:
+            engine._PAIR[0] = 0
             if ckv is not None:
                 ckv.select(None, None)
         # an fp16 activation stream ends here: the samplers' update arithmetic runs in the latent's own type

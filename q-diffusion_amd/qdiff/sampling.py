@@ -96,8 +96,18 @@ def guided_eps(unet, x, t, cond, uncond, scale, ctx2=None):
     ctx2: `torch.cat([uncond, cond])` made once by the caller (see guidance_context) instead of at every step."""
     if uncond is None or scale == 1.0:
         return unet(x, t, cond)
-    e_u, e_c = unet(torch.cat([x] * 2), torch.cat([t] * 2), ctx2 if ctx2 is not None else torch.cat([uncond, cond])).chunk(2)
+    x_in, t_in = _doubled(x, t)
+    e_u, e_c = unet(x_in, t_in, ctx2 if ctx2 is not None else torch.cat([uncond, cond])).chunk(2)
     return e_u + scale * (e_c - e_u)
+
+
+def _doubled(x, t):
+    """torch.cat([x] * 2), torch.cat([t] * 2) of a guidance pair (plms.py:184-186), announced to the engine: both halves of the
+    batch are the same samples, so a qdiff.QuantModel evaluates what they share once (engine.mark_pair; no device work)."""
+    from . import engine
+    x_in, t_in = torch.cat([x] * 2), torch.cat([t] * 2)
+    engine.mark_pair(x_in, t_in)
+    return x_in, t_in
 
 
 def guidance_context(unet, cond, uncond, scale):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Steady-state per-kernel breakdown of ONE UNet evaluation (eager launches, GPU kept busy so kernels run back to back).
 
-  step 1 (under rocprofv3 --kernel-trace):  python tools/eval_breakdown.py run [sd|ldm|cifar] [n images] [evals] [graph] [pin]
+  step 1 (under rocprofv3 --kernel-trace):  python tools/eval_breakdown.py run [sd|ldm|cifar] [n images] [evals] [graph] [pin] [pair]
   step 2:                                   python tools/eval_breakdown.py join results.db [evals]
 
 The measured evaluations are bracketed by two spin kernels (torch.cuda._sleep), which `join` looks for in the trace;
@@ -16,7 +16,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run(kind, n, evals, graph=False, pin=False):
+def run(kind, n, evals, graph=False, pin=False, pair=False):
     import torch
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "q-diffusion_amd"))
@@ -26,6 +26,12 @@ def run(kind, n, evals, graph=False, pin=False):
     qnn, _ = bench.build_quantised_unet(kind, dev)
     x, t, c = synthetic.synthetic_inputs(kind, 2 * n if kind == "sd" else n)
     args = [a.to(dev) for a in (x, t, c) if a is not None]
+    if pair and kind == "sd":
+        # what a sampler evaluates under classifier-free guidance: both halves of the batch hold the same n samples, announced
+        # to the engine (QDIFF_CFG_SHARE=0 keeps the evaluation unshared on the same inputs)
+        from qdiff import engine
+        args[0], args[1] = torch.cat([args[0][:n]] * 2), torch.cat([args[1][:n]] * 2)
+        engine.mark_pair(args[0], args[1])
     if pin and len(args) > 2:
         with torch.no_grad():
             qnn(*args)                       # plans, packs
@@ -120,6 +126,6 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1] == "run":
         run(sys.argv[2] if len(sys.argv) > 2 else "sd", int(sys.argv[3]) if len(sys.argv) > 3 else 8,
-            int(sys.argv[4]) if len(sys.argv) > 4 else 3, graph="graph" in sys.argv, pin="pin" in sys.argv)
+            int(sys.argv[4]) if len(sys.argv) > 4 else 3, graph="graph" in sys.argv, pin="pin" in sys.argv, pair="pair" in sys.argv)
     else:
         join(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 3)
