@@ -531,7 +531,8 @@ int qd_rows_to_h16(const void* x, int x_dtype, int64_t B, int64_t C, int64_t S, 
  *                    element strides (sb, s_token, sh, sd); sd must be 1 and every run of 8 channels 16-byte aligned
  *                    (16-byte aligned bases, the other strides multiples of 16 bytes' worth of elements).  Values are rounded
  *                    to op_dtype (QD_F16 / QD_BF16, nearest even) when a tile is staged.
- *         d          a multiple of 8 in [8, 160]; any T >= 1, S >= 1; no mask.  scale > 0.
+ *         d          a multiple of 8 in [8, 256]; any T >= 1, S >= 1; no mask.  scale > 0.  Head dims above 160 (the one-head
+ *                    attention of the DDIM UNet) run one wave per SIMD.
  *         out        merged-head rows out[b*T + t][h*d + c], out_dtype QD_F32 or QD_F16, row stride ldo (>= H*d, a multiple
  *                    of 4 elements, out aligned to 4 elements).
  *         Scores accumulate in fp32 (v_mfma_f32_32x32x16_{f16,bf16}), the softmax runs in fp32 (exp2 with scale*log2 e

@@ -111,8 +111,11 @@ __device__ __forceinline__ int ah_vpos(int kk) {
     return 16 * s + 8 * ((rem >> 2) & 1) + 4 * (rem >> 3) + (rem & 3);
 }
 
+// Head dims up to 160 (DK <= 10) run two blocks per CU.  The wide ones (DK = 11 .. 16, d = 168 .. 256: the one-head attention of the
+// DDIM UNet) fill the register file at one wave per SIMD — the query fragment is 4 DK registers, the O^T tiles
+// 16 NT — hence the launch bounds; the body is the same.
 template <bool BF, int DK, int DT>
-__global__ __launch_bounds__(256, 2) void attn_h16_kernel(const AttnH p) {
+__global__ __launch_bounds__(256, DK > 10 ? 1 : 2) void attn_h16_kernel(const AttnH p) {
     constexpr int NT = (DK + 1) / 2;                           // 32-channel output tiles
     constexpr int KC = 2 * DK + 1;                             // 16-byte chunks per K row (odd: conflict-free reads)
     constexpr int VC = 5;                                      // 16-byte chunks per V^T row (32 keys = 4, + 1)
@@ -286,6 +289,7 @@ void launch_h16(const AttnH& a, int DK, dim3 grid, hipStream_t st) {
     switch (DK) {
 #define QD_AH(N) case N: hipLaunchKernelGGL((attn_h16_kernel<BF, N, DT>), grid, dim3(256), 0, st, a); break;
         QD_AH(1) QD_AH(2) QD_AH(3) QD_AH(4) QD_AH(5) QD_AH(6) QD_AH(7) QD_AH(8) QD_AH(9) QD_AH(10)
+        QD_AH(11) QD_AH(12) QD_AH(13) QD_AH(14) QD_AH(15) QD_AH(16)
 #undef QD_AH
     }
 }
@@ -314,7 +318,7 @@ extern "C" int qd_attn_h16(const void* q, const void* k, const void* v, int in_d
     QD_REQUIRE(op_dtype == QD_F16 || op_dtype == QD_BF16, "qd_attn_h16: op_dtype must be f16/bf16 (got %d)", op_dtype);
     QD_REQUIRE(out_dtype == QD_F32 || out_dtype == QD_F16, "qd_attn_h16: out_dtype must be f32/f16 (got %d)", out_dtype);
     QD_REQUIRE(B > 0 && T > 0 && S > 0 && H > 0, "qd_attn_h16: bad shape B=%d T=%d S=%d H=%d", B, T, S, H);
-    QD_REQUIRE(d >= 8 && d <= 160 && d % 8 == 0, "qd_attn_h16: head dim %d unsupported (a multiple of 8 in [8, 160])", d);
+    QD_REQUIRE(d >= 8 && d <= 256 && d % 8 == 0, "qd_attn_h16: head dim %d unsupported (a multiple of 8 in [8, 256])", d);
     QD_REQUIRE(std::isfinite(scale) && scale > 0.f, "qd_attn_h16: scale must be finite and positive");
     QD_REQUIRE(ldo >= (int64_t)H * d && ldo % 4 == 0 && qd_aligned(out, out_dtype == QD_F32 ? 16 : 8),
                "qd_attn_h16: ldo must be >= H*d and a multiple of 4, out aligned to 4 elements");

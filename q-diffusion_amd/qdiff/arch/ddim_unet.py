@@ -304,6 +304,8 @@ class Model(nn.Module):
             rows = qb._nhwc_rows(h)
             xq = qb._gn_silu_to(conv, rows, B, H * W, C, self.norm_out)
             return qb._rows_to_nchw(conv.forward_codes(xq, B, H, W), B, H, W)
+        if engine.WEIGHT_ONLY_FUSE_DDIM and qb.ddim_head_wonly(self, h):
+            return qb.ddim_head_forward_wonly(self, h)      # weights-only state: the same one-producer head on 16-bit operand rows
         if h.dtype != torch.float32:
             h = h.float()                                   # fp16 activation stream: the torch output head runs on fp32
         return self.conv_out(nonlinearity(self.norm_out(h)))

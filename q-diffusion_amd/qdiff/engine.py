@@ -748,6 +748,24 @@ def wonly_mod_state():
     return WEIGHT_ONLY_FUSE_MOD and wonly_fuse_state()
 
 
+# DDIM family, on top of WEIGHT_ONLY_FUSE (effective only while wonly_fuse_state() holds): False (default) = a
+# weights-only QuantResnetBlock / QuantAttnBlock and the DDIM output head keep the reference's composition; True = they run
+# QuantResnetBlock._forward_wonly / QuantAttnBlock._forward_wonly / the fused head of arch.ddim_unet.Model.forward.  WONLY_FUSED
+# gets the keys "resnetblock", "attnblock_ddim" and "head_ddim" when a forward takes the route, never while the knob is off.
+# QDIFF_WEIGHT_ONLY_FUSE_DDIM=1, or engine.set_weight_only_fusion_ddim().
+WEIGHT_ONLY_FUSE_DDIM = _parse_flag(os.environ.get("QDIFF_WEIGHT_ONLY_FUSE_DDIM"), "QDIFF_WEIGHT_ONLY_FUSE_DDIM")
+
+
+def set_weight_only_fusion_ddim(on):
+    """True / False (or the strings QDIFF_WEIGHT_ONLY_FUSE_DDIM accepts)."""
+    _set_flag("WEIGHT_ONLY_FUSE_DDIM", on, "weight-only fusion of the DDIM blocks")
+
+
+def wonly_ddim_state():
+    """The routes of the DDIM blocks engage: the knob, and everything wonly_fuse_state() asks."""
+    return WEIGHT_ONLY_FUSE_DDIM and wonly_fuse_state()
+
+
 def wonly_count(kind):
     """One more block forward of `kind` on a fused route (a default: tests replace WONLY_FUSED by a dict without the new keys)."""
     WONLY_FUSED[kind] = WONLY_FUSED.get(kind, 0) + 1
@@ -869,6 +887,16 @@ def set_weight_only_attention(dtype):
 def wonly_attn_shape_ok(d):
     """qd_attn_h16 covers head dims that are multiples of 8 in [8, 160] (any token counts)."""
     return d % 8 == 0 and WONLY_ATTN_DMIN <= d <= WONLY_ATTN_DMAX
+
+
+# head dims the kernel takes on the DDIM route (QuantAttnBlock._forward_wonly: one head as wide as the layer)
+WONLY_ATTN_WIDE_DMAX = 256
+
+
+def wonly_attn_wide_shape_ok(d):
+    """qd_attn_h16 covers head dims that are multiples of 8 in [8, 256]; asked by the DDIM route only (wonly_attn_shape_ok keeps
+    the range of the routes that came before it)."""
+    return d % 8 == 0 and WONLY_ATTN_DMIN <= d <= WONLY_ATTN_WIDE_DMAX
 
 
 def _attn_h16_operand(x, B, N, H, d, strides, dtype):

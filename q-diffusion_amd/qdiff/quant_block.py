@@ -1512,6 +1512,8 @@ class QuantResnetBlock(BaseQuantBlock):
             x, temb = x
         if _int_mode(self.conv1, self.conv2, self.temb_proj) and not _dropout_live(self):
             return self._forward_int(x, temb, split, out_slot)
+        if self._wonly_route(x, temb):
+            return self._forward_wonly(x, temb, split)
         h = self.conv1(ddim_unet.nonlinearity(self.norm1(x)))
         h = h + self.temb_proj(ddim_unet.nonlinearity(temb))[:, :, None, None]
         h = ddim_unet.nonlinearity(self.norm2(h))
@@ -1521,6 +1523,46 @@ class QuantResnetBlock(BaseQuantBlock):
         if self.in_channels != self.out_channels:
             x = self.conv_shortcut(x) if self.use_conv_shortcut else self.nin_shortcut(x, split=split)
         return x + h
+
+    def _wonly_route(self, x, temb):
+        """This call takes _forward_wonly (engine.WEIGHT_ONLY_FUSE_DDIM on top of engine.WEIGHT_ONLY_FUSE): everything
+        _wonly_fuse_gate demands of the two 3x3 convolutions, two nn.GroupNorms, and both convolutions reading all their
+        channels (a multiple of 8: wonly_plain_plan) as one segment, keeping the map size and giving out_channels."""
+        if not engine.WEIGHT_ONLY_FUSE_DDIM or not torch.is_tensor(x) or x.dim() != 4:
+            return False
+        if not (isinstance(self.norm1, nn.GroupNorm) and isinstance(self.norm2, nn.GroupNorm)):
+            return False
+        conv1, conv2 = self.conv1, self.conv2
+        if not _wonly_fuse_gate(self, (conv1, conv2), (x, temb)):
+            return False
+        p1, p2 = conv1.wonly_plan(), conv2.wonly_plan()          # (not None: _wonly_fuse_gate asked wonly_ready())
+        H, W = x.shape[2], x.shape[3]
+        return (conv1.kind == 'conv2d' and conv2.kind == 'conv2d' and engine.wonly_plain_plan(p1, x.shape[1])
+                and engine.wonly_plain_plan(p2, self.out_channels) and p1.Cout == self.out_channels and p2.Cout == self.out_channels
+                and engine.conv_out_hw(H, W, p1) == (H, W) and engine.conv_out_hw(H, W, p2) == (H, W))
+
+    def _forward_wonly(self, x, temb, split):
+        """Reference :318-338 in the weights-only state (the plain kind of QuantResBlock._forward_wonly): norm1 . swish ->
+        operand rows of conv1; conv1 with the embedding projection as a row bias; norm2 . swish -> operand rows of conv2; conv2
+        with the skip rows as the residual of its epilogue.  temb_proj and the shortcut (nin_shortcut with its two-segment
+        split, or conv_shortcut) keep their own module calls."""
+        B, C, H, W = x.shape
+        S = H * W
+        conv1, conv2 = self.conv1, self.conv2
+        rows = _nhwc_rows(x)
+        xh = engine.wonly_groupnorm_rows(rows, B, S, C, self.norm1, True, conv1.wonly_plan())
+        e = self.temb_proj(ddim_unet.nonlinearity(temb)).float()
+        if e.stride(1) != 1:
+            e = e.contiguous()
+        h = conv1.forward_rows(xh, B, H, W, rowbias=e)
+        hh = engine.wonly_groupnorm_rows(h, B, S, self.out_channels, self.norm2, True, conv2.wonly_plan())
+        if self.in_channels != self.out_channels:
+            res = _nhwc_rows(self.conv_shortcut(x) if self.use_conv_shortcut else self.nin_shortcut(x, split=split))
+        else:
+            res = rows
+        out = conv2.forward_rows(hh, B, H, W, residual=res)
+        engine.wonly_count("resnetblock")
+        return _rows_to_nchw(out, B, H, W)
 
     def _skip_plan(self, split, C):
         """see QuantResBlock._skip_plan: the 1x1 `nin_shortcut` reads the tensor norm1 normalises"""
@@ -1578,6 +1620,8 @@ class QuantAttnBlock(BaseQuantBlock, _AttnQuant):
         if (self.use_act_quant and _int_mode(self.q, self.k, self.v, self.proj_out)
                 and _aq_ready(self.act_quantizer_q, self.act_quantizer_k, self.act_quantizer_v, self.act_quantizer_w)):
             return self._forward_int(x, out_slot)
+        if self._wonly_route(x):
+            return self._forward_wonly(x)
         hn = self.norm(x)
         q, k, v = self.q(hn), self.k(hn), self.v(hn)
         b, c, h, w = q.shape
@@ -1592,6 +1636,52 @@ class QuantAttnBlock(BaseQuantBlock, _AttnQuant):
             v, w_ = self.act_quantizer_v(v), self.act_quantizer_w(w_)
         out = th.bmm(v, w_).reshape(b, c, h, w)
         return x + self.proj_out(out)
+
+    def _wonly_route(self, x):
+        """This call takes _forward_wonly (engine.WEIGHT_ONLY_FUSE_DDIM on top of engine.WEIGHT_ONLY_FUSE): no activation
+        quantisation in the block, everything _wonly_fuse_gate demands of q / k / v / proj_out, an nn.GroupNorm, four one-tap
+        stride-1 layers that read the C channels (a multiple of 8) as one plain segment and give C back, and q, k, v agreeing on
+        the layout and type of their operand rows (they share ONE buffer)."""
+        if not engine.WEIGHT_ONLY_FUSE_DDIM or self.use_act_quant or not torch.is_tensor(x) or x.dim() != 4:
+            return False
+        if not isinstance(self.norm, nn.GroupNorm):
+            return False
+        layers = (self.q, self.k, self.v, self.proj_out)
+        if not _wonly_fuse_gate(self, layers, (x,)):
+            return False
+        C = x.shape[1]
+        plans = [m.wonly_plan() for m in layers]                 # (not None: _wonly_fuse_gate asked wonly_ready())
+        one_tap = lambda p: (p.kh, p.kw, p.stride, p.pad) == (1, 1, 1, 0)
+        pq = plans[0]
+        return (all(one_tap(p) and engine.wonly_plain_plan(p, C) and p.Cout == C for p in plans)
+                and all(p.ldx == pq.ldx and p.act_dtype == pq.act_dtype for p in plans[1:3]))
+
+    def _forward_wonly(self, x):
+        """Reference :356-386 in the weights-only state: ONE qd_groupnorm_h16 (no SiLU) writes the operand rows q, k and v
+        read; the attention is qd_attn_h16 with one head as wide as the layer under engine.WEIGHT_ONLY_ATTN (q / k / v then
+        fp16 rows when that is the operand type, and the kernel writes proj_out's fp16 operand rows itself when the layouts
+        agree), else — also for a width engine.wonly_attn_wide_shape_ok refuses — the library bmm / softmax / bmm on the fp32
+        projections; proj_out adds x's rows in its epilogue."""
+        B, C, H, W = x.shape
+        T, M = H * W, B * H * W
+        rows, xh = _wide_front(x, self.norm, self.q)
+        fused = engine.WEIGHT_ONLY_ATTN is not None and engine.wonly_attn_wide_shape_ok(C)
+        qdt = torch.float16 if fused and engine.WEIGHT_ONLY_ATTN == torch.float16 else torch.float32
+        q, k, v = (m.forward_rows(xh, 1, 1, M, out_dtype=qdt) for m in (self.q, self.k, self.v))
+        oplan = self.proj_out.wonly_plan()
+        scale = int(C) ** (-0.5)
+        if fused:
+            direct = oplan.act_dtype == torch.float16 and oplan.ldx == C
+            st = (T * C, C, C, 1)
+            o = engine.attention_h16(q, k, v, B, T, T, 1, C, st, st, st, scale, torch.float16 if direct else torch.float32)
+            oh = o if direct else engine.wonly_rows(o, oplan, 1, C, M, (0, 1, C))
+        else:
+            w_ = F.softmax(th.bmm(q.view(B, T, C), k.view(B, T, C).transpose(1, 2)) * scale, dim=2)
+            o = th.bmm(w_, v.view(B, T, C)).reshape(M, C)
+            oh = engine.wonly_rows(o, oplan, 1, C, M, (0, 1, o.stride(0)))
+        out = self.proj_out.forward_rows(oh, 1, 1, M, residual=rows)
+        engine.wonly_count("attnblock_ddim")
+        return _rows_to_nchw(out, B, H, W)
 
     def _forward_int(self, x, out_slot=None):
         B, C, H, W = x.shape
@@ -1629,6 +1719,30 @@ class QuantAttnBlock(BaseQuantBlock, _AttnQuant):
         o = engine.attention(ap, q, k, v, B, T, T, 1, C, st, st, st)
         out = _linear_like_conv2d(self.proj_out, o, B, H, W, residual=rows, gn_stats=True, slot=out_slot)
         return _rows_to_nchw(out, B, H, W)
+
+
+def ddim_head_wonly(model, h):
+    """The output head of arch.ddim_unet.Model takes ddim_head_forward_wonly for this call: engine.wonly_ddim_state(), an fp32
+    GPU map, an nn.GroupNorm and an unsplit weights-only conv_out without hooks that reads the C channels (a multiple of 8) as
+    one plain segment and keeps the map size."""
+    conv, gn = model.conv_out, model.norm_out
+    if not (engine.wonly_ddim_state() and isinstance(conv, QuantModule) and isinstance(gn, nn.GroupNorm) and torch.is_tensor(h)
+            and h.dim() == 4 and h.dtype == torch.float32 and engine.wonly_device_ok(h) and conv.kind == 'conv2d' and conv.split == 0
+            and conv.wonly_ready() and _no_hooks(conv, gn)):
+        return False
+    plan = conv.wonly_plan()
+    return engine.wonly_plain_plan(plan, h.shape[1]) and engine.conv_out_hw(h.shape[2], h.shape[3], plan) == (h.shape[2], h.shape[3])
+
+
+def ddim_head_forward_wonly(model, h):
+    """conv_out(swish(norm_out(h))) (reference ddim/models/diffusion.py:346-348) in the weights-only state: one
+    qd_groupnorm_h16 with SiLU into conv_out's operand rows, then the contraction."""
+    B, C, H, W = h.shape
+    conv = model.conv_out
+    xh = engine.wonly_groupnorm_rows(_nhwc_rows(h), B, H * W, C, model.norm_out, True, conv.wonly_plan())
+    out = conv.forward_rows(xh, B, H, W)
+    engine.wonly_count("head_ddim")
+    return _rows_to_nchw(out, B, H, W)
 
 
 def _linear_like_conv2d(mod, rows, B, H, W, residual=None, gn_stats=False, slot=None):

@@ -407,6 +407,96 @@ def run_mod(kind, batch, k, dev, attn, wide, rounds):
     return res
 
 
+def run_ddim(kind, batch, k, dev, attn, rounds):
+    """Every other weights-only knob on (layer knob fp16, block fusion, wide, mod, split-K; the attention knob with --attn);
+    engine.WEIGHT_ONLY_FUSE_DDIM off / on alternated `rounds` times in one process."""
+    import bench
+    from qdiff import engine, hip, synthetic
+    qnn, _ = bench.build_quantised_unet(kind, dev)
+    x, t, c = synthetic.synthetic_inputs(kind, batch, seed=0)
+    args = [a.to(dev) for a in (x, t, c) if a is not None]
+    qnn.set_quant_state(True, False)
+    one = lambda: qnn(*args)
+    res = {"model": kind, "batch": batch, "layer_knob": "fp16", "attn_knob": "fp16" if attn else "off", "fuse": True, "wide": True,
+           "mod": True, "splitk": True, "evals_timed": k, "rounds": rounds}
+    prev = (engine.WEIGHT_ONLY_KERNEL, engine.WEIGHT_ONLY_ATTN, engine.WEIGHT_ONLY_FUSE, engine.WEIGHT_ONLY_FUSE_WIDE, engine.WEIGHT_ONLY_FUSE_MOD,
+            engine.WEIGHT_ONLY_SPLITK, engine.WEIGHT_ONLY_FUSE_DDIM)
+    new_keys = ("resnetblock", "attnblock_ddim", "head_ddim")
+    try:
+        engine.set_weight_only_kernel(torch.float16)
+        engine.set_weight_only_attention(torch.float16 if attn else None)
+        engine.set_weight_only_fusion(True)
+        engine.set_weight_only_fusion_wide(True)
+        engine.set_weight_only_fusion_mod(True)
+        engine.set_weight_only_splitk(True)
+        res["box_probe_mfma_ms"] = round(hip.box_probe(dev, 0, 512, 60000)[0], 3)
+        off, on = [], []
+        for _ in range(rounds):                                  # alternated A/B
+            engine.set_weight_only_fusion_ddim(False)
+            off.append(_timed(one, k))
+            engine.set_weight_only_fusion_ddim(True)
+            on.append(_timed(one, k))
+        res["box_probe_mfma_ms_after"] = round(hip.box_probe(dev, 0, 512, 60000)[0], 3)
+        res["ddim_off_ms"], res["ddim_on_ms"] = round(min(off), 3), round(min(on), 3)
+        res["ddim_off_ms_all"], res["ddim_on_ms_all"] = [round(v, 3) for v in off], [round(v, 3) for v in on]
+        res["ddim_off_spread_ms"], res["ddim_on_spread_ms"] = round(max(off) - min(off), 3), round(max(on) - min(on), 3)
+        res["faster_by_more_than_spread"] = bool(min(off) - max(on) > 0 and min(off) - min(on) > max(max(off) - min(off), max(on) - min(on)))
+        outs = {}
+        for name, flag in (("off", False), ("on", True)):
+            engine.set_weight_only_fusion_ddim(flag)
+            for key in new_keys:
+                engine.WONLY_FUSED.pop(key, None)
+            for k2 in engine.WONLY_FUSED:
+                engine.WONLY_FUSED[k2] = 0
+            n0 = engine.ATTN_H16_LAUNCHES
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats(dev)
+            with torch.no_grad():
+                outs[name] = one()
+            torch.cuda.synchronize()
+            res[f"ddim_{name}_max_mem_mib"] = round(torch.cuda.max_memory_allocated(dev) / 2 ** 20, 1)
+            res[f"ddim_{name}_blocks"] = dict(engine.WONLY_FUSED)
+            res[f"ddim_{name}_attn_launches"] = engine.ATTN_H16_LAUNCHES - n0
+        res["ddim_on_vs_off_of_range"] = float((outs["on"] - outs["off"]).abs().max() / outs["off"].abs().max())
+    finally:
+        engine.set_weight_only_kernel(prev[0])
+        engine.set_weight_only_attention(prev[1])
+        engine.set_weight_only_fusion(prev[2])
+        engine.set_weight_only_fusion_wide(prev[3])
+        engine.set_weight_only_fusion_mod(prev[4])
+        engine.set_weight_only_splitk(prev[5])
+        engine.set_weight_only_fusion_ddim(prev[6])
+        for key in new_keys:
+            engine.WONLY_FUSED.pop(key, None)
+    return res
+
+
+# the one-head attention of the CIFAR-10 DDIM UNet at batch 64: (B, T, d) of the five 16x16 blocks and of mid.attn_1
+DDIM_ATTN_SHAPES = [(64, 256, 256), (64, 16, 256)]
+
+
+def ddim_shape_table(dev, shapes=DDIM_ATTN_SHAPES):
+    """The attention of QuantAttnBlock alone, fp16 projections as the route hands them over: the library passes (bmm, * scale,
+    softmax, bmm on fp32, as the route's fallback runs them) against qd_attn_h16."""
+    import torch.nn.functional as F
+    from qdiff import engine
+    prev = engine.WEIGHT_ONLY_ATTN
+    engine.set_weight_only_attention(torch.float16)
+    g = torch.Generator(device=dev).manual_seed(0)
+    try:
+        for B, T, d in shapes:
+            q, k, v = (torch.randn(B, T, d, device=dev, generator=g) for _ in range(3))
+            qh, kh, vh = q.half(), k.half(), v.half()
+            st = (T * d, d, d, 1)
+            scale = d ** -0.5
+            lib = 1000 * _events_ms(lambda: torch.bmm(F.softmax(torch.bmm(q, k.transpose(1, 2)) * scale, dim=2), v))
+            us = 1000 * _events_ms(lambda: engine.attention_h16(qh, kh, vh, B, T, T, 1, d, st, st, st, scale, torch.float16))
+            print(json.dumps({"B": B, "T": T, "d": d, "library_fp32_us": round(lib, 1), "kernel_us": round(us, 1),
+                              "tflops": round(4.0 * B * T * T * d / us / 1e6, 1), "speedup_vs_library": round(lib / us, 2)}), flush=True)
+    finally:
+        engine.set_weight_only_attention(prev)
+
+
 # LSUN-Churches LDM-8 at batch 16: (H = W, channels) of the maps its residual blocks normalise
 CHURCHES_GN_SHAPES = [(32, 192), (32, 384), (16, 384), (16, 768), (8, 384), (8, 768), (4, 768), (4, 1536), (2, 768), (2, 1536)]
 
@@ -649,6 +739,10 @@ def main():
     ap.add_argument("--splitk-shapes", action="store_true", help="the under-filled contraction shapes alone: unsplit against forced slice counts")
     ap.add_argument("--mod", action="store_true", help="the column of the scale-shift / resampling residual blocks: fusion on, FUSE_MOD off / on alternated")
     ap.add_argument("--mod-shapes", action="store_true", help="the three launch forms of --mod alone at LSUN-Churches' shapes")
+    ap.add_argument("--ddim", action="store_true", help="the column of the DDIM (CIFAR) blocks: every other weights-only knob on (the attention "
+                                                        "kernel with --attn), FUSE_DDIM off / on alternated")
+    ap.add_argument("--ddim-shapes", action="store_true", help="the DDIM attention alone at B = 64, d = 256, T = 256 and 16: library passes "
+                                                               "against the kernel")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     from qdiff import hip
@@ -658,14 +752,18 @@ def main():
         attn_shape_table(dev, SD_SHAPES + LDM_SHAPES)
     if a.fuse_shapes:
         fuse_shape_table(dev)
-    if a.wide and not a.mod:
+    if a.ddim_shapes:
+        ddim_shape_table(dev)
+    if a.wide and not a.mod and not a.ddim:
         wide_shape_table(dev)
     if a.mod_shapes:
         mod_shape_table(dev)
     if a.splitk_shapes:
         splitk_shape_table(dev)
     for kind in [m for m in a.models.split(",") if m]:           # --models "" = the shape tables alone
-        if a.mod:
+        if a.ddim:
+            res = run_ddim(kind, a.batch, a.evals, dev, a.attn, a.rounds)
+        elif a.mod:
             res = run_mod(kind, a.batch, a.evals, dev, a.attn, a.wide, a.rounds)
         elif a.splitk:
             res = run_splitk(kind, a.batch, a.evals, dev, a.rounds)

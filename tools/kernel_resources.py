@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""VGPR / spill / scratch / SGPR / LDS of every kernel of one csrc file, as hipcc compiles it for gfx950.
+"""VGPR / AGPR / spill / scratch / SGPR / LDS of every kernel of one csrc file, as hipcc compiles it for gfx950.
 
     python tools/kernel_resources.py igemm_dma.hip [substring ...]
 
@@ -20,7 +20,8 @@ def resources(asm):
     out = {}
     for b in asm.split("  - .agpr_count:")[1:]:
         g = lambda k: int(re.search(rf"\.{k}:\s+(\d+)", b).group(1))
-        out[re.search(r"\.name:\s+(\S+)", b).group(1)] = dict(vgpr=g("vgpr_count"), spill=g("vgpr_spill_count"), scratch=g("private_segment_fixed_size"),
+        # vgpr_count is the unified file (architectural VGPRs, rounded up, then the AGPRs); agpr_count leads the entry
+        out[re.search(r"\.name:\s+(\S+)", b).group(1)] = dict(agpr=int(b.split()[0]), vgpr=g("vgpr_count"), spill=g("vgpr_spill_count"), scratch=g("private_segment_fixed_size"),
                                                               sgpr=g("sgpr_count"), lds=g("group_segment_fixed_size"))
     return out
 
@@ -41,7 +42,7 @@ def main():
         short = short.replace("(anonymous namespace)::", "").replace("((anonymous namespace)::ConvD)", "")
         if filt and not any(f in short for f in filt):
             continue
-        print(f"{short:70s} vgpr {d['vgpr']:3d} spill {d['spill']:3d} scratch {d['scratch']:4d} B sgpr {d['sgpr']:3d} lds {d['lds']}")
+        print(f"{short:70s} vgpr {d['vgpr']:3d} agpr {d['agpr']:3d} spill {d['spill']:3d} scratch {d['scratch']:4d} B sgpr {d['sgpr']:3d} lds {d['lds']}")
 
 
 if __name__ == "__main__":
