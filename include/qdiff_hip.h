@@ -250,6 +250,27 @@ int qd_temb_mlp(const float* x, int64_t ldx, int B, int K, int apply_silu, const
                 const int32_t* blocks, int n_blocks, int wbits, int qmin, int qmax, int off, float* out, int64_t ldo,
                 void* stream);
 
+/* K6w  (additive in ABI 20) the same Linears in the weights-only state (weight_quant, act_quant) = (True, False)
+ *     (quant_layer.py:620-631: the fp Linear of the fake-quantised weight; openaimodel.py:758-759 `time_embed`,
+ *     openaimodel.py:225-232 with qdiff/quant_block.py:98-107 `emb_layers`, ddim diffusion.py:127 `temb_proj`, 318-320
+ *     `temb.dense`), which ran as a torch SiLU, a qd_rows_to_h16 and a qd_conv2d_wq_h16 launch per Linear.  One launch
+ *     evaluates n_layers Linears that share the fp32 input x [B][K] (row stride ldx, rows 16-byte aligned, K % 16 == 0):
+ *         out[b][out_off_l + n] = delta_l[n] * sum_k r(silu?(x[b][k])) * (q_l[k][n] - z_l[n]) + bias_l[n]
+ *     r: the one rounding to act_dtype (QD_F16 / QD_BF16, nearest even, as qd_rows_to_h16); silu = x / (1 + exp(-x)) in
+ *     fp32 as in qd_temb_mlp; q: the tile-ordered codes of qd_pack_weights_t4 / _t8 (the array qd_conv2d_wq_h16 reads);
+ *     z: the RAW weight zero point, subtracted from the code before the multiply (no row sums); fp32 accumulation.
+ *     layers: DEVICE array of n_layers records, 40 bytes each:
+ *         { const uint8_t* w (first K-step of the layer's ONLY segment: the caller checks that there is one);
+ *           const float* delta; const int32_t* z; const float* bias (or NULL); int32_t Cout; int32_t out_off; }
+ *     blocks: DEVICE int32 [n_blocks][2] = {layer index, first output channel}: one workgroup per 64 output channels.
+ *     Any B > 0 (32-row MFMA tiles).  Each output element is accumulated exactly as qd_conv2d_wq_h16 accumulates it unsplit (the
+ *     same instruction, K order and epilogue), so the results equal that path's bit for bit whenever the SiLU values do.
+ *     Columns of out outside every [out_off_l, out_off_l + Cout_l) are never written.  bf16 operands carry q - z exactly
+ *     only while |q - z| <= 256 (the caller checks, as for qd_conv2d_wq_h16). */
+int qd_temb_mlp_wq_h16(const float* x, int64_t ldx, int B, int K, int apply_silu, const void* layers, int n_layers,
+                       const int32_t* blocks, int n_blocks, int wbits, int act_dtype, float* out, int64_t ldo,
+                       void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * K5  GroupNorm -> SiLU -> quantise.   Replaces nn.GroupNorm(32,C) / GroupNorm32 → x*sigmoid(x)
  *     → act_quantizer of the following QuantModule (ddim/models/diffusion.py:121-123,127-130;

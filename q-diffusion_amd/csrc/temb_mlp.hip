@@ -139,7 +139,157 @@ __global__ __launch_bounds__(256) void temb_kernel(const float* __restrict__ x, 
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Weights-only form (qd_temb_mlp_wq_h16): the same Linears in the reference's (weight_quant, act_quant) = (True, False) state
+// (quant_layer.py:620-631), where each was a torch SiLU, a qd_rows_to_h16 and a qd_conv2d_wq_h16 launch whose 128 x 128 tile
+// held 2 .. 64 real rows:
+//     out[b][out_off + n] = delta[n] * sum_k r(silu?(x[b][k])) * (q[k][n] - z[n]) + bias[n]
+// r = the ONE rounding to fp16 / bf16 (nearest even, the packing functions of qd_rows_to_h16).
+// One wave = one 32-row x 32-channel tile of one layer on v_mfma_f32_32x32x16_{f16,bf16}, and it walks K exactly as
+// wq_h16_kernel (csrc/igemm_dma.hip) walks it for the same output element: 64-channel K-steps in order, in each the four MFMAs
+// (g, u) over k = g*32 + half*16 + u*8 + 0..7, the same A / B lane maps, the weight fragment q - z by the same 0x6400 | q
+// pattern and packed add, channels past K as zeros, then qd_wq_affine(acc, delta, 0, bias).  The same operand values in the same
+// places of the same instructions give the same fp32 bits, so the results equal the unsplit generic path's bit for bit
+// whenever the SiLU values do — the property the int8 kernel above has towards qd_conv2d_i8 — and a model does not move when the
+// knob flips.  (An FMA or dot2 chain sums in another order: agreement to rounding only, and in a network of fp16 roundings a
+// 1e-7 difference in the embedding flips operand roundings downstream.)  With 2 .. 64 rows most of the 32-row tile is idle;
+// the launch is bound by latency either way.  The operand fragment is made in registers (8 floats -> SiLU -> 8 halves per
+// lane and MFMA): no LDS, no barrier, any number of rows.  block = 64 channels of a layer = 2 waves, grid.y = 32-row groups.
+// ---------------------------------------------------------------------------------------------
+struct TembWqLayer {
+    const uint8_t* w;        // tile-ordered codes (qd_pack_weights_t4 / _t8), K-step 0 of the layer's only segment
+    const float*   delta;    // [Cout] delta_w[n]
+    const int*     z;        // [Cout] RAW weight zero point
+    const float*   bias;     // [Cout] or NULL
+    int Cout, out_off;
+};
+
+typedef _Float16 tw_v2h __attribute__((ext_vector_type(2)));
+typedef float tw_v16f __attribute__((ext_vector_type(16)));
+
+// 8 codes of a unit -> the halves 1024 + q in K order (wq_magic_t4 / _t8 of csrc/igemm_dma.hip)
+template <int WB>
+__device__ __forceinline__ v4i temb_wq_magic(unsigned x, unsigned y) {
+    if constexpr (WB == 4) {                                  // one word: lo nibbles are codes 0..3, hi nibbles 4..7
+        const unsigned lo = x & 0x0F0F0F0Fu, hi = (x >> 4) & 0x0F0F0F0Fu;
+        return v4i{(int)__builtin_amdgcn_perm(0x64646464u, lo, 0x04010400u), (int)__builtin_amdgcn_perm(0x64646464u, lo, 0x04030402u),
+                   (int)__builtin_amdgcn_perm(0x64646464u, hi, 0x04010400u), (int)__builtin_amdgcn_perm(0x64646464u, hi, 0x04030402u)};
+    } else {                                                  // two words of stored bytes q - 128
+        x ^= 0x80808080u;
+        y ^= 0x80808080u;
+        return v4i{(int)__builtin_amdgcn_perm(0x64646464u, x, 0x04010400u), (int)__builtin_amdgcn_perm(0x64646464u, x, 0x04030402u),
+                   (int)__builtin_amdgcn_perm(0x64646464u, y, 0x04010400u), (int)__builtin_amdgcn_perm(0x64646464u, y, 0x04030402u)};
+    }
+}
+// halves 1024 + q -> the B fragment (q - z) in the operand type; nz = {-(1024 + z), -(1024 + z)}  (wq_frag)
+template <bool FH>
+__device__ __forceinline__ v4i temb_wq_frag(const v4i& mag, const tw_v2h nz) {
+    v4i r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int w = mag[e];                                 // (through a scalar, as wq_frag)
+        const tw_v2h d = __builtin_bit_cast(tw_v2h, w) + nz;  // v_pk_add_f16: exact integers
+        if constexpr (FH) r[e] = __builtin_bit_cast(int, d);
+        else r[e] = (int)qd_pack2bf((float)d[0], (float)d[1]);
+    }
+    return r;
+}
+
+template <int WB, bool FH>
+__global__ __launch_bounds__(128) void temb_wq_kernel(const float* __restrict__ x, long ldx, int B, int K, int silu,
+                                                      const TembWqLayer* __restrict__ layers, const int2* __restrict__ blocks,
+                                                      float* __restrict__ out, long ldo) {
+    constexpr int UB = 2 * WB, TB = 256 * WB;                  // bytes of one unit (16 codes of a channel), of one (K-step, 32-channel) tile
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int frow = lane & 31, fhalf = lane >> 5;
+    const int2 bl = blocks[blockIdx.x];
+    const TembWqLayer L = layers[bl.x];
+    const int n0 = bl.y + 32 * wave;
+    if (n0 >= L.Cout) return;                                  // (wave-uniform; the kernel has no barrier)
+    const int m0 = blockIdx.y * 32, row = m0 + frow;
+    const bool rok = row < B;
+    const float* xr = x + (long)(rok ? row : 0) * ldx;
+    const int n = n0 + frow;
+    const bool nok = n < L.Cout;
+    const int ntiles = (L.Cout + 31) >> 5;
+    const int z = nok ? L.z[n] : 0;
+    const _Float16 hz = (_Float16)(float)(-(1024 + z));        // exact: |1024 + z| <= 2048
+    const tw_v2h nz = {hz, hz};
+    const float dl = nok ? L.delta[n] : 0.f, bias = (nok && L.bias) ? L.bias[n] : 0.f;
+    tw_v16f acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    const int nst = (K + 63) >> 6;
+    for (int ks = 0; ks < nst; ++ks) {
+        const uint8_t* wsrc = L.w + ((long)ks * ntiles + (n0 >> 5)) * TB;
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+            v4i mag[2];
+            const uint8_t* bp = wsrc + ((g * 2 + fhalf) * 32 + frow) * UB;
+            if constexpr (WB == 4) {
+                const uint2 raw = *reinterpret_cast<const uint2*>(bp);
+                mag[0] = temb_wq_magic<4>(raw.x, 0u);
+                mag[1] = temb_wq_magic<4>(raw.y, 0u);
+            } else {
+                const v4i raw = *reinterpret_cast<const v4i*>(bp);
+                mag[0] = temb_wq_magic<8>((unsigned)raw.x, (unsigned)raw.y);
+                mag[1] = temb_wq_magic<8>((unsigned)raw.z, (unsigned)raw.w);
+            }
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int k0 = ks * 64 + g * 32 + fhalf * 16 + u * 8;
+                v4i af = {0, 0, 0, 0};                             // rows past B and channels past K read zeros
+                if (rok && k0 < K) {
+                    const float4 v0 = *reinterpret_cast<const float4*>(xr + k0), v1 = *reinterpret_cast<const float4*>(xr + k0 + 4);
+                    float e[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+                    if (silu) {
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) e[j] = e[j] / (1.0f + expf(-e[j]));   // torch's silu: x / (1 + exp(-x))
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) af[j] = (int)(FH ? qd_pack2h(e[2 * j], e[2 * j + 1]) : qd_pack2bf(e[2 * j], e[2 * j + 1]));
+                }
+                const v4i bf = temb_wq_frag<FH>(mag[u], nz);
+                if constexpr (FH)
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, af), __builtin_bit_cast(v8h, bf), acc, 0, 0, 0);
+                else
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(v8bf, af), __builtin_bit_cast(v8bf, bf), acc, 0, 0, 0);
+            }
+        }
+    }
+    if (!nok) return;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {                              // C layout: lane = column, register r = row (r & 3) + 8 (r >> 2) + 4 half
+        const int m = m0 + (r & 3) + 8 * (r >> 2) + 4 * fhalf;
+        if (m < B) out[(long)m * ldo + L.out_off + n] = qd_wq_affine(acc[r], dl, 0.f, bias);
+    }
+}
+
 }  // namespace
+
+extern "C" int qd_temb_mlp_wq_h16(const float* x, int64_t ldx, int B, int K, int apply_silu, const void* layers, int n_layers,
+                                  const int32_t* blocks, int n_blocks, int wbits, int act_dtype, float* out, int64_t ldo,
+                                  void* stream) {
+    QD_REQUIRE(x && layers && blocks && out, "qd_temb_mlp_wq_h16: null pointer");
+    QD_REQUIRE(B > 0 && K > 0 && n_layers > 0 && n_blocks > 0, "qd_temb_mlp_wq_h16: bad shape (B = %d, K = %d, %d layers, %d blocks)", B, K, n_layers, n_blocks);
+    QD_REQUIRE(K % 16 == 0, "qd_temb_mlp_wq_h16: K must be a multiple of 16 (got %d)", K);
+    QD_REQUIRE(wbits == 4 || wbits == 8, "qd_temb_mlp_wq_h16: wbits must be 4 or 8");
+    QD_REQUIRE(act_dtype == QD_F16 || act_dtype == QD_BF16, "qd_temb_mlp_wq_h16: act_dtype must be f16/bf16");
+    QD_REQUIRE(ldx >= K && ldx % 4 == 0 && qd_aligned(x, 16), "qd_temb_mlp_wq_h16: x rows must be 16-byte aligned");
+    QD_REQUIRE(ldo > 0, "qd_temb_mlp_wq_h16: bad output row stride");
+    const int groups = (B + 31) / 32;                          // 32-row tiles
+    QD_REQUIRE(groups <= 65535, "qd_temb_mlp_wq_h16: %d rows need %d row groups of 32 (the grid holds 65535)", B, groups);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const auto* L = reinterpret_cast<const TembWqLayer*>(layers);
+    const auto* bl = reinterpret_cast<const int2*>(blocks);
+    const bool fh = act_dtype == QD_F16;
+#define QD_TEMB_WQ(WB, FH) hipLaunchKernelGGL((temb_wq_kernel<WB, FH>), dim3(n_blocks, groups), dim3(128), 0, st, x, (long)ldx, B, K, apply_silu, L, bl, out, (long)ldo)
+    if (wbits == 4) { if (fh) QD_TEMB_WQ(4, true); else QD_TEMB_WQ(4, false); }
+    else            { if (fh) QD_TEMB_WQ(8, true); else QD_TEMB_WQ(8, false); }
+#undef QD_TEMB_WQ
+    QD_LAUNCH_CHECK("qd_temb_mlp_wq_h16");
+    return 0;
+}
 
 extern "C" int qd_temb_mlp(const float* x, int64_t ldx, int B, int K, int apply_silu, const void* layers, int n_layers,
                            const int32_t* blocks, int n_blocks, int wbits, int qmin, int qmax, int off, float* out,

@@ -766,6 +766,40 @@ def wonly_ddim_state():
     return WEIGHT_ONLY_FUSE_DDIM and wonly_fuse_state()
 
 
+# Timestep-embedding Linears: False (default) = `time_embed` / `temb.dense` and every block's `emb_layers` /
+# `temb_proj` run as weights-only QuantModules of their own (torch SiLU, qd_rows_to_h16, qd_conv2d_wq_h16 each); True = one
+# qd_temb_mlp_wq_h16 launch per dependency level (quant_block.time_mlp: two, quant_block.EmbGroup: one for all blocks).
+# Effective only while WEIGHT_ONLY_KERNEL is set; independent of WEIGHT_ONLY_FUSE.  QDIFF_WEIGHT_ONLY_TEMB=1, or
+# engine.set_weight_only_temb().
+WEIGHT_ONLY_TEMB = _parse_flag(os.environ.get("QDIFF_WEIGHT_ONLY_TEMB"), "QDIFF_WEIGHT_ONLY_TEMB")
+
+# qd_temb_mlp_wq_h16 launches (tests read it)
+WONLY_TEMB = [0]
+
+
+def set_weight_only_temb(on):
+    """True / False (or the strings QDIFF_WEIGHT_ONLY_TEMB accepts)."""
+    _set_flag("WEIGHT_ONLY_TEMB", on, "weight-only embedding projections")
+
+
+def wonly_temb_state():
+    """The one-launch embedding Linears engage: both knobs, no simulation, no autograd, no autocast."""
+    return (WEIGHT_ONLY_TEMB and WEIGHT_ONLY_KERNEL is not None and not SIMULATE and not torch.is_grad_enabled()
+            and not _autocast_on())
+
+
+# HIP-graph replay of weights-only evaluations (DESIGN.md §4.19): False (default) = an evaluation in state (True, False) runs
+# launch by launch from Python, as it always did (a replay runs no Python: the WONLY_* counters above stop ticking); True =
+# QuantModel.forward captures and replays it under the rules of the integer state (QuantModel._wonly_token), one graph per call
+# signature and tuple of weights-only knobs.  QDIFF_WEIGHT_ONLY_GRAPH=1, or engine.set_weight_only_graph().
+WEIGHT_ONLY_GRAPH = _parse_flag(os.environ.get("QDIFF_WEIGHT_ONLY_GRAPH"), "QDIFF_WEIGHT_ONLY_GRAPH")
+
+
+def set_weight_only_graph(on):
+    """True / False (or the strings QDIFF_WEIGHT_ONLY_GRAPH accepts)."""
+    _set_flag("WEIGHT_ONLY_GRAPH", on, "weight-only graph replay")
+
+
 def wonly_count(kind):
     """One more block forward of `kind` on a fused route (a default: tests replace WONLY_FUSED by a dict without the new keys)."""
     WONLY_FUSED[kind] = WONLY_FUSED.get(kind, 0) + 1

@@ -65,7 +65,7 @@ EXPORTS = ["qd_abi_version", "qd_last_error", "qd_device_ok", "qd_box_probe", "q
            "qd_pack_weights_t8",
            "qd_conv2d_i8", "qd_conv_config", "qd_conv2d_i8_group", "qd_conv2d_i8_splitk_ws_bytes",
            "qd_conv2d_i8_acc", "qd_groupnorm_ws_bytes", "qd_groupnorm_silu_quant", "qd_groupnorm_mod_silu_quant", "qd_layernorm_quant",
-           "qd_geglu_quant", "qd_quantize_heads", "qd_attn_i8", "qd_attn_i8_qp", "qd_attn_keyterm", "qd_attn_uses_keyterm", "qd_attn_config", "qd_attn_ws_bytes", "qd_bmm_qk_i8", "qd_bmm_pv_i8", "qd_temb_mlp",
+           "qd_geglu_quant", "qd_quantize_heads", "qd_attn_i8", "qd_attn_i8_qp", "qd_attn_keyterm", "qd_attn_uses_keyterm", "qd_attn_config", "qd_attn_ws_bytes", "qd_bmm_qk_i8", "qd_bmm_pv_i8", "qd_temb_mlp", "qd_temb_mlp_wq_h16",
            "qd_fakequant_blocks", "qd_fakequant_fwd", "qd_fakequant_bwd",
            "qd_conv2d_bf16", "qd_pack_weights_bf16_bytes", "qd_pack_weights_bf16", "qd_groupnorm_silu_bf16",
            "qd_pack_weights_h16", "qd_groupnorm_silu_h16", "qd_conv2d_wq_h16", "qd_rows_to_h16",
@@ -119,6 +119,7 @@ def load():
     lib.qd_attn_config.argtypes = [i32, i32, i32, i32]
     lib.qd_attn_config.restype = None
     lib.qd_temb_mlp.argtypes = [vp, i64, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp, i64, vp]
+    lib.qd_temb_mlp_wq_h16.argtypes = [vp, i64, i32, i32, i32, vp, i32, vp, i32, i32, i32, vp, i64, vp]
     lib.qd_bmm_qk_i8.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i64, i64, vp]
     lib.qd_bmm_pv_i8.argtypes = [vp, i64, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, i64, i64, vp]
     lib.qd_fakequant_blocks.restype = ctypes.c_int64
@@ -774,3 +775,57 @@ def temb_mlp(x, silu, plans, offsets, out):
         _check(load().qd_temb_mlp(_ptr(xb, "x"), xb.stride(0), xb.shape[0], K, 1 if silu else 0, raw.data_ptr(), len(plans),
                                   tab.data_ptr(), nblk, p0.pack.wbits, g.qmin, g.qmax, g.off, _ptr(ob, "out"), ob.stride(0),
                                   _stream()), "qd_temb_mlp")
+
+
+class _TembWqLayer(ctypes.Structure):
+    _fields_ = [("w", ctypes.c_void_p), ("delta", ctypes.c_void_p), ("z", ctypes.c_void_p), ("bias", ctypes.c_void_p),
+                ("Cout", ctypes.c_int32), ("out_off", ctypes.c_int32)]
+
+
+_TEMB_WQ_DESC = {}       # tuple(id(plan)) + offsets -> (layer records on the device, block table, #blocks, the plans themselves)
+
+
+def _temb_wq_desc(plans, offsets, device):
+    key = tuple(id(p) for p in plans) + tuple(offsets)
+    hit = _TEMB_WQ_DESC.get(key)
+    if hit is not None:
+        return hit
+    recs = (_TembWqLayer * len(plans))()
+    blocks = []
+    for i, (p, off) in enumerate(zip(plans, offsets)):
+        sg = p.segs[0]
+        r = recs[i]
+        r.w = p.pack.wq.data_ptr() + sg["kstep0"] * ((p.Cout + 31) // 32) * (1024 if p.pack.wbits == 4 else 2048)
+        r.delta, r.z, r.bias = _ptr(sg["scale"], "delta"), _ptr(sg["zw"], "z"), _ptr(p.bias, "bias")
+        r.Cout, r.out_off = p.Cout, off
+        blocks += [(i, n0) for n0 in range(0, p.Cout, 64)]
+    raw = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(device)
+    tab = torch.tensor(blocks, dtype=torch.int32).to(device).contiguous()
+    if len(_TEMB_WQ_DESC) > 64:
+        _TEMB_WQ_DESC.clear()
+    hit = _TEMB_WQ_DESC[key] = (raw, tab, len(blocks), list(plans))  # the plans (and through them every pointer) stay alive
+    return hit
+
+
+def temb_mlp_wq_h16(x, silu, plans, offsets, out, act_dtype):
+    """x [B][K] fp32 rows; plans: single-segment WonlyPlans of Linears that share this input; out[:, off:off+Cout] per plan
+    (fp32, columns outside the slices untouched).  One launch (qd_temb_mlp_wq_h16), any B."""
+    if act_dtype not in (torch.float16, torch.bfloat16):
+        raise HipEngineError("temb_mlp_wq_h16: operands must be float16 or bfloat16")
+    if x.dim() != 2 or x.dtype != torch.float32 or out.dim() != 2 or out.dtype != torch.float32 or out.stride(1) != 1:
+        raise HipEngineError("temb_mlp_wq_h16: x and out must be fp32 rows")
+    B, K = x.shape
+    p0 = plans[0]
+    if any(len(p.segs) != 1 or p.pack.wbits != p0.pack.wbits or p.Cin != K or p.pack.taps != 1 or p.act_dtype != act_dtype
+           for p in plans):
+        raise HipEngineError("temb_mlp_wq_h16: the Linears must share input width, weight bits and operand type (one segment each)")
+    if out.shape[0] != B or any(off < 0 or off + p.Cout > out.shape[1] for p, off in zip(plans, offsets)):
+        raise HipEngineError("temb_mlp_wq_h16: a slice lies outside the output rows")
+    if x.stride(1) != 1 or x.stride(0) % 4 != 0 or x.data_ptr() % 16:
+        x = x.contiguous()
+    raw, tab, nblk, _ = _temb_wq_desc(plans, offsets, x.device)
+    _check(load().qd_temb_mlp_wq_h16(_ptr(x, "x"), x.stride(0) if B > 1 else max(x.stride(0), K), B, K, 1 if silu else 0,
+                                     raw.data_ptr(), len(plans), tab.data_ptr(), nblk, p0.pack.wbits, _H16[act_dtype],
+                                     _ptr(out, "out"), out.stride(0), _stream()), "qd_temb_mlp_wq_h16")
+    from . import engine
+    engine.WONLY_TEMB[0] += 1

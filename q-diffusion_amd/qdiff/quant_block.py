@@ -337,14 +337,17 @@ class EmbGroup:
     quant_block.py:98-107 `emb_layers`, ddim diffusion.py:127 `temb_proj`): every block receives the SAME embedding
     tensor, so the first block that asks evaluates all of them with ONE launch (K6, csrc/temb_mlp.hip) and the others
     pick their slice.  Falls back to the per-block composition (returns None) whenever a projection is not on the
-    integer path, is tracking its range, or still needs its data-dependent initialisation."""
+    integer path, is tracking its range, or still needs its data-dependent initialisation.
+    In the weights-only state under engine.WEIGHT_ONLY_TEMB the one launch is qd_temb_mlp_wq_h16 (_compute_wonly); there the
+    scale-shift blocks (projections to 2 C features) are members too."""
 
     def __init__(self):
-        self.members = []            # (block, QuantModule)
+        self.members = []            # (block, QuantModule, member of the integer launch as well)
         self._emb, self._out, self._offs = None, None, {}
 
-    def register(self, blk, linear):
-        self.members.append((blk, linear))
+    def register(self, blk, linear, int_path=True):
+        """int_path=False: a member of the weights-only launch only (the integer route of such a block never asked)."""
+        self.members.append((blk, linear, int_path))
         blk.__dict__["_emb_group"] = self
 
     def reset(self):
@@ -358,15 +361,28 @@ class EmbGroup:
             e = self.get(blk, base)
             return None if e is None else e[:emb.shape[0]]
         if self._emb is not emb:
-            self._emb, self._out = emb, None
+            self._emb, self._out, self._offs = emb, None, {}
             self._compute(emb)
-        if self._out is None:
+        if self._out is None or id(blk) not in self._offs:
             return None
         off, n = self._offs[id(blk)]
         return self._out[:, off:off + n]
 
+    def _launch(self, emb, members, plans, fn):
+        offs, tot = [], 0
+        for (blk, _, _), p in zip(members, plans):
+            self._offs[id(blk)] = (tot, p.Cout)
+            offs.append(tot)
+            tot += (p.Cout + 63) // 64 * 64
+        out = torch.empty((emb.shape[0], tot), dtype=torch.float32, device=emb.device)
+        fn(plans, offs, out)
+        self._out = out
+
     def _compute(self, emb):
-        lins = [l for _, l in self.members]
+        if engine.WEIGHT_ONLY_TEMB and self._compute_wonly(emb):
+            return
+        members = [m for m in self.members if m[2]]
+        lins = [l for _, l, _ in members]
         if not torch.is_tensor(emb) or emb.dim() != 2 or not emb.is_floating_point() or len(lins) < 2 or emb.shape[1] % 16:
             return                                       # (qd_temb_mlp streams 16-byte chunks of K)
         if not _int_mode(*lins) or any(l.split or l.kind != 'linear' or not l.act_quantizer.inited for l in lins):
@@ -377,14 +393,51 @@ class EmbGroup:
         if any(len(p.segs) != 1 or p.pack.Cin != emb.shape[1] or p.pack.wbits != p0.pack.wbits
                or (p.grids[0].qmin, p.grids[0].qmax, p.grids[0].off) != g0 for p in plans):
             return
-        offs, tot = [], 0
-        for (blk, _), p in zip(self.members, plans):
-            self._offs[id(blk)] = (tot, p.Cout)
-            offs.append(tot)
-            tot += (p.Cout + 63) // 64 * 64
-        out = torch.empty((emb.shape[0], tot), dtype=torch.float32, device=emb.device)
-        engine.hip.temb_mlp(emb.float(), True, plans, offs, out)
-        self._out = out
+        self._launch(emb, members, plans, lambda pl, offs, out: engine.hip.temb_mlp(emb.float(), True, pl, offs, out))
+
+    def _compute_wonly(self, emb):
+        """The weights-only launch (engine.WEIGHT_ONLY_TEMB): True when it ran.  Any miss leaves every block its own module
+        call for this evaluation: the knobs (engine.wonly_temb_state), a 2-D fp32 GPU embedding of K % 16 == 0 features, at
+        least two members, each a weights-only-ready one-segment Linear of K inputs without split, all of one weight width and
+        operand type, and no forward (pre-)hook on a member or on the `emb_layers` container around it (a hooked module must
+        keep seeing its calls)."""
+        if not engine.wonly_temb_state() or len(self.members) < 2:
+            return False
+        lins = [l for _, l, _ in self.members]
+        plans = wonly_temb_plans(lins, emb, [getattr(blk, "emb_layers", None) for blk, _, _ in self.members])
+        if plans is None:
+            return False
+        dt = plans[0].act_dtype
+        self._launch(emb, self.members, plans, lambda pl, offs, out: engine.hip.temb_mlp_wq_h16(emb, True, pl, offs, out, dt))
+        return True
+
+
+def wonly_temb_plans(lins, x, containers=()):
+    """The WonlyPlans of Linears `lins` that qd_temb_mlp_wq_h16 evaluates on the fp32 rows x in one launch, or None (the gate
+    of EmbGroup._compute_wonly / time_mlp below engine.wonly_temb_state())."""
+    if (not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32 or not engine.wonly_device_ok(x) or x.shape[0] < 1
+            or x.shape[1] % 16):
+        return None
+    hooked = [m for c in containers if isinstance(c, nn.Module) for m in c.modules()] + list(lins)
+    if not _no_hooks(*hooked):
+        return None
+    if any(l.kind != 'linear' or l.split or not l.wonly_ready() for l in lins):
+        return None
+    plans = [l.wonly_plan() for l in lins]
+    p0 = plans[0]
+    if any(len(p.segs) != 1 or p.Cin != x.shape[1] or p.pack.taps != 1 or p.pack.wbits != p0.pack.wbits
+           or p.act_dtype != p0.act_dtype for p in plans):
+        return None
+    return plans
+
+
+def wonly_emb(blk, emb):
+    """The block's slice of the one-launch embedding projections in the weights-only state (engine.WEIGHT_ONLY_TEMB), fp32
+    [B][Cout] with unit column stride, or None: the block then calls its own `emb_layers` / `temb_proj`."""
+    if not engine.WEIGHT_ONLY_TEMB:
+        return None
+    grp = blk.__dict__.get("_emb_group")
+    return grp.get(blk, emb) if grp is not None else None
 
 
 # where the context branch forks off the main stream: "start" = the model's forward pre-hook (before the stem), "attn" = right
@@ -682,7 +735,8 @@ class ContextKV:
 
 def time_mlp(lin0, lin1, t_emb, act=F.silu):
     """`Linear -> SiLU -> Linear` on the sinusoid table (reference openaimodel.py:758-759 `time_embed`, ddim
-    diffusion.py:318-320): two K6 launches on the integer path, the plain composition otherwise."""
+    diffusion.py:318-320): two K6 launches on the integer path, two qd_temb_mlp_wq_h16 launches in the weights-only state under
+    engine.WEIGHT_ONLY_TEMB, the plain composition otherwise."""
     if (_int_mode(lin0, lin1) and lin0.kind == 'linear' and lin1.kind == 'linear' and not (lin0.split or lin1.split)
             and lin0.act_quantizer.inited and lin1.act_quantizer.inited and torch.is_tensor(t_emb) and t_emb.dim() == 2):
         p0, p1 = lin0.conv_plan(), lin1.conv_plan()
@@ -692,6 +746,17 @@ def time_mlp(lin0, lin1, t_emb, act=F.silu):
             out = torch.empty((t_emb.shape[0], p1.Cout), dtype=torch.float32, device=t_emb.device)
             engine.hip.temb_mlp(h, True, [p1], [0], out)
             return out
+    if engine.WEIGHT_ONLY_TEMB and engine.wonly_temb_state():
+        p0 = wonly_temb_plans([lin0], t_emb)
+        # (both Linears or neither: the second one's gate is asked before the first launch; its input is [B][Cout of the first])
+        if p0 is not None:
+            h = torch.empty((t_emb.shape[0], p0[0].Cout), dtype=torch.float32, device=t_emb.device)
+            p1 = wonly_temb_plans([lin1], h)
+            if p1 is not None and p1[0].pack.wbits == p0[0].pack.wbits:
+                engine.hip.temb_mlp_wq_h16(t_emb, False, p0, [0], h, p0[0].act_dtype)
+                out = torch.empty((t_emb.shape[0], p1[0].Cout), dtype=torch.float32, device=t_emb.device)
+                engine.hip.temb_mlp_wq_h16(h, True, p1, [0], out, p1[0].act_dtype)
+                return out
     return lin1(act(lin0(t_emb)))
 
 
@@ -866,7 +931,9 @@ class QuantResBlock(BaseQuantBlock, ldm_unet.TimestepBlock):
         else:
             xh = engine.wonly_groupnorm_rows(rows, B, H * W, C, self.in_layers[0], True, conv1.wonly_plan())
         S = H * W
-        e = self.emb_layers(emb).float()
+        e = wonly_emb(self, emb)                           # all blocks' projections in one launch (engine.WEIGHT_ONLY_TEMB)
+        if e is None:
+            e = self.emb_layers(emb).float()
         if e.stride(1) != 1:
             e = e.contiguous()
         if self.use_scale_shift_norm:
@@ -893,7 +960,10 @@ class QuantResBlock(BaseQuantBlock, ldm_unet.TimestepBlock):
             h = self.in_layers[-1](h)
         else:
             h = self.in_layers(x)
-        e = self.emb_layers(emb).type(h.dtype)
+        e = wonly_emb(self, emb)
+        if e is None:
+            e = self.emb_layers(emb)
+        e = e.type(h.dtype)
         while e.dim() < h.dim():
             e = e[..., None]
         live = _dropout_live(self)      # the dropout mask follows MEMORY order: NCHW, as the reference's tensors are laid out
@@ -1515,7 +1585,10 @@ class QuantResnetBlock(BaseQuantBlock):
         if self._wonly_route(x, temb):
             return self._forward_wonly(x, temb, split)
         h = self.conv1(ddim_unet.nonlinearity(self.norm1(x)))
-        h = h + self.temb_proj(ddim_unet.nonlinearity(temb))[:, :, None, None]
+        e = wonly_emb(self, temb)
+        if e is None:
+            e = self.temb_proj(ddim_unet.nonlinearity(temb))
+        h = h + e[:, :, None, None]
         h = ddim_unet.nonlinearity(self.norm2(h))
         if _dropout_live(self):
             h = h.contiguous()          # the dropout mask follows MEMORY order: NCHW, as the reference's tensors are laid out
@@ -1551,7 +1624,9 @@ class QuantResnetBlock(BaseQuantBlock):
         conv1, conv2 = self.conv1, self.conv2
         rows = _nhwc_rows(x)
         xh = engine.wonly_groupnorm_rows(rows, B, S, C, self.norm1, True, conv1.wonly_plan())
-        e = self.temb_proj(ddim_unet.nonlinearity(temb)).float()
+        e = wonly_emb(self, temb)
+        if e is None:
+            e = self.temb_proj(ddim_unet.nonlinearity(temb)).float()
         if e.stride(1) != 1:
             e = e.contiguous()
         h = conv1.forward_rows(xh, B, H, W, rowbias=e)

@@ -86,8 +86,10 @@ class QuantModel(nn.Module):
         embedding tensor), two for the `time_embed` MLP of the LDM / SD UNet (this repo's class or the reference's)."""
         group = EmbGroup()
         for m in self.model.modules():
-            if isinstance(m, QuantResBlock) and not m.use_scale_shift_norm and isinstance(m.emb_layers[-1], QuantModule):
-                group.register(m, m.emb_layers[-1])
+            if isinstance(m, QuantResBlock) and isinstance(m.emb_layers[-1], QuantModule):
+                # (a scale-shift block projects to 2 C features: a member of the weights-only launch only, as before on the
+                # integer path, where its own module call feeds the modulated norm)
+                group.register(m, m.emb_layers[-1], int_path=not m.use_scale_shift_norm)
             elif isinstance(m, QuantResnetBlock) and isinstance(m.temb_proj, QuantModule):
                 group.register(m, m.temb_proj)
         ctx = ContextKV()                # cross-attention keys / values of every transformer block: one side-stream branch
@@ -296,6 +298,84 @@ class QuantModel(nn.Module):
     def state_token(self):
         return self._state_token()
 
+    # ---- the weights-only token: "every layer runs the weights-only kernel, and these are the tensors its plans were made from" ----
+    # Kept apart from _state_token(): that one also switches on the guidance-pair sharing and the prepared context, which are
+    # integer-only.  This one gates nothing but HIP-graph replay of the state (True, False) (engine.WEIGHT_ONLY_GRAPH).  The
+    # weights-only knobs are NOT part of it: they select a graph (_wonly_graph_key), they do not drop the set.
+    def _wonly_graph_state(self):
+        """What the weights-only token asks apart from the layers: the knobs, the state, eval(), no simulation / autocast / autograd."""
+        return (engine.WEIGHT_ONLY_GRAPH and self._quant_state == (True, False) and engine.WEIGHT_ONLY_KERNEL is not None
+                and not engine.SIMULATE and not engine._autocast_on() and not self.model.training and not torch.is_grad_enabled())
+
+    def _wonly_fingerprint(self):
+        if not self._wonly_graph_state():
+            return None, None
+        keys, tens = [], []
+        for m in self.model.modules():
+            if isinstance(m, QuantModule):
+                if not m.wonly_ready():                    # a layer the packer refuses keeps the whole model eager
+                    return None, None
+                wkey, akey = m.plan_keys()
+                keys.append((wkey, akey[2]))
+                tens += m.state_tensors()
+            elif isinstance(m, (nn.GroupNorm, nn.LayerNorm)):
+                keys.append(tuple((id(t), t.data_ptr()) for t in (m.weight, m.bias) if torch.is_tensor(t)))
+        return tuple(keys), tens
+
+    def _wonly_token(self):
+        """>= 0: engine.WEIGHT_ONLY_GRAPH is set, the model is in eval() in state (True, False) outside autocast / autograd /
+        simulation, EVERY QuantModule takes the weights-only kernel, and nothing its plans were made from has changed since this
+        number was handed out; -1 otherwise.  The fast path is _state_token's (engine.STATE_GENERATION and the version sum);
+        the knob, the mode and autocast are asked every time.  Never re-derives under stream capture."""
+        d = self.__dict__
+        if not self._wonly_graph_state():
+            return -1
+        gen = engine.STATE_GENERATION[0]
+        tens = d.get("_wtok_tensors")
+        # (the plans are per operand type: a flip of the layer knob re-derives, and finds the same keys)
+        if (d.get("_wtok_gen") == gen and d.get("_wtok_dt") == engine.WEIGHT_ONLY_KERNEL
+                and (tens is None or self._vsum(tens) == d["_wtok_vsum"])):
+            return d["_wtok"]
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            return d.get("_wtok", -1)
+        keys, tens = self._wonly_fingerprint()
+        if keys is None:
+            d["_wtok"], d["_wtok_keys"] = -1, None
+        elif d.get("_wtok_keys") != keys:
+            d["_wtok_serial"] = d.get("_wtok_serial", -1) + 1
+            d["_wtok"], d["_wtok_keys"] = d["_wtok_serial"], keys
+        else:
+            d["_wtok"] = d["_wtok_serial"]
+        d["_wtok_tensors"], d["_wtok_vsum"] = tens, (self._vsum(tens) if tens is not None else 0)
+        d["_wtok_gen"], d["_wtok_dt"] = engine.STATE_GENERATION[0], engine.WEIGHT_ONLY_KERNEL
+        return d["_wtok"]
+
+    @staticmethod
+    def _wonly_graph_key():
+        """Every weights-only knob: flipping one selects another graph of the set."""
+        return ("wonly", engine.WEIGHT_ONLY_KERNEL, engine.WEIGHT_ONLY_ATTN, engine.WEIGHT_ONLY_FUSE, engine.WEIGHT_ONLY_FUSE_WIDE,
+                engine.WEIGHT_ONLY_SPLITK, engine.WEIGHT_ONLY_FUSE_MOD, engine.WEIGHT_ONLY_FUSE_DDIM, engine.WEIGHT_ONLY_TEMB)
+
+    def _drop_graphs(self):
+        """The graph set becomes empty: the pool handle goes with it.  The allocator keeps a pool whose graphs are gone only
+        while a block of it is live, and refuses a capture into a pool without users: the next capture asks for a fresh one."""
+        self._graphs.clear()
+        self._graph_seen.clear()
+        self.__dict__["_graph_pool"] = None
+
+    def _wonly_prewarm(self, x, timesteps, context):
+        """One eager evaluation on the stream torch.cuda.graph captures on, BEFORE the capture: scratch keyed by stream (the shared
+        split-K scratch, the GroupNorm workspace) is then allocated outside the graph's pool, and the capture finds it.  The
+        warm-up evaluations of GraphedUNet run on a stream of their own and cover what is keyed otherwise (plans, descriptor
+        tables, attributes set on first use)."""
+        if torch.cuda.graph.default_capture_stream is None:
+            torch.cuda.graph.default_capture_stream = torch.cuda.Stream()
+        cap, cur = torch.cuda.graph.default_capture_stream, torch.cuda.current_stream()
+        cap.wait_stream(cur)
+        with torch.cuda.stream(cap), torch.no_grad():
+            self.model(x, timesteps, context) if context is not None else self.model(x, timesteps)
+        cur.wait_stream(cap)
+
     def _select_stream(self):
         """fp16 activation stream (engine.STREAM_DTYPE) only for evaluations that run entirely on the integer path."""
         if engine.STREAM_DTYPE == torch.float32:
@@ -366,18 +446,22 @@ class QuantModel(nn.Module):
         ckv = self.__dict__.get("_ctx_kv")
         cuda = torch.is_tensor(x) and x.is_cuda
         capturing = cuda and torch.cuda.is_current_stream_capturing()
-        tok = -1
+        tok = wtok = -1
         if not torch.is_grad_enabled() and not self.model.training and not capturing:
             tok = self._state_token()
+            if tok < 0 and engine.WEIGHT_ONLY_GRAPH and self._graphs is not None:
+                wtok = self._wonly_token()
+        # the token the graph set hangs on: the integer one, or ("w", n) of the weights-only state (engine.WEIGHT_ONLY_GRAPH).
+        # Everything else below that asks `tok >= 0` — the guidance pair, the prepared context — stays integer-only.
+        gtok = tok if tok >= 0 else (("w", wtok) if wtok >= 0 else None)
         entry = None
-        graphs = self._graphs is not None and tok >= 0 and cuda and torch.is_tensor(timesteps)
+        graphs = self._graphs is not None and gtok is not None and cuda and torch.is_tensor(timesteps)
         hooks_own = None                                   # "no foreign hook below the model": counted at most once per evaluation
         if graphs:
             from .graph import GraphedUNet, signature
-            if self._graph_tok != tok:                     # plans were rebuilt: the captured pointers are stale
-                self._graphs.clear()
-                self._graph_seen.clear()
-                self._graph_tok = tok
+            if self._graph_tok != gtok:                    # plans were rebuilt: the captured pointers are stale
+                self._drop_graphs()
+                self._graph_tok = gtok
                 self.__dict__["_hook_tables"] = None
             # a replay runs no Python: with a foreign hook below the model (calibration capture, recorders — registered at any
             # time, also AFTER a graph of this signature was captured) the evaluation stays eager
@@ -417,7 +501,10 @@ class QuantModel(nn.Module):
         engine._PAIR[0], engine._PAIR_TAKEN[0] = pair, False
         try:
             if graphs:
-                key = signature(x, timesteps, context) + (engine.STREAM_DTYPE, None if entry is None else entry["slot"], pair)
+                if tok >= 0:
+                    key = signature(x, timesteps, context) + (engine.STREAM_DTYPE, None if entry is None else entry["slot"], pair)
+                else:
+                    key = signature(x, timesteps, context) + self._wonly_graph_key()
                 g = self._graphs.get(key)
                 if g is None:
                     if len(self._graph_seen) > 256:
@@ -429,6 +516,10 @@ class QuantModel(nn.Module):
                             old = next(iter(self._graphs))
                             logger.info("HIP graph of signature %s dropped (QDIFF_HIP_GRAPH_MAX=%d)", old[:5], _MAX_GRAPHS)
                             self._graphs.pop(old)
+                        if not self._graphs:               # (evicted down to zero: QDIFF_HIP_GRAPH_MAX=1)
+                            self.__dict__["_graph_pool"] = None
+                        if tok < 0:
+                            self._wonly_prewarm(x, timesteps, context)
                         # ONE private memory pool for all captures of this model: replays are serialised on the launch stream,
                         # so the activations of different signatures may share the same bytes
                         pool = self.__dict__.get("_graph_pool")
@@ -436,6 +527,11 @@ class QuantModel(nn.Module):
                             pool = self.__dict__["_graph_pool"] = torch.cuda.graph_pool_handle()
                         g = self._graphs[key] = GraphedUNet(self, x, timesteps, context, pinned=entry is not None, pool=pool)
                         g.pair_taken = engine._PAIR_TAKEN[0]       # the captured walk shared the stretch: so does every replay
+                        if tok < 0:
+                            # the plans of the captured operand type and the descriptor tables outlive a flip of the layer knob
+                            g.keep = ([c[1] for m in self.model.modules() if isinstance(m, QuantModule)
+                                       for c in (m.__dict__.get("_wonly_cache"), m.__dict__.get("_wonly_geglu_cache")) if c],
+                                      list(engine.hip._TEMB_WQ_DESC.values()))
                         logger.info("HIP graph captured for signature %s (%d kept)", key[:5], len(self._graphs))
                 if g is not None:
                     self.pair_evals += 1 if g.pair_taken else 0
@@ -452,7 +548,7 @@ class QuantModel(nn.Module):
     def invalidate_plans(self):
         """Forget every packed weight / epilogue constant / captured graph (see QuantModule.invalidate)."""
         engine.bump_state()
-        self.__dict__["_tok_keys"] = None                  # the next token is a new one even if every key looks the same
+        self.__dict__["_tok_keys"] = self.__dict__["_wtok_keys"] = None      # the next token is a new one even if every key looks the same
         self.release_context()
         for m in self.model.modules():
             if isinstance(m, QuantModule):
@@ -461,6 +557,7 @@ class QuantModel(nn.Module):
         if self._graphs is not None:
             self._graphs = {}
             self._graph_seen = {}
+        self.__dict__["_graph_pool"] = None
 
     def enable_hip_graphs(self, on: bool = True):
         """Replay each (shape, quant-state) UNet evaluation as one HIP graph (qdiff/graph.py), captured the FIRST time a call
@@ -469,6 +566,7 @@ class QuantModel(nn.Module):
         self._graphs = {} if on else None
         self._graph_seen = {}
         self._graph_after = 0
+        self.__dict__["_graph_pool"] = None
 
     def set_running_stat(self, running_stat: bool, sm_only=False):
         """reference :71-87"""

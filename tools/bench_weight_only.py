@@ -38,6 +38,13 @@ LSUN-Churches' shapes at batch 16 (scale-shift norm; norm + 2x2 average; norm + 
 tensors and a device copy of the same bytes.
 
     python tools/bench_weight_only.py --attn --fuse --wide --mod --models churches [--rounds 3] [--mod-shapes]
+
+--graph: every block-level weights-only knob on; the eager walk and the HIP-graph replay
+(engine.WEIGHT_ONLY_GRAPH) alternated --rounds times in one process, best, all values and spread of each side; with --temb the
+replay with the one-launch embedding Linears (engine.WEIGHT_ONLY_TEMB) as a third side; --temb alone alternates that knob on the
+eager walk.  Also the launch count of one evaluation with and without TEMB and the outputs' agreement.
+
+    python tools/bench_weight_only.py --attn --graph --temb --models cifar --batch 64 [--rounds 3]
 """
 import argparse
 import json
@@ -471,6 +478,90 @@ def run_ddim(kind, batch, k, dev, attn, rounds):
     return res
 
 
+def run_graph(kind, batch, k, dev, attn, temb, rounds):
+    """Every block-level weights-only knob on (layer knob fp16, block fusion, wide, mod, DDIM, split-K; the attention knob with
+    --attn).  --graph: engine.WEIGHT_ONLY_GRAPH off / on (eager walk / HIP-graph replay) alternated `rounds` times in one process,
+    engine.WEIGHT_ONLY_TEMB as --temb says.  --graph --temb: under replay, engine.WEIGHT_ONLY_TEMB off / on alternated as well
+    (the knob selects the graph: both stay captured).  --temb alone: the eager walk, TEMB off / on alternated.
+    `launches` counts the calls of the library's launch wrappers during one eager walk (the replayed graph holds the same)."""
+    import bench
+    from qdiff import engine, hip, synthetic
+    qnn, _ = bench.build_quantised_unet(kind, dev)
+    x, t, c = synthetic.synthetic_inputs(kind, batch, seed=0)
+    args = [a.to(dev) for a in (x, t, c) if a is not None]
+    qnn.set_quant_state(True, False)
+    one = lambda: qnn(*args)
+    graph = "graph" in temb[1]
+    res = {"model": kind, "batch": batch, "layer_knob": "fp16", "attn_knob": "fp16" if attn else "off", "fuse": True, "wide": True,
+           "mod": True, "ddim": True, "splitk": True, "evals_timed": k, "rounds": rounds}
+    names = ("WEIGHT_ONLY_KERNEL", "WEIGHT_ONLY_ATTN", "WEIGHT_ONLY_FUSE", "WEIGHT_ONLY_FUSE_WIDE", "WEIGHT_ONLY_FUSE_MOD",
+             "WEIGHT_ONLY_FUSE_DDIM", "WEIGHT_ONLY_SPLITK", "WEIGHT_ONLY_TEMB", "WEIGHT_ONLY_GRAPH")
+    prev = {n: getattr(engine, n) for n in names}
+
+    def launches():
+        wrappers = [n for n in ("conv2d_wq_h16", "rows_to_h16", "groupnorm_h16", "groupnorm_mod_h16", "groupnorm_resample_h16",
+                                "layernorm_h16", "geglu_h16", "attn_h16", "temb_mlp_wq_h16") if hasattr(hip, n)]
+        orig, n = {w: getattr(hip, w) for w in wrappers}, [0]
+        for w in wrappers:
+            setattr(hip, w, (lambda f: lambda *a, **kw: (n.__setitem__(0, n[0] + 1), f(*a, **kw))[1])(orig[w]))
+        try:
+            with torch.no_grad():
+                one()
+            torch.cuda.synchronize()
+        finally:
+            for w in wrappers:
+                setattr(hip, w, orig[w])
+        return n[0]
+
+    try:
+        engine.set_weight_only_kernel(torch.float16)
+        engine.set_weight_only_attention(torch.float16 if attn else None)
+        for f in (engine.set_weight_only_fusion, engine.set_weight_only_fusion_wide, engine.set_weight_only_fusion_mod,
+                  engine.set_weight_only_fusion_ddim, engine.set_weight_only_splitk):
+            f(True)
+        sides = {}                                               # name -> (graph, temb)
+        if graph:
+            sides["eager"], sides["replay"] = (False, temb[0]), (True, temb[0])
+            if temb[0]:
+                sides["eager"], sides["replay"] = (False, False), (True, False)
+                sides["replay_temb"] = (True, True)
+        else:
+            sides["temb_off"], sides["temb_on"] = (False, False), (False, True)
+        qnn.enable_hip_graphs(True)                              # capture on first sight; only the knob decides whether anything is captured
+        times = {name: [] for name in sides}
+        res["box_probe_mfma_ms"] = round(hip.box_probe(dev, 0, 512, 60000)[0], 3)
+        for _ in range(rounds):                                  # alternated
+            for name, (g, te) in sides.items():
+                engine.set_weight_only_graph(g)
+                engine.set_weight_only_temb(te)
+                times[name].append(_timed(one, k))
+        res["box_probe_mfma_ms_after"] = round(hip.box_probe(dev, 0, 512, 60000)[0], 3)
+        res["graphs_kept"] = len(qnn._graphs)
+        for name, v in times.items():
+            res[f"{name}_ms"], res[f"{name}_ms_all"] = round(min(v), 3), [round(u, 3) for u in v]
+            res[f"{name}_spread_ms"] = round(max(v) - min(v), 3)
+        outs = {}
+        engine.set_weight_only_graph(False)
+        for name, (g, te) in sides.items():
+            engine.set_weight_only_graph(g)
+            engine.set_weight_only_temb(te)
+            with torch.no_grad():
+                outs[name] = one().clone()
+        torch.cuda.synchronize()
+        engine.set_weight_only_graph(False)
+        for te in sorted({te for _, te in sides.values()}):
+            engine.set_weight_only_temb(te)
+            res[f"launches_temb_{'on' if te else 'off'}"] = launches()
+        first = next(iter(sides))
+        for name in list(sides)[1:]:
+            res[f"{name}_vs_{first}_of_range"] = float((outs[name] - outs[first]).abs().max() / outs[first].abs().max())
+    finally:
+        qnn.enable_hip_graphs(False)
+        for n, v in prev.items():
+            setattr(engine, n, v)
+    return res
+
+
 # the one-head attention of the CIFAR-10 DDIM UNet at batch 64: (B, T, d) of the five 16x16 blocks and of mid.attn_1
 DDIM_ATTN_SHAPES = [(64, 256, 256), (64, 16, 256)]
 
@@ -743,6 +834,10 @@ def main():
                                                         "kernel with --attn), FUSE_DDIM off / on alternated")
     ap.add_argument("--ddim-shapes", action="store_true", help="the DDIM attention alone at B = 64, d = 256, T = 256 and 16: library passes "
                                                                "against the kernel")
+    ap.add_argument("--graph", action="store_true", help="HIP-graph replay of the weights-only state: every block-level knob on, eager / "
+                                                         "replay alternated; with --temb also the one-launch embedding Linears off / on under replay")
+    ap.add_argument("--temb", action="store_true", help="the one-launch embedding Linears (WEIGHT_ONLY_TEMB): alone, off / on alternated on the "
+                                                        "eager walk; with --graph, off / on under replay")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "needs a GPU"
     from qdiff import hip
@@ -761,7 +856,9 @@ def main():
     if a.splitk_shapes:
         splitk_shape_table(dev)
     for kind in [m for m in a.models.split(",") if m]:           # --models "" = the shape tables alone
-        if a.ddim:
+        if a.graph or a.temb:
+            res = run_graph(kind, a.batch, a.evals, dev, a.attn, (a.temb, ("graph",) if a.graph else ()), a.rounds)
+        elif a.ddim:
             res = run_ddim(kind, a.batch, a.evals, dev, a.attn, a.rounds)
         elif a.mod:
             res = run_mod(kind, a.batch, a.evals, dev, a.attn, a.wide, a.rounds)
