@@ -210,6 +210,17 @@ int qd_conv2d_i8_group(const qd_conv_desc* const* descs, int n, void* stream);
  * read); 0 when the layer is launched unsplit. */
 int64_t qd_conv2d_i8_splitk_ws_bytes(const qd_conv_desc* d);
 
+/* Launch-form query (ABI v20, additive; a pure host function): form4 = {rows per block, columns per block, threads per block,
+ * K slices} of the launch qd_conv2d_i8(d, stream) would make NOW — the state of qd_conv_config and of the environment knobs
+ * the library read (QD_KGROUPS, QD_WIDE_MINK, QD_WIDE_MINBLK, QD_SPLITK_TARGET) included; d->splitk_ws / splitk_ws_bytes decide
+ * as they do for the launch (K slices > 1 = the split-K schedule: that many partial contractions plus the finalise pass).
+ * Threads per block is 512 for the two-K-group block of qd_conv_config, 256 otherwise.  The descriptor goes through the
+ * launcher's own checks and tile choice with the launch withheld, so the answer cannot drift from the launcher; it returns
+ * non-zero with qd_last_error wherever qd_conv2d_i8 would refuse the descriptor.  Nothing is launched and no pointer of the
+ * descriptor is followed (null tests and alignment only).  For tests, which assert with it the tile a case was written for,
+ * and for tools; not on any launch path.  The exact-accumulator hook qd_conv2d_i8_acc always takes 128-row tiles. */
+int qd_conv2d_i8_form(const qd_conv_desc* d, int32_t* form4);
+
 /* K2b  tile-ordered int4 packer for the LDS-DMA contraction kernel (csrc/igemm_dma.hip).  Same code
  *     formula as qd_pack_weights (adaptive_rounding.py:49-59).  Output wt[kstep][ntile][1024 B]:
  *     kstep enumerates (tap, 64-channel step) of the slice starting at kstep0, ntile = n/32, and each

@@ -1424,7 +1424,9 @@ constexpr int kgroups_min_steps() { return 8; }
 // qd_conv2d_i8_group runs every member through run() — all its checks, its tile choice — with this set: dispatch() then
 // records the finished kernel descriptor and the tile it would have launched instead of launching, and run() returns right
 // after it (no split-K finalise pass, no launch check).
-struct GroupCapture { ConvD k; int out, tile; bool split; };
+// qd_conv2d_i8_form probes the same way with `query` set: the tile choice then stays the single launch's own (a member of a
+// grouped launch takes 128 rows, want_mt2 in run()), and bm / bn / threads / nsplit describe the launch dispatch() withheld.
+struct GroupCapture { ConvD k; int out = 0, tile = 0; bool split = false, query = false; int bm = 0, bn = 0, threads = 0, nsplit = 0; };
 thread_local GroupCapture* g_capture = nullptr;
 constexpr int tile_code(int MT, int NT, int WM, int WN, int WB) { return (((MT * 16 + NT) * 8 + WM) * 8 + WN) * 32 + WB; }
 
@@ -1433,10 +1435,14 @@ int dispatch(ConvD& k, bool split, int out, hipStream_t st, int nsplit = 1) {
     constexpr int BM = 32 * MT * WM, BN = 32 * NT * WN;
     k.nblk_m = (k.M + BM - 1) / BM;
     k.nblk_n = (k.Cout + BN - 1) / BN;
-    if (g_capture) {
-        *g_capture = GroupCapture{k, out, nsplit == 1 ? tile_code(MT, NT, WM, WN, WB) : -1, split};
-        return 0;
-    }
+    // a probe records the launch at the point where it would be made (so that the block form is known) and launches nothing
+    auto probe = [&](int threads) {
+        if (!g_capture) return false;
+        GroupCapture& c = *g_capture;
+        c.k = k; c.out = out; c.tile = nsplit == 1 ? tile_code(MT, NT, WM, WN, WB) : -1; c.split = split;
+        c.bm = BM; c.bn = BN; c.threads = threads; c.nsplit = nsplit;
+        return true;
+    };
     // At most one tile per CU and a K loop worth splitting: two K-groups in a 512-thread block (igemm_body, KS = 2) — linear rows
     // on every tile shape, split-K partials and the head-layout epilogues on the shapes the three UNets launch them with
     if constexpr (WB <= 8 && (WM == 4 || (MT == 2 && NT == 5)) && (NT == 4 || NT == 5 || NT == 7) && (WB == 4 || NT == 4)) {
@@ -1444,7 +1450,7 @@ int dispatch(ConvD& k, bool split, int out, hipStream_t st, int nsplit = 1) {
         const int ksteps = out == O_PART ? k.it_per : k.taps * k.seg[0].nsteps_tap;
         if (kgroups_knob() && !split && k.nseg == 1 && nb <= 256 && ksteps >= kgroups_min_steps()) {
             dim3 grid2(k.nblk_m * k.nblk_n, nsplit), block2(512);
-#define QD_K2(O) { hipLaunchKernelGGL((igemm_k2_kernel<MT, NT, WM, WN, O, WB>), grid2, block2, 0, st, k); return 0; }
+#define QD_K2(O) { if (!probe(512)) hipLaunchKernelGGL((igemm_k2_kernel<MT, NT, WM, WN, O, WB>), grid2, block2, 0, st, k); return 0; }
             if (out == O_F32) QD_K2(O_F32)
             if constexpr (NT == 5 && MT == 1) { if (out == O_F16) QD_K2(O_F16) }        // (fp16 rows on the 256-row tiles spill: four-wave block)
             if constexpr (MT == 1 && WM == 4 && ((WB == 4 && (NT == 5 || NT == 7)) || (WB == 8 && NT == 4))) { if (out == O_PART) QD_K2(O_PART) }
@@ -1455,7 +1461,7 @@ int dispatch(ConvD& k, bool split, int out, hipStream_t st, int nsplit = 1) {
     dim3 grid(k.nblk_m * k.nblk_n, nsplit), block(256);
 #define QD_CASE(SP, O)                                                                              \
     if (split == SP && out == O) {                                                                  \
-        hipLaunchKernelGGL((igemm_kernel<MT, NT, WM, WN, SP, O, WB>), grid, block, 0, st, k);       \
+        if (!probe(256)) hipLaunchKernelGGL((igemm_kernel<MT, NT, WM, WN, SP, O, WB>), grid, block, 0, st, k); \
         return 0;                                                                                   \
     }
     if constexpr (WB == 16) {
@@ -1645,7 +1651,7 @@ int run(const qd_conv_desc* d, int32_t* iout, void* stream) {
         if (split || !mt2_ok || out == O_I32) return false;
         // members of a grouped launch take 128-row tiles: three times the blocks fill the chip anyway, and the smaller tile's
         // epilogue tail is shorter (heads_i8_out 1.82 -> 1.74 ms per SD evaluation, profiles/r06_group_ab.md)
-        if (g_capture) return false;
+        if (g_capture && !g_capture->query) return false;
         return blocks(256, bn) >= 256;
     };
     if (w8) {                                      // int8 weights (CIFAR W8A8): 128-wide N tiles
@@ -1815,7 +1821,7 @@ int run_group(const qd_conv_desc* const* descs, int n, void* stream) {
     QD_REQUIRE(descs && n >= 1 && n <= 3, "qd_conv2d_i8_group: 1..3 descriptors");
     for (int i = 0; i < n; ++i)
         QD_REQUIRE(!descs[i] || descs[i]->res_period == 0, "qd_conv2d_i8_group: res_period is not supported (head-layout epilogues)");
-    GroupCapture cap[3];
+    GroupCapture cap[3] = {};
     bool ok = n >= 2;
     for (int i = 0; i < n && ok; ++i) {
         QD_REQUIRE(descs[i] != nullptr, "qd_conv2d_i8_group: null descriptor");
@@ -1847,6 +1853,19 @@ int run_group(const qd_conv_desc* const* descs, int n, void* stream) {
         const int rc = run(descs[i], nullptr, stream);
         if (rc) return rc;
     }
+    return 0;
+}
+
+// The launch form qd_conv2d_i8(d) would take now, found by running run() itself as a probe: no second copy of the policy.
+extern "C" int qd_conv2d_i8_form(const qd_conv_desc* d, int32_t* form4) {
+    QD_REQUIRE(form4 != nullptr, "qd_conv2d_i8_form: null form4");
+    GroupCapture cap{};
+    cap.query = true;
+    g_capture = &cap;
+    const int rc = run(d, nullptr, nullptr);
+    g_capture = nullptr;
+    if (rc) return rc;
+    form4[0] = cap.bm; form4[1] = cap.bn; form4[2] = cap.threads; form4[3] = cap.nsplit;
     return 0;
 }
 

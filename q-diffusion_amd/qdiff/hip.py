@@ -63,7 +63,7 @@ EPI_GEGLU_H16 = 4          # qd_conv2d_wq_h16 only: value * gelu(gate) -> operan
 
 EXPORTS = ["qd_abi_version", "qd_last_error", "qd_device_ok", "qd_box_probe", "qd_make_qparams", "qd_quantize_act", "qd_pack_weights", "qd_pack_weights_t4",
            "qd_pack_weights_t8",
-           "qd_conv2d_i8", "qd_conv_config", "qd_conv2d_i8_group", "qd_conv2d_i8_splitk_ws_bytes",
+           "qd_conv2d_i8", "qd_conv_config", "qd_conv2d_i8_group", "qd_conv2d_i8_splitk_ws_bytes", "qd_conv2d_i8_form",
            "qd_conv2d_i8_acc", "qd_groupnorm_ws_bytes", "qd_groupnorm_silu_quant", "qd_groupnorm_mod_silu_quant", "qd_layernorm_quant",
            "qd_geglu_quant", "qd_quantize_heads", "qd_attn_i8", "qd_attn_i8_qp", "qd_attn_keyterm", "qd_attn_uses_keyterm", "qd_attn_config", "qd_attn_ws_bytes", "qd_bmm_qk_i8", "qd_bmm_pv_i8", "qd_temb_mlp", "qd_temb_mlp_wq_h16",
            "qd_fakequant_blocks", "qd_fakequant_fwd", "qd_fakequant_bwd",
@@ -100,6 +100,8 @@ def load():
     lib.qd_conv2d_i8_acc.argtypes = [ctypes.POINTER(ConvDesc), vp, vp]
     lib.qd_conv2d_i8_splitk_ws_bytes.argtypes = [ctypes.POINTER(ConvDesc)]
     lib.qd_conv2d_i8_splitk_ws_bytes.restype = ctypes.c_int64
+    if hasattr(lib, "qd_conv2d_i8_form"):        # (as qd_attn_i8_qp below: an A/B library of an earlier revision has none)
+        lib.qd_conv2d_i8_form.argtypes = [ctypes.POINTER(ConvDesc), vp]
     lib.qd_groupnorm_silu_quant.argtypes = [vp, i32, i64, i64, i32, i64, i32, f32, vp, vp, i32, vp, i32, i32, i32, vp,
                                             i64, vp, i64, vp, vp, i32, i64, ctypes.POINTER(RawQuant), vp]
     lib.qd_groupnorm_mod_silu_quant.argtypes = [vp, i32, i64, i64, i32, i64, i32, f32, vp, vp, i32, vp, i32, i32, i32, vp,
@@ -284,18 +286,32 @@ def splitk_ws_bytes(c):
     return int(load().qd_conv2d_i8_splitk_ws_bytes(ctypes.byref(_conv_desc(c))))
 
 
+def _launch_desc(c):
+    """The descriptor conv2d_i8 hands to qd_conv2d_i8 for ConvCall `c`: split-K scratch attached where the library would use it."""
+    d = _conv_desc(c)
+    if c.w_tiled and c.splitk is not False:
+        need = int(load().qd_conv2d_i8_splitk_ws_bytes(ctypes.byref(d)))
+        if need:
+            ws = _splitk_scratch(c.x.device, need)
+            d.splitk_ws, d.splitk_ws_bytes = ws.data_ptr(), ws.numel()
+    return d
+
+
 def conv2d_i8(c, acc_out=None):
     """c: ConvCall.  segs: list of dicts {c0, clen, kofs, wzp, scale, zc, zw, zfill} (tensors or None)."""
-    d = _conv_desc(c)
     if acc_out is None:
-        if c.w_tiled and c.splitk is not False:
-            need = int(load().qd_conv2d_i8_splitk_ws_bytes(ctypes.byref(d)))
-            if need:
-                ws = _splitk_scratch(c.x.device, need)
-                d.splitk_ws, d.splitk_ws_bytes = ws.data_ptr(), ws.numel()
+        d = _launch_desc(c)
         _check(load().qd_conv2d_i8(ctypes.byref(d), _stream()), "qd_conv2d_i8")
     else:
-        _check(load().qd_conv2d_i8_acc(ctypes.byref(d), _ptr(acc_out), _stream()), "qd_conv2d_i8_acc")
+        _check(load().qd_conv2d_i8_acc(ctypes.byref(_conv_desc(c)), _ptr(acc_out), _stream()), "qd_conv2d_i8_acc")
+
+
+def conv2d_i8_form(c):
+    """(rows per block, columns per block, threads per block, K slices) of the launch conv2d_i8(c) would make now
+    (qd_conv2d_i8_form: the launcher's own checks and tile choice with the launch withheld; nothing runs on the device)."""
+    form = (ctypes.c_int32 * 4)()
+    _check(load().qd_conv2d_i8_form(ctypes.byref(_launch_desc(c)), form), "qd_conv2d_i8_form")
+    return tuple(form)
 
 
 def conv_config(kgroups=-1):

@@ -355,6 +355,54 @@ def splitk_ws_bytes(c):
     return 0
 
 
+def conv2d_i8_form(c, kgroups=None):
+    """qd_conv2d_i8_form for a descriptor the launcher accepts: (rows per block, columns per block, threads per block, K slices).
+    The emulation never splits K, so this is the one-pass launch (K slices = 1, what the library answers without a split-K
+    workspace).  Written from DESIGN.md's description of the tile choice, NOT from the launcher's code: test_host_logic.py holds
+    the library's answer against it over a sweep of shapes, so a change of policy has to be stated twice to pass.
+    kgroups: the qd_conv_config state (None = the library's start-up value, QD_KGROUPS)."""
+    import os
+    env = lambda name, default: int(os.environ.get(name, default))
+    if kgroups is None:
+        kgroups = 0 if os.environ.get("QD_KGROUPS") is not None and env("QD_KGROUPS", 1) == 0 else 1
+    M, N, taps = c.B * c.Ho * c.Wo, c.Cout, c.kh * c.kw
+    epi = getattr(c, "epilogue", 0) or 0
+    heads, geglu, two_seg = epi in (2, 3), epi == 1, len(c.segs) == 2
+    linear = epi == 0
+    f16 = linear and c.out is not None and c.out.dtype == torch.float16
+    blocks = lambda bm, bn: -(-M // bm) * -(-N // bn)
+    # 256-row blocks wherever they still give each of the 256 CUs one: one segment, and with a head-layout epilogue whole blocks
+    # inside one sample
+    tall = lambda bn: not two_seg and (not heads or c.heads["T"] % 256 == 0) and blocks(256, bn) >= 256
+    k_total = taps * c.segs[0]["clen"]
+    wide = False
+    if c.wbits == 8:
+        rows, cols = (256 if linear and tall(128) else 128, 128) if N > 64 else (128, 64)
+    elif geglu:
+        rows, cols = 128, 128
+    elif N % 320 == 0 and linear and not two_seg and k_total >= env("QD_WIDE_MINK", 1280) and blocks(128, 320) >= env("QD_WIDE_MINBLK", 200):
+        rows, cols, wide = 128, 320, True                      # 2 x 2 waves of 64 x 160
+    elif N % 160 == 0:
+        rows, cols = 256 if tall(160) else 128, 160
+    elif N % 224 == 0:
+        rows, cols = 128, 224
+    elif N > 64:
+        rows, cols = 256 if tall(128) else 128, 128
+    else:
+        rows, cols = 128, 64
+    # two K-groups (512 threads): at most one block per CU, one segment, at least eight 64-byte K-steps, on the block forms built
+    # with it — fp32 rows on every tile of 128 columns and more; fp16 rows on the 128 x 160 tile only; head layouts behind int4
+    # weights on the 160-wide tiles; never the GEGLU epilogue
+    ksteps = taps * ((c.segs[0]["clen"] + 63) // 64)
+    k2 = bool(kgroups) and not two_seg and cols >= 128 and blocks(rows, cols) <= 256 and ksteps >= 8
+    if k2:
+        if linear:
+            k2 = not f16 or (cols == 160 and rows == 128)
+        else:
+            k2 = heads and c.wbits == 4 and cols == 160
+    return (rows, cols, 512 if k2 else 256, 1)
+
+
 # ---- first-stage decoder entry points (include/qdiff_hip.h "First-stage decoder"; qdiff.hip wrappers of the same names) ----
 
 def pack_weights_bf16(w, dtype=torch.bfloat16):
@@ -431,6 +479,6 @@ def install(monkeypatch):
     """Replace qdiff.hip's device entry points by the emulation (CPU tensors only)."""
     from qdiff import hip
     for name in ("make_qparams", "quantize_act", "pack_weights", "pack_weights_t4", "pack_weights_t8", "conv2d_i8", "conv2d_i8_group", "groupnorm_ws_bytes", "groupnorm_silu_quant",
-                 "layernorm_quant", "geglu_quant", "quantize_heads", "attn_i8", "attn_keyterm", "attn_uses_keyterm", "splitk_ws_bytes", "bmm_qk_i8", "bmm_pv_i8", "temb_mlp",
+                 "layernorm_quant", "geglu_quant", "quantize_heads", "attn_i8", "attn_keyterm", "attn_uses_keyterm", "splitk_ws_bytes", "conv2d_i8_form", "bmm_qk_i8", "bmm_pv_i8", "temb_mlp",
                  "pack_weights_bf16", "conv2d_bf16", "groupnorm_silu_bf16"):
         monkeypatch.setattr(hip, name, globals()[name])

@@ -35,8 +35,10 @@ def _linear_plan(cuda, K, Cout, g):
                                   torch.randn(Cout, generator=g).to(cuda))
 
 
-def _period_case(cuda, plan, K, Cout, groups, P, hw, dt, gn, splitk, seed):
-    """Rows of `groups` x P outputs whose residual holds P rows, against the same launch on the duplicated residual."""
+def _period_case(cuda, plan, K, Cout, groups, P, hw, dt, gn, splitk, seed, form=None):
+    """Rows of `groups` x P outputs whose residual holds P rows, against the same launch on the duplicated residual.
+    form: the (rows, columns) of the block both launches must take, asserted through qd_conv2d_i8_form."""
+    from conv_tall_tile_cases import launch_forms
     from qdiff import engine
     g = torch.Generator().manual_seed(seed)
     M = groups * P
@@ -44,8 +46,10 @@ def _period_case(cuda, plan, K, Cout, groups, P, hw, dt, gn, splitk, seed):
     xq = engine.quantize_rows(rows, plan, 1, K, M, (0, 1, K))
     res = torch.randn(P, Cout, generator=g).to(cuda).to(dt)
     B = M // hw
-    got = engine.conv_forward(plan, xq, B, 1, hw, residual=res, out_dtype=dt, splitk=splitk, gn_stats=gn, res_period=P)
-    want = engine.conv_forward(plan, xq, B, 1, hw, residual=res.repeat(groups, 1), out_dtype=dt, splitk=False, gn_stats=gn)
+    with launch_forms() as forms:
+        got = engine.conv_forward(plan, xq, B, 1, hw, residual=res, out_dtype=dt, splitk=splitk, gn_stats=gn, res_period=P)
+        want = engine.conv_forward(plan, xq, B, 1, hw, residual=res.repeat(groups, 1), out_dtype=dt, splitk=False, gn_stats=gn)
+    assert form is None or [f[:2] for f in forms] == [form, form], forms
     torch.cuda.synchronize()
     assert torch.isfinite(want.float()).all() and want.float().abs().max() > 0
     assert torch.equal(got, want), (got.float() - want.float()).abs().max().item()
@@ -72,13 +76,18 @@ def test_residual_row_period(cuda, Cout, K, dt):
 @pytest.mark.parametrize("dt", [torch.float32, torch.float16])
 def test_residual_row_period_straddles_a_tile(cuda, dt):
     """The mapping is per row: 6 samples of 64 rows with P = 192 (the second 128-row tile holds rows of two groups), and
-    2 x 16512 rows on 256-row tiles (tile 64 straddles; enough tiles for the 256-row block to be chosen)."""
+    2 x 16512 rows whose period ends inside a block.  Which block the second launch takes depends on the process: N = 320 with
+    K = 64 runs 256 x 160 blocks (130 x 2 of them: block 64 straddles) under the library's default thresholds, and the 128 x 320
+    tile of 2 x 2 waves (block 129 straddles) once test_hip_kernels.py has been imported, which lowers that tile's K threshold to
+    64 through the environment — so in a run of the whole suite this is NOT the 256-row tile; test_conv_tall_tiles_gpu.py has the
+    period on the 256-row tile in either kind of run."""
     g = torch.Generator().manual_seed(5)
     plan = _linear_plan(cuda, 64, 320, g)
-    _period_case(cuda, plan, 64, 320, 2, 192, 64, dt, False, False, 11)
-    _period_case(cuda, plan, 64, 320, 2, 16512, 16512, dt, False, False, 12)
+    wide = int(os.environ.get("QD_WIDE_MINK", "1280")) <= 64
+    _period_case(cuda, plan, 64, 320, 2, 192, 64, dt, False, False, 11, form=(128, 160))           # three row blocks: too few for either
+    _period_case(cuda, plan, 64, 320, 2, 16512, 16512, dt, False, False, 12, form=(128, 320) if wide else (256, 160))
     plan = _linear_plan(cuda, 1024, 160, g)
-    _period_case(cuda, plan, 1024, 160, 4, 192, 64, dt, False, False, 13)
+    _period_case(cuda, plan, 1024, 160, 4, 192, 64, dt, False, False, 13, form=(128, 160))
 
 
 def test_every_other_entry_refuses_a_period(cuda):

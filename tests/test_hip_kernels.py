@@ -254,7 +254,7 @@ os.environ.setdefault("QD_WIDE_MINBLK", "4")      # read once by the library: le
 os.environ.setdefault("QD_WIDE_MINK", "64")
 
 WIDE_CASES = [
-    # name,             B, Cin,  H,  W, Cout, k   — N % 320 == 0: the shapes the 2 x 2-wave tiles (256 x 320, 128 x 320) cover
+    # name,             B, Cin,  H,  W, Cout, k   — N % 320 == 0: the shapes the 128 x 320 tile of 2 x 2 waves covers
     ("n320_ragged_m",   3, 96, 13, 13, 320, 3),   # 507 rows: ragged last M block
     ("n640_k1",         2, 320, 16, 16, 640, 1),
     ("n320_k960",       1, 960, 24, 24, 320, 3),
@@ -264,8 +264,10 @@ WIDE_CASES = [
 @pytest.mark.parametrize("case", WIDE_CASES, ids=[c[0] for c in WIDE_CASES])
 def test_conv_wide_tiles_match_fake_quant(cuda, case):
     """fp32 output (+ row bias + residual) of 320-multiple-wide layers vs the reference's simulation, 2e-5 of range.  These
-    shapes take the 128 x 320 tile of 2 x 2 waves (block-count thresholds lowered through the environment below); the
-    default 256 x 160 / 128 x 160 tiles are covered by the other convolution tests."""
+    shapes take the 128 x 320 tile of 2 x 2 waves (block-count and K thresholds lowered through the environment above; asserted
+    through qd_conv2d_i8_form); the 128 x 160 tile is covered by the other convolution tests, the 256 x 160 tile by
+    test_conv_tall_tiles_gpu.py."""
+    from conv_tall_tile_cases import launch_forms, one_form
     from qdiff import engine
     _, B, Cin, H, W, Cout, k = case
     g = torch.Generator().manual_seed(23)
@@ -279,7 +281,9 @@ def test_conv_wide_tiles_match_fake_quant(cuda, case):
     xq = engine.quantize_rows(x.to(cuda), plan, B, Cin, H * W, (Cin * H * W, H * W, 1))
     rowbias = torch.randn(B, Cout, generator=g).to(cuda)
     residual = torch.randn(B * H * W, Cout, generator=g).to(cuda)
-    a = engine.conv_forward(plan, xq, B, H, W, rowbias=rowbias, residual=residual, splitk=False)
+    with launch_forms() as forms:
+        a = engine.conv_forward(plan, xq, B, H, W, rowbias=rowbias, residual=residual, splitk=False)
+    one_form(forms, 128, 320)
     torch.cuda.synchronize()
     want = R.quant_module_forward(x, w, bias, "conv2d", dict(stride=1, padding=k // 2),
                                   [dict(delta=q.delta, zero_point=q.zero_point, alpha=q.alpha, n_levels=q.n_levels)],
@@ -843,22 +847,38 @@ def test_attention_keyterm_table(cuda):
         assert torch.equal(got.cpu(), want)
 
 
-@pytest.mark.parametrize("B,Cin,H,Cout,k,wbits,dt", [
-    (2, 1280, 16, 1280, 3, 4, torch.float32),      # SD 16 x 16 level: 128 x 160 tiles, 180 K-steps
-    (4, 640, 32, 640, 3, 4, torch.float32),        # SD 32 x 32 level: the 128 x 320 tile of 2 x 2 waves, 90 K-steps
-    (1, 320, 64, 320, 3, 4, torch.float32),        # 256-row tiles, 45 K-steps (odd: the second group's last round is a zero stage)
-    (2, 1280, 16, 1280, 1, 4, torch.float32),      # 1 x 1, 20 K-steps (+ head-layout epilogues: 8 heads of 160)
-    (2, 640, 16, 320, 1, 4, torch.float32), (16, 1280, 8, 1280, 3, 4, torch.float32),       # heads of 40 on 10 steps; 8 x 8 level: split-K partials
-    (2, 1920, 16, 1280, 3, 4, torch.float32), (3, 200, 16, 320, 3, 4, torch.float32),       # K tail (200 = 3 x 64 + 8), odd step counts
-    (2, 448, 32, 448, 3, 4, torch.float32), (2, 672, 16, 896, 1, 4, torch.float32),         # LDM-4: 224-wide tiles
-    (8, 256, 16, 256, 3, 8, torch.float32), (4, 128, 32, 128, 3, 8, torch.float32), (2, 192, 16, 64, 3, 4, torch.float32),  # CIFAR int8 / 128- and 64-wide
-    (2, 1280, 16, 1280, 3, 4, torch.float16), (4, 640, 32, 640, 3, 4, torch.float16)])
+# The block form each case below must take WITH two K-groups, asserted through qd_conv2d_i8_form: (rows, columns, threads); without
+# them the same tile on 256 threads.  Every N % 320 == 0 case runs the 128 x 320 tile of 2 x 2 waves here, whatever its K and
+# block count: this file lowers that tile's thresholds through the environment (QD_WIDE_MINBLK / QD_WIDE_MINK above).  The
+# 128 x 160 and 256-row forms of the variant are compared in test_random_shapes_gpu.py (N = 160) and test_conv_tall_tiles_gpu.py.
+_K2_CASES = [
+    ((2, 1280, 16, 1280, 3, 4, torch.float32), (128, 320, 512)),     # SD 16 x 16 level: 180 K-steps
+    ((4, 640, 32, 640, 3, 4, torch.float32), (128, 320, 512)),       # SD 32 x 32 level: 90 K-steps
+    ((1, 320, 64, 320, 3, 4, torch.float32), (128, 320, 512)),       # 45 K-steps (odd: the second group's last round is a zero stage)
+    ((2, 1280, 16, 1280, 1, 4, torch.float32), (128, 320, 512)),     # 1 x 1, 20 K-steps (+ head-layout epilogues: 8 heads of 160)
+    ((2, 640, 16, 320, 1, 4, torch.float32), (128, 320, 512)),       # heads of 40 on 10 steps
+    ((16, 1280, 8, 1280, 3, 4, torch.float32), (128, 320, 512)),     # 8 x 8 level: split-K partials (second half of the test)
+    ((2, 1920, 16, 1280, 3, 4, torch.float32), (128, 320, 512)),
+    ((3, 200, 16, 320, 3, 4, torch.float32), (128, 320, 512)),       # K tail (200 = 3 x 64 + 8), odd step counts
+    ((2, 448, 32, 448, 3, 4, torch.float32), (128, 224, 512)),       # LDM-4: 224-wide tiles
+    ((2, 672, 16, 896, 1, 4, torch.float32), (128, 224, 512)),
+    ((8, 256, 16, 256, 3, 8, torch.float32), (128, 128, 512)),       # CIFAR int8: 128-wide
+    ((4, 128, 32, 128, 3, 8, torch.float32), (128, 128, 512)),
+    ((2, 192, 16, 64, 3, 4, torch.float32), (128, 64, 256)),         # 64-wide: no two-K-group form, compares trivially equal
+    ((2, 1280, 16, 1280, 3, 4, torch.float16), (128, 320, 256)),     # fp16 rows on the 128 x 320 tile: the four-wave block only,
+    ((4, 640, 32, 640, 3, 4, torch.float16), (128, 320, 256))]       # trivially equal (the variant's fp16 form is the 128 x 160 tile's)
+_K2_FORMS = dict(_K2_CASES)
+
+
+@pytest.mark.parametrize("B,Cin,H,Cout,k,wbits,dt", [c for c, _ in _K2_CASES])
 def test_conv_two_k_groups_equal_the_four_wave_block(cuda, B, Cin, H, Cout, k, wbits, dt):
     """Round 6: launches with at most one tile per CU run 512-thread blocks whose two groups of four waves contract alternate
     K-steps and add their int32 accumulators in LDS (igemm_body, KS = 2).  Integer adds commute: the output — rows, with
     row bias, residual and GroupNorm statistics of the epilogue — equals the four-wave kernel's bit for bit (qd_conv_config
     switches the variant; shapes the variant is not built for fall back and compare trivially equal)."""
+    from conv_tall_tile_cases import launch_forms
     from qdiff import engine, hip
+    form = _K2_FORMS[(B, Cin, H, Cout, k, wbits, dt)]
     g = torch.Generator().manual_seed(61)
     x = F.silu(torch.randn(B, Cin, H, H, generator=g))
     w = torch.randn(Cout, Cin, k, k, generator=g) * 0.05
@@ -873,7 +893,9 @@ def test_conv_two_k_groups_equal_the_four_wave_block(cuda, B, Cin, H, Cout, k, w
     try:
         for kg in (1, 0):
             hip.conv_config(kgroups=kg)
-            o = engine.conv_forward(plan, xq, B, H, H, rowbias=rowbias, residual=residual, out_dtype=dt, splitk=False, gn_stats=(H * H) % 128 == 0)
+            with launch_forms() as forms:
+                o = engine.conv_forward(plan, xq, B, H, H, rowbias=rowbias, residual=residual, out_dtype=dt, splitk=False, gn_stats=(H * H) % 128 == 0)
+            assert forms == [(form[0], form[1], form[2] if kg else 256, 1)], forms
             torch.cuda.synchronize()
             outs[kg] = (o.clone(), getattr(o, "qd_gn_part", None))
     finally:

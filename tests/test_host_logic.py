@@ -118,6 +118,103 @@ def test_ctypes_signatures_match_the_header_prototypes():
         assert [ctypes_kind(c) for c in at] == want, name
 
 
+from conv_form_util import FAKE as _FAKE, form as _form, form_case as _form_case          # noqa: E402
+
+
+@pytest.fixture
+def conv_lib():
+    from qdiff import hip
+    lib = hip.load()
+    start = 0 if os.environ.get("QD_KGROUPS") is not None and int(os.environ["QD_KGROUPS"]) == 0 else 1
+    lib.qd_conv_config(start)
+    yield lib
+    lib.qd_conv_config(start)
+
+
+def test_conv_launch_form_query_states_the_tile_policy(conv_lib):
+    """qd_conv2d_i8_form is the launcher itself with the launch withheld — a pure host function, so it runs here on fake
+    pointers — and abi_emulator.conv2d_i8_form is the tile policy written down from DESIGN.md.  They agree on every shape of a
+    sweep across the break points of the policy (block counts around 256, the width classes, K-step counts around eight, one and
+    two segments, every epilogue), with and without two K-groups, and on the benchmark's own hot launches: whoever changes the
+    policy changes this statement of it too, and the GPU tests that assert their tile by the query keep meaning what they say."""
+    lib = conv_lib
+    cases = []
+    for M_shape in ((1, 1, 96), (2, 16, 16), (8, 16, 16), (16, 32, 32), (31, 16, 16), (32, 16, 16), (51, 16, 16), (52, 16, 16), (125, 8, 8),
+                    (130, 10, 10), (1, 1, 13256), (16, 64, 64)):
+        for N in (32, 64, 96, 128, 160, 224, 320, 448, 640, 800, 1000, 1002, 1024, 1280):
+            for k, clens in ((1, [64]), (1, [320]), (1, [512]), (3, [16]), (3, [80]), (3, [320]), (3, [640]), (1, [320, 160]), (3, [64, 64])):
+                for wbits in (4, 8):
+                    for f16 in (False, True):
+                        cases.append(_form_case(M_shape, N, k, clens, wbits, f16))
+    from qdiff import hip
+    for B, T in ((2, 128), (2, 256), (32, 256), (52, 256), (64, 384), (16, 4096)):
+        for N, heads in ((320, 8), (800, 5), (1024, 8), (448, 14), (256, 1)):
+            for clen in (64, 320, 1024):
+                for epi in (hip.EPI_HEADS_I8, hip.EPI_HEADS_T_I8):
+                    cases.append(_form_case((B, 1, T), N, 1, [clen], 4, False, epi, T, heads))
+                    if N > 64:
+                        cases.append(_form_case((B, 1, T), N, 1, [clen], 8, False, epi, T, heads))
+    for M in (128, 4096, 32768):
+        cases.append(_form_case((1, 1, M), 2560, 1, [320], 4, False, hip.EPI_GEGLU_I8))
+    seen = set()
+    for kg in (1, 0):
+        lib.qd_conv_config(kg)
+        for d, call in cases:
+            got = _form(lib, d)
+            assert got == abi_emulator.conv2d_i8_form(call, kgroups=kg), (kg, call.B, call.Ho, call.Wo, call.Cout, call.kh, [s["clen"] for s in call.segs],
+                                                                        call.wbits, call.out.dtype, call.epilogue, got)
+            seen.add(got[:3])
+    # the sweep reaches every block form the launcher has for these weights
+    assert {(256, 160, 256), (256, 128, 256), (128, 160, 256), (128, 160, 512), (128, 128, 512), (128, 320, 256), (128, 224, 256), (128, 64, 256),
+            (256, 160, 512), (256, 128, 512)} <= seen, sorted(seen)
+
+
+def test_conv_launch_form_query_on_the_benchmark_shapes(conv_lib):
+    """Batch 16 (eight images and guidance) at the 64 x 64 level of the SD UNet, 320 channels, with the library's DEFAULT knobs
+    (a child process started without them: this process may carry the values test_hip_kernels.py sets at import): the 1 x 1
+    layers and the q / v projections (T = 4096) run 256 x 160 blocks, the long-K 3 x 3 layers the 128 x 320 tile of 2 x 2
+    waves, a two-segment launch 128 rows.  In this process, whatever its knobs: a head layout whose sample is no multiple of 256
+    rows stays on 128 rows however many rows there are, and the K slices follow the workspace offered."""
+    import json
+    import subprocess
+    from qdiff import hip
+    import conv_form_util
+    env = {k: v for k, v in os.environ.items() if k not in conv_form_util.KNOBS}
+    r = subprocess.run([sys.executable, conv_form_util.__file__], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    forms = {k: tuple(v) for k, v in json.loads(r.stdout.strip().splitlines()[-1]).items()}
+    assert forms == dict(conv1x1=(256, 160, 256, 1), q_heads=(256, 160, 256, 1), v_heads=(256, 160, 256, 1), conv3x3=(128, 320, 256, 1),
+                         skip_two_segments=(128, 160, 256, 1), conv3x3_32=(128, 320, 512, 1)), forms
+    lib = conv_lib
+    assert _form(lib, _form_case((171, 1, 384), 800, 1, [320], epilogue=hip.EPI_HEADS_I8, T=384, heads=5)[0])[:2] == (128, 160)
+    assert _form(lib, _form_case((171, 1, 256), 800, 1, [320], epilogue=hip.EPI_HEADS_I8, T=256, heads=5)[0])[:2] == (256, 160)
+    # K slices: offered enough scratch, the under-filled long-K layer of the 8 x 8 level is contracted in slices on 128-row blocks
+    d, _ = _form_case((16, 8, 8), 1280, 3, [1280])
+    one_pass = _form(lib, d)
+    need = int(lib.qd_conv2d_i8_splitk_ws_bytes(ctypes.byref(d)))
+    assert need > 0 and one_pass[3] == 1
+    d.splitk_ws, d.splitk_ws_bytes = _FAKE, need
+    sliced = _form(lib, d)
+    assert sliced[:2] == (128, 160) and sliced[3] == need // (16 * 64 * 1280 * 4) >= 2
+    d.splitk_ws_bytes = need - 1                                  # too small a workspace: the one-pass launch, as qd_conv2d_i8 does
+    assert _form(lib, d) == one_pass
+
+
+def test_conv_launch_form_query_refuses_what_the_launcher_refuses(conv_lib):
+    lib = conv_lib
+    form = (ctypes.c_int32 * 4)(-1, -1, -1, -1)
+    assert lib.qd_conv2d_i8_form(None, form) != 0 and "null descriptor" in lib.qd_last_error().decode()
+    d, _ = _form_case((2, 16, 16), 320, 3, [64])
+    assert lib.qd_conv2d_i8_form(ctypes.byref(d), None) != 0 and "form4" in lib.qd_last_error().decode()
+    for field, value, word in (("wbits", 5, "wbits"), ("w_tiled", 0, "tile order"), ("x", 0, "null tensor pointer"), ("ldx", 72, "16-byte aligned"),
+                               ("epilogue", 1, "GEGLU"), ("res_period", 100, "res_period")):
+        d, _ = _form_case((2, 16, 16), 320, 3, [64])
+        setattr(d, field, value)
+        assert lib.qd_conv2d_i8_form(ctypes.byref(d), form) != 0, field
+        assert word in lib.qd_last_error().decode(), (field, lib.qd_last_error().decode())
+    assert tuple(form) == (-1, -1, -1, -1)                        # a refusal writes nothing
+
+
 def test_modulated_groupnorm_entry_validates_its_arguments_on_the_host():
     """qd_groupnorm_mod_silu_quant (ABI v15): the argument checks that precede any device work are reachable without a GPU and
     tell that `mod` / `mod_ld` arrive in the positions the ctypes binding puts them (fake non-null pointers are never
