@@ -296,14 +296,11 @@ class Model(nn.Module):
         self.__dict__["_cat_plan"] = seen
 
         # output head (reference ddim/models/diffusion.py:346-348: norm_out -> swish -> conv_out): on the integer path the
-        # normalisation emits conv_out's int8 rows in one pass (statistics from the last block's epilogue), as UNetModel._out does
+        # normalisation emits conv_out's int8 rows in one pass (quant_block.int_head, as UNetModel._out)
         conv = self.conv_out
         if (isinstance(conv, QuantModule) and qb._int_mode(conv) and conv.split == 0 and conv.kind == 'conv2d'
                 and conv.act_quantizer.inited and h.dim() == 4 and h.shape[1] % 16 == 0):
-            B, C, H, W = h.shape
-            rows = qb._nhwc_rows(h)
-            xq = qb._gn_silu_to(conv, rows, B, H * W, C, self.norm_out)
-            return qb._rows_to_nchw(conv.forward_codes(xq, B, H, W), B, H, W)
+            return qb.int_head(conv, self.norm_out, h)
         if engine.WEIGHT_ONLY_FUSE_DDIM and qb.ddim_head_wonly(self, h):
             return qb.ddim_head_forward_wonly(self, h)      # weights-only state: the same one-producer head on 16-bit operand rows
         if h.dtype != torch.float32:

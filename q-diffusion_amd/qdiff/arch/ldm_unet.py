@@ -560,10 +560,7 @@ class UNetModel(nn.Module):
         if (len(self.out) == 3 and isinstance(self.out[0], nn.GroupNorm) and isinstance(self.out[1], nn.SiLU) and h.dim() == 4
                 and qb._int_mode(conv) and conv.split == 0 and conv.kind == 'conv2d' and conv.act_quantizer.inited
                 and h.shape[1] % 16 == 0):
-            B, C, H, W = h.shape
-            rows = qb._nhwc_rows(h)
-            xq = qb._gn_silu_to(conv, rows, B, H * W, C, self.out[0])
-            return qb._rows_to_nchw(conv.forward_codes(xq, B, H, W), B, H, W)
+            return qb.int_head(conv, self.out[0], h)
         return self.out(h)
 
 

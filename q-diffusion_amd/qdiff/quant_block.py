@@ -14,6 +14,7 @@ import logging
 import math
 import os
 from types import MethodType
+from typing import Callable, NamedTuple, Optional
 
 import torch
 import torch as th
@@ -167,6 +168,11 @@ def _out_features(m):
     return w.shape[0] if torch.is_tensor(w) and w.dim() >= 2 and w.numel() else None
 
 
+def _one_tap(plan):
+    """A one-tap stride-1 layer without padding: a Linear on every row."""
+    return (plan.kh, plan.kw, plan.stride, plan.pad) == (1, 1, 1, 0)
+
+
 def _wonly_wide_edges(block, x, first, last, C, Cmid):
     """engine.WEIGHT_ONLY_FUSE_WIDE takes the edges of a SpatialTransformer / QuantAttentionBlock: the gate of the fused route
     (_wonly_fuse_gate on the two projections: knobs, fp32 GPU input, unsplit, wonly_ready, no hook below the block), an
@@ -177,8 +183,7 @@ def _wonly_wide_edges(block, x, first, last, C, Cmid):
     if not _wonly_fuse_gate(block, (first, last), (x,)):
         return False
     pf, pl = first.wonly_plan(), last.wonly_plan()
-    one_tap = lambda p: (p.kh, p.kw, p.stride, p.pad) == (1, 1, 1, 0)
-    return (one_tap(pf) and one_tap(pl) and engine.wonly_plain_plan(pf, C) and engine.wonly_plain_plan(pl, Cmid)
+    return (_one_tap(pf) and _one_tap(pl) and engine.wonly_plain_plan(pf, C) and engine.wonly_plain_plan(pl, Cmid)
             and pf.Cout % 8 == 0 and pl.Cout == C)
 
 
@@ -237,6 +242,14 @@ def _gn_silu_to(conv, rows, B, S, C, gn, silu=True, raw_plan=None, mod=None):
     res = engine.groupnorm_silu_quant(rows, B, S, C, gn, silu, plan=conv.conv_plan(), part=getattr(rows, "qd_gn_part", None),
                                       raw_plan=raw_plan, mod=mod)
     return (res[0], res[2]) if raw_plan is not None else res[0]
+
+
+def int_head(conv, gn, h):
+    """conv(SiLU(gn(h))), the output head of both UNets, on the integer path: the normalisation emits conv's int8 rows in one
+    pass (statistics from the last block's epilogue).  The caller asked its own predicate."""
+    B, C, H, W = h.shape
+    xq = _gn_silu_to(conv, _nhwc_rows(h), B, H * W, C, gn)
+    return _rows_to_nchw(conv.forward_codes(xq, B, H, W), B, H, W)
 
 
 def _ln_to(consumers, rows, M, C, ln):
@@ -349,6 +362,7 @@ class EmbGroup:
         """int_path=False: a member of the weights-only launch only (the integer route of such a block never asked)."""
         self.members.append((blk, linear, int_path))
         blk.__dict__["_emb_group"] = self
+        blk.__dict__.pop("_res_parts", None)
 
     def reset(self):
         """Start of a UNet evaluation (forward pre-hook of the wrapped model): nothing carries over between evaluations —
@@ -829,6 +843,169 @@ class BaseQuantBlock(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------
+# residual blocks: the routes both families share  (reference quant_block.py:83-111, :318-338)
+# ------------------------------------------------------------------------------------------------
+class _ResParts(NamedTuple):
+    """What a residual block hands to the routes below (QuantResBlock._parts, QuantResnetBlock._parts).  Where the two families
+    differ, the difference is one of these parts: the routes never ask whose parts they hold."""
+    block: nn.Module           # the owner: its out_channels, EmbGroup slice, dropout, hooks and (mode 1, 2) h_upd / x_upd are asked of it
+    norm1: nn.Module
+    conv1: nn.Module
+    norm2: nn.Module
+    conv2: nn.Module
+    emb_rows: nn.Module        # emb -> the embedding projection [B][out_channels] (scale | shift: 2 out_channels), a module call
+    emb_act: Optional[Callable]  # applied to emb first where emb_rows does not hold its own activation
+    skip: Optional[nn.Module]  # None: the identity
+    skip_split: bool           # `skip` is told a split != 0 (skip(x, split=split)); else it is always skip(x)
+    skip_reads_x: bool         # `skip` reads the tensor norm1 reads: a 1x1 `skip` may take its int8 rows from that pass
+    split_exact: bool          # ... once it has recorded this very split (else: any split); before, the module call records it
+    cout1: bool                # the weights-only gate asks conv1 for out_channels
+    kind: Optional[str] = None  # the block's engine.WONLY_FUSED counter (the weights-only route's; the integer route names none)
+    mode: Optional[int] = 0    # between norm1 and conv1: 0 nothing, 1 the 2x2 average, 2 nearest 2x; None: what no fused route covers
+    scale_shift: bool = False  # norm2 * (1 + scale) + shift instead of conv1 + projection (reference :99-103)
+
+
+def _parts_of(blk, *key):
+    """blk._parts(*key), gathered once per key (the look-ups cost Python time in every forward).  Kept in blk.__dict__ beside
+    `_emb_group`: no state-dict key, and like the group's members the sub-modules the block had; EmbGroup.register drops it."""
+    hit = blk.__dict__.get("_res_parts")
+    if hit is None or hit[0] != key:
+        hit = blk.__dict__["_res_parts"] = (key, blk._parts(*key))
+    return hit[1]
+
+
+def _res_skip_plan(p, split, C):
+    """ConvPlan of the 1x1 skip connection when its int8 input rows can be produced by the GroupNorm pass that
+    already reads x (engine.groupnorm_silu_quant(raw_plan=...)), else None (the module quantises x itself)."""
+    sk = p.skip
+    if not (_FUSE_SKIP_QUANT and isinstance(sk, QuantModule) and sk.kind == 'conv2d' and _int_mode(sk)):
+        return None
+    if not p.skip_reads_x or (split != 0 and (sk.split != split if p.split_exact else sk.split == 0)):
+        return None                                   # (the first call records the split: module path)
+    if not all(q.inited for q in sk._act_quantizers()) or sk._geometry() != (1, 1, 1, 0):
+        return None
+    plan = sk.conv_plan()
+    return plan if engine.raw_quant_segs(plan, C) is not None else None
+
+
+def _res_forward_int(p, x, emb, split, out_slot=None):
+    """Reference :83-111 on the integer engine.  Plain blocks: GN.SiLU -> int8 (one pass; the skip connection's rows in
+    the same pass), conv1 with the embedding as a row bias and the next norm's statistics in its epilogue, GN.SiLU ->
+    int8, conv2 with the residual in its epilogue.  `updown` blocks (:84-90) resample between the first norm and the
+    first convolution: nearest-2x commutes with the quantiser, so the SMALL map is quantised and its int8 rows are
+    replicated; the 2x2 average does not, so the norm writes fp32 rows, torch averages them (F.avg_pool2d, as the
+    reference) and the small map is quantised.  `use_scale_shift_norm` blocks (:99-103) hand the two halves of the
+    embedding projection to the second norm as a per-sample modulation (qd_groupnorm_mod_silu_quant) instead of
+    adding the projection to h."""
+    B, C, H, W = x.shape
+    S = H * W
+    rows = _nhwc_rows(x)
+    blk, conv1, conv2 = p.block, p.conv1, p.conv2
+    skp = _res_skip_plan(p, split, C)
+    if p.mode == 1:
+        y = engine.groupnorm_silu_quant(rows, B, S, C, p.norm1, True, want_float=True,
+                                        part=getattr(rows, "qd_gn_part", None))[1]
+        hp = blk.h_upd(_rows_to_nchw(y, B, H, W))
+        x = blk.x_upd(x)
+        H, W = H // 2, W // 2
+        S = H * W
+        conv1._init_act_quantizers(hp)
+        hp = _nhwc_rows(hp)
+        xq = engine.quantize_rows(hp, conv1.conv_plan(), 1, C, B * S, (0, 1, hp.stride(0)))
+        rows = _nhwc_rows(x)
+    elif skp is not None:
+        xq, skq = _gn_silu_to(conv1, rows, B, S, C, p.norm1, raw_plan=skp)
+    else:
+        xq = _gn_silu_to(conv1, rows, B, S, C, p.norm1)
+    if p.mode == 2:
+        xq = xq.view(B, H, 1, W, 1, -1).expand(B, H, 2, W, 2, xq.shape[1]).reshape(B * 4 * S, xq.shape[1])
+        x = blk.x_upd(x)
+        H, W = 2 * H, 2 * W
+        S = H * W
+        rows = _nhwc_rows(x)
+    grp = blk.__dict__.get("_emb_group")
+    e = grp.get(blk, emb) if grp is not None else None            # all blocks' projections in one launch (K6)
+    if e is None:
+        e = p.emb_rows(emb if p.emb_act is None else p.emb_act(emb)).float().contiguous()   # SiLU + integer linear -> [B, Cout] (2 Cout: scale | shift)
+    if p.scale_shift:
+        h = conv1.forward_codes(xq, B, H, W, gn_stats=True)
+        if e.stride(1) != 1:
+            e = e.contiguous()
+        hq = _gn_silu_to(conv2, h, B, S, blk.out_channels, p.norm2, mod=e)
+    else:
+        h = conv1.forward_codes(xq, B, H, W, rowbias=e, gn_stats=True)
+        hq = _gn_silu_to(conv2, h, B, S, blk.out_channels, p.norm2)
+    if p.skip is None:
+        res = rows
+    elif skp is not None:
+        res = p.skip.forward_codes(skq, B, H, W)
+    else:
+        res = _nhwc_rows(p.skip(x, split=split) if p.skip_split and split != 0 else p.skip(x))
+    out = conv2.forward_codes(hq, B, H, W, residual=res, gn_stats=True, slot=out_slot)   # the next block normalises this
+    return _rows_to_nchw(out, B, H, W)
+
+
+def _res_wonly_route(p, x, emb):
+    """The fused weights-only route takes this call: p.kind, the name of its engine.WONLY_FUSED counter, or None.  It asks for a
+    4-D map, two nn.GroupNorms, a resampling the producers cover (the 2x2 average of even H, W or nearest 2x), everything
+    _wonly_fuse_gate demands of the two convolutions, and both convolutions reading all their channels as one segment (a
+    multiple of 8: wonly_plain_plan), keeping the (resampled) size, conv2 — and with p.cout1 conv1 — giving out_channels.
+    The knobs are the caller's to ask."""
+    if not torch.is_tensor(x) or x.dim() != 4 or not (isinstance(p.norm1, nn.GroupNorm) and isinstance(p.norm2, nn.GroupNorm)):
+        return None
+    H, W = x.shape[2], x.shape[3]
+    if p.mode is None or (p.mode == 1 and (H % 2 or W % 2)):
+        return None
+    conv1, conv2, oc = p.conv1, p.conv2, p.block.out_channels
+    if not _wonly_fuse_gate(p.block, (conv1, conv2), (x, emb)):
+        return None
+    Hr, Wr = (H // 2, W // 2) if p.mode == 1 else (2 * H, 2 * W) if p.mode == 2 else (H, W)
+    p1, p2 = conv1.wonly_plan(), conv2.wonly_plan()          # (not None: _wonly_fuse_gate asked wonly_ready())
+    # the producers' C % 8 and out_channels % 8 are not asked again: wonly_plain_plan refuses a C that is no multiple of 8
+    if not (conv1.kind == 'conv2d' and conv2.kind == 'conv2d' and engine.wonly_plain_plan(p1, x.shape[1])
+            and engine.wonly_plain_plan(p2, oc) and (p1.Cout == oc or not p.cout1) and p2.Cout == oc
+            and engine.conv_out_hw(Hr, Wr, p1) == (Hr, Wr) and engine.conv_out_hw(Hr, Wr, p2) == (Hr, Wr)):
+        return None
+    return p.kind
+
+
+def _res_forward_wonly(p, x, emb, split):
+    """Reference :83-111 (ddim :318-338) in the weights-only state: GN.SiLU (and h_upd of an `updown` block, before the one
+    rounding: qd_groupnorm_resample_h16) -> operand rows of conv1; conv1 with the embedding projection as a row bias unless the
+    block is scale-shift; GN.SiLU, for scale-shift GN * (1 + scale) + shift . SiLU (qd_groupnorm_mod_h16, the projection as
+    `mod`) -> operand rows of conv2; conv2 with the skip rows as the residual of its epilogue.  The embedding projection and the
+    skip connection (nin_shortcut with its two-segment split, or conv_shortcut, for DDIM) keep their own module calls; x_upd on
+    the fp32 skip tensor stays in torch."""
+    B, C, H, W = x.shape
+    blk, conv1, conv2, mode = p.block, p.conv1, p.conv2, p.mode
+    rows = _nhwc_rows(x)
+    if mode:
+        xh = engine.wonly_groupnorm_resample_rows(rows, B, H, W, C, p.norm1, True, mode, conv1.wonly_plan())
+        H, W = (H // 2, W // 2) if mode == 1 else (2 * H, 2 * W)
+    else:
+        xh = engine.wonly_groupnorm_rows(rows, B, H * W, C, p.norm1, True, conv1.wonly_plan())
+    S = H * W
+    e = wonly_emb(blk, emb)                            # all blocks' projections in one launch (engine.WEIGHT_ONLY_TEMB)
+    if e is None:
+        e = p.emb_rows(emb if p.emb_act is None else p.emb_act(emb)).float()
+    if e.stride(1) != 1:
+        e = e.contiguous()
+    if p.scale_shift:
+        h = conv1.forward_rows(xh, B, H, W)
+        hh = engine.wonly_groupnorm_mod_rows(h, B, S, blk.out_channels, p.norm2, e, True, conv2.wonly_plan())
+    else:
+        h = conv1.forward_rows(xh, B, H, W, rowbias=e)
+        hh = engine.wonly_groupnorm_rows(h, B, S, blk.out_channels, p.norm2, True, conv2.wonly_plan())
+    if mode:
+        x = blk.x_upd(x)
+        rows = _nhwc_rows(x)
+    res = rows if p.skip is None else _nhwc_rows(p.skip(x, split=split) if p.skip_split and split != 0 else p.skip(x))
+    out = conv2.forward_rows(hh, B, H, W, residual=res)
+    engine.wonly_count(p.kind)
+    return _rows_to_nchw(out, B, H, W)
+
+
+# ------------------------------------------------------------------------------------------------
 # LDM / SD residual block  (reference quant_block.py:44-111)
 # ------------------------------------------------------------------------------------------------
 class QuantResBlock(BaseQuantBlock, ldm_unet.TimestepBlock):
@@ -855,7 +1032,8 @@ class QuantResBlock(BaseQuantBlock, ldm_unet.TimestepBlock):
         H_ = x.shape[2]
         conv1, conv2 = self.in_layers[-1], self.out_layers[-1]
         if self._int_route(H_):
-            return self._forward_int(x, emb, split, conv1, conv2, out_slot)
+            mode = 0 if not self.updown else 1 if hasattr(self.h_upd, "op") else 2     # Upsample has .conv / nothing, Downsample has .op
+            return _res_forward_int(_parts_of(self, conv1, conv2, mode), x, emb, split, out_slot)
         kind = self._wonly_route(x, emb, conv1, conv2)
         if kind is not None:
             return self._forward_wonly(x, emb, split, conv1, conv2, kind)
@@ -882,76 +1060,36 @@ class QuantResBlock(BaseQuantBlock, ldm_unet.TimestepBlock):
             and op.padding in (0, (0, 0)) and not op.ceil_mode and op.divisor_override is None
         return 1 if all(pool(op) for op in ops) else None
 
+    def _parts(self, conv1, conv2, mode, kind=None):
+        """The block's parts for the shared routes; mode: the resampling of an `updown` block as the calling route reads it."""
+        sk = self.skip_connection
+        return _ResParts(
+            block=self, norm1=self.in_layers[0], conv1=conv1, norm2=self.out_layers[0], conv2=conv2, emb_rows=self.emb_layers,
+            emb_act=None, skip=None if isinstance(sk, nn.Identity) else sk, skip_split=True,
+            # an `updown` block's skip reads x_upd(x), not what norm1 reads; any split the skip has recorded will do (reference :75-81)
+            skip_reads_x=not self.updown, split_exact=False,
+            cout1=kind != "resblock", kind=kind, mode=mode, scale_shift=self.use_scale_shift_norm)
+
     def _wonly_route(self, x, emb, conv1, conv2):
         """The fused weights-only route this call takes, by the name of its engine.WONLY_FUSED counter: "resblock" for a plain
         block (no `updown`, no `use_scale_shift_norm`) under engine.WEIGHT_ONLY_FUSE, "resblock_mod" for any other block, which
-        needs engine.WEIGHT_ONLY_FUSE_MOD on top, or None.  Both ask for the reference's layer lists (norm, SiLU, conv / norm,
-        SiLU, dropout, conv; an `updown` block applies in_layers[:-1], h_upd / x_upd, in_layers[-1]), everything
-        _wonly_fuse_gate demands, and both convolutions reading all their channels as one segment and keeping the (resampled)
-        size.  "resblock_mod" also asks for h_upd / x_upd being the 2x2 average (even H, W) or nearest 2x, conv1 giving
-        out_channels, and for scale-shift an embedding projection of 2 out_channels features."""
+        needs engine.WEIGHT_ONLY_FUSE_MOD on top, or None.  Both ask for the reference's layer lists (norm, SiLU, conv / norm, SiLU,
+        dropout, conv) and what _res_wonly_route demands; scale-shift for an embedding projection of 2 out_channels features."""
         plain = not (self.updown or self.use_scale_shift_norm)
-        if not engine.WEIGHT_ONLY_FUSE or not (plain or engine.WEIGHT_ONLY_FUSE_MOD) or x.dim() != 4:
+        if not engine.WEIGHT_ONLY_FUSE or not (plain or engine.WEIGHT_ONLY_FUSE_MOD):
             return None
         if not (len(self.in_layers) == 3 and len(self.out_layers) == 4 and isinstance(self.in_layers[0], nn.GroupNorm)
                 and isinstance(self.out_layers[0], nn.GroupNorm) and isinstance(self.in_layers[1], nn.SiLU)
                 and isinstance(self.out_layers[1], nn.SiLU) and isinstance(self.out_layers[2], nn.Dropout)):
             return None
-        mode = self._wonly_resample()                      # (0 without `updown`: the next check then asks nothing)
-        H, W = x.shape[2], x.shape[3]
-        if mode is None or (mode == 1 and (H % 2 or W % 2)):
+        kind = "resblock" if plain else "resblock_mod"
+        if (_res_wonly_route(_parts_of(self, conv1, conv2, self._wonly_resample(), kind), x, emb) is None
+                or (self.use_scale_shift_norm and _out_features(self.emb_layers[-1]) != 2 * self.out_channels)):
             return None
-        if not _wonly_fuse_gate(self, (conv1, conv2), (x, emb)):
-            return None
-        Hr, Wr = (H // 2, W // 2) if mode == 1 else (2 * H, 2 * W) if mode == 2 else (H, W)
-        p1, p2 = conv1.wonly_plan(), conv2.wonly_plan()          # (not None: _wonly_fuse_gate asked wonly_ready())
-        if not plain and (p1.Cout != self.out_channels
-                          or (self.use_scale_shift_norm and _out_features(self.emb_layers[-1]) != 2 * self.out_channels)):
-            return None
-        # the producers' C % 8 and out_channels % 8 are not asked again: wonly_plain_plan refuses a C that is no multiple of 8
-        if not (conv1.kind == 'conv2d' and conv2.kind == 'conv2d' and engine.wonly_plain_plan(p1, x.shape[1])
-                and engine.wonly_plain_plan(p2, self.out_channels) and p2.Cout == self.out_channels
-                and engine.conv_out_hw(Hr, Wr, p1) == (Hr, Wr) and engine.conv_out_hw(Hr, Wr, p2) == (Hr, Wr)):
-            return None
-        return "resblock" if plain else "resblock_mod"
+        return kind
 
     def _forward_wonly(self, x, emb, split, conv1, conv2, kind):
-        """Reference :83-111 in the weights-only state: GN.SiLU (and h_upd of an `updown` block, before the one rounding:
-        qd_groupnorm_resample_h16) -> operand rows of conv1; conv1 with the embedding projection as a row bias unless the block
-        is scale-shift; GN.SiLU, for scale-shift GN * (1 + scale) + shift . SiLU (qd_groupnorm_mod_h16, the projection as `mod`)
-        -> operand rows of conv2; conv2 with the skip rows as the residual of its epilogue.  The embedding projection and the
-        skip connection keep their own module calls; x_upd on the fp32 skip tensor stays in torch.  kind: the counter of
-        _wonly_route."""
-        B, C, H, W = x.shape
-        mode = self._wonly_resample()
-        rows = _nhwc_rows(x)
-        if mode:
-            xh = engine.wonly_groupnorm_resample_rows(rows, B, H, W, C, self.in_layers[0], True, mode, conv1.wonly_plan())
-            H, W = (H // 2, W // 2) if mode == 1 else (2 * H, 2 * W)
-        else:
-            xh = engine.wonly_groupnorm_rows(rows, B, H * W, C, self.in_layers[0], True, conv1.wonly_plan())
-        S = H * W
-        e = wonly_emb(self, emb)                           # all blocks' projections in one launch (engine.WEIGHT_ONLY_TEMB)
-        if e is None:
-            e = self.emb_layers(emb).float()
-        if e.stride(1) != 1:
-            e = e.contiguous()
-        if self.use_scale_shift_norm:
-            h = conv1.forward_rows(xh, B, H, W)
-            hh = engine.wonly_groupnorm_mod_rows(h, B, S, self.out_channels, self.out_layers[0], e, True, conv2.wonly_plan())
-        else:
-            h = conv1.forward_rows(xh, B, H, W, rowbias=e)
-            hh = engine.wonly_groupnorm_rows(h, B, S, self.out_channels, self.out_layers[0], True, conv2.wonly_plan())
-        if mode:
-            x = self.x_upd(x)
-            rows = _nhwc_rows(x)
-        if isinstance(self.skip_connection, nn.Identity):
-            res = rows
-        else:
-            res = _nhwc_rows(self.skip_connection(x, split=split) if split != 0 else self.skip_connection(x))
-        out = conv2.forward_rows(hh, B, H, W, residual=res)
-        engine.wonly_count(kind)
-        return _rows_to_nchw(out, B, H, W)
+        return _res_forward_wonly(_parts_of(self, conv1, conv2, self._wonly_resample(), kind), x, emb, split)
 
     def _forward_sim(self, x, emb, split=0):
         if self.updown:
@@ -976,79 +1114,6 @@ class QuantResBlock(BaseQuantBlock, ldm_unet.TimestepBlock):
         if split != 0:
             return self.skip_connection(x, split=split) + h
         return self.skip_connection(x) + h
-
-    def _skip_plan(self, split, C):
-        """ConvPlan of the 1x1 skip connection when its int8 input rows can be produced by the GroupNorm pass that
-        already reads x (engine.groupnorm_silu_quant(raw_plan=...)), else None (the module quantises x itself)."""
-        sk = self.skip_connection
-        if not (_FUSE_SKIP_QUANT and isinstance(sk, QuantModule) and sk.kind == 'conv2d' and _int_mode(sk)):
-            return None
-        if split != 0 and sk.split == 0:
-            return None                                   # the first call records the split: module path
-        if not all(q.inited for q in sk._act_quantizers()) or sk._geometry() != (1, 1, 1, 0):
-            return None
-        plan = sk.conv_plan()
-        return plan if engine.raw_quant_segs(plan, C) is not None else None
-
-    def _forward_int(self, x, emb, split, conv1, conv2, out_slot=None):
-        """Reference :83-111 on the integer engine.  Plain blocks: GN.SiLU -> int8 (one pass; the skip connection's rows in
-        the same pass), conv1 with the embedding as a row bias and the next norm's statistics in its epilogue, GN.SiLU ->
-        int8, conv2 with the residual in its epilogue.  `updown` blocks (:84-90) resample between the first norm and the
-        first convolution: nearest-2x commutes with the quantiser, so the SMALL map is quantised and its int8 rows are
-        replicated; the 2x2 average does not, so the norm writes fp32 rows, torch averages them (F.avg_pool2d, as the
-        reference) and the small map is quantised.  `use_scale_shift_norm` blocks (:99-103) hand the two halves of the
-        embedding projection to the second norm as a per-sample modulation (qd_groupnorm_mod_silu_quant) instead of
-        adding the projection to h."""
-        B, C, H, W = x.shape
-        S = H * W
-        rows = _nhwc_rows(x)
-        ident = isinstance(self.skip_connection, nn.Identity)
-        up = self.updown and not hasattr(self.h_upd, "op")            # Upsample has .conv / nothing, Downsample has .op
-        down = self.updown and not up
-        skp = None if (ident or self.updown) else self._skip_plan(split, C)
-        if down:
-            y = engine.groupnorm_silu_quant(rows, B, S, C, self.in_layers[0], True, want_float=True,
-                                            part=getattr(rows, "qd_gn_part", None))[1]
-            hp = self.h_upd(_rows_to_nchw(y, B, H, W))
-            x = self.x_upd(x)
-            H, W = H // 2, W // 2
-            S = H * W
-            conv1._init_act_quantizers(hp)
-            hp = _nhwc_rows(hp)
-            xq = engine.quantize_rows(hp, conv1.conv_plan(), 1, C, B * S, (0, 1, hp.stride(0)))
-            rows = _nhwc_rows(x)
-        elif skp is not None:
-            xq, skq = _gn_silu_to(conv1, rows, B, S, C, self.in_layers[0], raw_plan=skp)
-        else:
-            xq = _gn_silu_to(conv1, rows, B, S, C, self.in_layers[0])
-        if up:
-            xq = xq.view(B, H, 1, W, 1, -1).expand(B, H, 2, W, 2, xq.shape[1]).reshape(B * 4 * S, xq.shape[1])
-            x = self.x_upd(x)
-            H, W = 2 * H, 2 * W
-            S = H * W
-            rows = _nhwc_rows(x)
-        grp = self.__dict__.get("_emb_group")
-        e = grp.get(self, emb) if grp is not None else None           # all blocks' projections in one launch (K6)
-        if e is None:
-            e = self.emb_layers(emb).float().contiguous()             # SiLU + integer linear -> [B, Cout] (2 Cout: scale | shift)
-        if self.use_scale_shift_norm:
-            h = conv1.forward_codes(xq, B, H, W, gn_stats=True)
-            if e.stride(1) != 1:
-                e = e.contiguous()
-            hq = _gn_silu_to(conv2, h, B, S, self.out_channels, self.out_layers[0], mod=e)
-        else:
-            h = conv1.forward_codes(xq, B, H, W, rowbias=e, gn_stats=True)
-            hq = _gn_silu_to(conv2, h, B, S, self.out_channels, self.out_layers[0])
-        if ident:
-            res = rows
-        elif skp is not None:
-            res = self.skip_connection.forward_codes(skq, B, H, W)
-        else:
-            sk = self.skip_connection(x, split=split) if split != 0 else self.skip_connection(x)
-            res = _nhwc_rows(sk)
-        out = conv2.forward_codes(hq, B, H, W, residual=res, gn_stats=True, slot=out_slot)   # the next block normalises this
-        return _rows_to_nchw(out, B, H, W)
-
 
 # ------------------------------------------------------------------------------------------------
 # LDM attention matmuls  (reference quant_block.py:114-160)
@@ -1220,6 +1285,15 @@ class QuantAttentionBlock(BaseQuantBlock, _AttnQuant):
         y = rows.view(B, T, nh * ch).permute(0, 2, 1)
         return y if cast is None else y.to(cast)
 
+    def _matmul_plan(self, d, device):
+        """The AttnPlan of the four quantisers that live on the two matmul modules of self.attention (heads of d channels)."""
+        qk, smv = self.attention.qkv_matmul, self.attention.smv_matmul
+        holder = self.__dict__.setdefault("_aq_view", type("V", (), {})())
+        holder.act_quantizer_q, holder.act_quantizer_k = qk.act_quantizer_q, qk.act_quantizer_k
+        holder.act_quantizer_v, holder.act_quantizer_w = smv.act_quantizer_v, smv.act_quantizer_w
+        scale = float(qk.scale) if qk.scale is not None else d ** -0.25
+        return self._attn_plan(holder, 1.0, scale, device)
+
     def _forward_int(self, x, out_slot=None):
         B, C, H, W = x.shape
         T, nh = H * W, self.num_heads
@@ -1227,12 +1301,7 @@ class QuantAttentionBlock(BaseQuantBlock, _AttnQuant):
         rows = _nhwc_rows(x)
         xq = _gn_silu_to(self.qkv, rows, B, T, C, self.norm, silu=False)
         qkv = self.qkv.forward_codes(xq, B, 1, T)                     # [B*T, 3C]; channel = head*3d + {q,k,v}*d + i
-        qk, smv = self.attention.qkv_matmul, self.attention.smv_matmul
-        holder = self.__dict__.setdefault("_aq_view", type("V", (), {})())
-        holder.act_quantizer_q, holder.act_quantizer_k = qk.act_quantizer_q, qk.act_quantizer_k
-        holder.act_quantizer_v, holder.act_quantizer_w = smv.act_quantizer_v, smv.act_quantizer_w
-        scale = float(qk.scale) if qk.scale is not None else d ** -0.25
-        ap = self._attn_plan(holder, 1.0, scale, x.device)
+        ap = self._matmul_plan(d, x.device)
         ld = qkv.stride(0)
         strides = (T * ld, ld, 3 * d, 1)
         att = engine.attention(ap, qkv, qkv[:, d:], qkv[:, 2 * d:], B, T, T, nh, d, strides, strides, strides)
@@ -1241,39 +1310,58 @@ class QuantAttentionBlock(BaseQuantBlock, _AttnQuant):
 
     def _forward_heads(self, x, plans, out_slot=None):
         """The same block with the qkv projection run as three GEMMs (QuantModule.head_plans) whose epilogues write the
-        attention operand bytes: no fp32 [B*T, 3C] round trip, no separate head quantisers; the attention epilogue
-        quantises for proj_out where its quantiser is ready."""
+        attention operand bytes (_attn_heads_tail): no fp32 [B*T, 3C] round trip."""
         B, C, H, W = x.shape
         T, nh = H * W, self.num_heads
         d = C // nh
         rows = _nhwc_rows(x)
         xq = _gn_silu_to(self.qkv, rows, B, T, C, self.norm, silu=False)
-        qk, smv = self.attention.qkv_matmul, self.attention.smv_matmul
-        holder = self.__dict__.setdefault("_aq_view", type("V", (), {})())
-        holder.act_quantizer_q, holder.act_quantizer_k = qk.act_quantizer_q, qk.act_quantizer_k
-        holder.act_quantizer_v, holder.act_quantizer_w = smv.act_quantizer_v, smv.act_quantizer_w
-        scale = float(qk.scale) if qk.scale is not None else d ** -0.25
-        ap = self._attn_plan(holder, 1.0, scale, x.device)
-        q8, k8, v8, vsum = engine.head_buffers(x.device, B * nh, T, T, d)
-        vsum = engine.vsum_slice(id(self), x.device, tuple(vsum.shape))
-        engine.project_heads_group([(plan, xq, which, buf) for which, (plan, buf) in enumerate(zip(plans, (q8, k8, v8)))], B, T, nh, ap, vsum)
-        po = self.proj_out
-        if po.act_quantizer.inited and po.split == 0 and po.conv_plan().ldx == C and len(po.conv_plan().segs) == 1:
-            o8 = engine.attention_codes(ap, q8, k8, v8, vsum, B, T, T, nh, d, out_plan=po.conv_plan())
-            out = po.forward_codes(o8, B, 1, T, residual=rows, gn_stats=True, slot=out_slot)
-        else:
-            att = engine.attention_codes(ap, q8, k8, v8, vsum, B, T, T, nh, d)
-            out = _linear_like_conv1d(po, att, B, T, residual=rows, gn_stats=True, slot=out_slot)
-        return _rows_to_nchw(out, B, H, W)
+        ap = self._matmul_plan(d, x.device)
+        return _attn_heads_tail(self, ap, members=[(plan, xq) for plan in plans], shape=(B, T, nh, d), po=self.proj_out, geom=(B, 1, T),
+                                fallback=_linear_like_conv1d, rows=rows, out_slot=out_slot, hw=(H, W))
+
+
+def _attn_heads_tail(owner, ap, *, members, shape, po, geom, fallback, rows, out_slot, hw):
+    """Integer self-attention on a map from its operand projections on: members = [(plan, int8 rows)] of q, k, v run as one
+    grouped launch whose epilogues write the attention operand bytes (no fp32 projections, no separate head quantisers, no zero
+    fills); the attention epilogue quantises for `po` where its quantiser is ready, else fp32 rows go through `fallback`
+    (_linear_like_conv1d / _linear_like_conv2d); `po` adds `rows` and emits the next norm's statistics.  shape = (B, T, H, d);
+    geom: the forward_codes geometry of `po`; hw: the map size of the NCHW view returned."""
+    B, T, H, d = shape
+    q8, k8, v8, vsum = engine.head_buffers(rows.device, B * H, T, T, d)
+    vsum = engine.vsum_slice(id(owner), rows.device, tuple(vsum.shape))
+    engine.project_heads_group([(plan, xq, which, buf) for which, ((plan, xq), buf) in enumerate(zip(members, (q8, k8, v8)))], B, T, H, ap, vsum)
+    if po.act_quantizer.inited and po.split == 0 and po.conv_plan().ldx == H * d and len(po.conv_plan().segs) == 1:
+        o8 = engine.attention_codes(ap, q8, k8, v8, vsum, B, T, T, H, d, out_plan=po.conv_plan())
+        out = po.forward_codes(o8, *geom, residual=rows, gn_stats=True, slot=out_slot)
+    else:
+        att = engine.attention_codes(ap, q8, k8, v8, vsum, B, T, T, H, d)
+        out = fallback(po, att, *geom, residual=rows, gn_stats=True, slot=out_slot)
+    return _rows_to_nchw(out, B, *hw)
 
 
 def _linear_like_conv1d(mod, rows, B, T, residual=None, gn_stats=False, slot=None):
-    """conv1d(k=1) QuantModule applied to token rows [B*T, C]."""
+    """conv1d(k=1) QuantModule applied to token rows [B*T, C]: initialised on its own [B, C, T] view, then a one-row map."""
     mod._init_act_quantizers(rows.view(B, T, -1).permute(0, 2, 1))
-    plan = mod.conv_plan()
-    M, K = rows.shape
-    xq = engine.quantize_rows(rows, plan, 1, K, M, (0, rows.stride(1), rows.stride(0)))
-    return engine.conv_forward(plan, xq, B, 1, T, 1, T, residual=residual, gn_stats=gn_stats, slot=slot)
+    return _linear_like_conv2d(mod, rows, B, 1, T, residual=residual, gn_stats=gn_stats, slot=slot)
+
+
+def _wonly_attn_tail(fused, q, k, v, *, shape, strides, scale, library, out_lin, rows):
+    """attention -> operand rows of the out-projection -> out-projection with `rows` as the residual of its epilogue.
+    shape = (B, T, S, H, d); fused (the caller's gate): q / k / v rows at element `strides` (one 4-tuple each) go into
+    qd_attn_h16, else `library()` returns the merged-head rows [B*T][H*d] of the caller's library passes."""
+    B, T, S, H, d = shape
+    M, inner, oplan = B * T, H * d, out_lin.wonly_plan()
+    if fused:
+        # fp16 operand rows of the out-projection straight from the kernel when the layouts agree (the same single rounding of
+        # the fp32 result that qd_rows_to_h16 would apply), else fp32 rows and that pass
+        direct = oplan.act_dtype == torch.float16 and oplan.ldx == inner
+        o = engine.attention_h16(q, k, v, B, T, S, H, d, *strides, scale, torch.float16 if direct else torch.float32)
+        oh = o if direct else engine.wonly_rows(o, oplan, 1, inner, M, (0, 1, inner))
+    else:
+        o = library()
+        oh = engine.wonly_rows(o, oplan, 1, inner, M, (0, 1, o.stride(0)))
+    return out_lin.forward_rows(oh, 1, 1, M, residual=rows)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1413,20 +1501,14 @@ class QuantBasicTransformerBlock(BaseQuantBlock, _AttnQuant):
             v = att.to_v.forward_rows(xh, 1, 1, M, out_dtype=qdt).view(B, T, inner)
         else:
             k, v = att.to_k(context), att.to_v(context)
-        S = k.shape[1]
-        if fused:
-            # fp16 operand rows of to_out straight from the kernel when the layouts agree (the same single rounding of the
-            # fp32 result that qd_rows_to_h16 would apply), else fp32 rows and that pass
-            direct = oplan.act_dtype == torch.float16 and oplan.ldx == inner
-            st = lambda t: (t.stride(0), t.stride(1), d, 1)
-            o = engine.attention_h16(q, k, v, B, T, S, h, d, st(q), st(k), st(v), att.scale, torch.float16 if direct else torch.float32)
-            oh = o if direct else engine.wonly_rows(o, oplan, 1, inner, M, (0, 1, inner))
-        else:
+        def library():
             qh, kh, vh = (ldm_unet._split_heads(t, h) for t in (q, k, v))
             p = (th.einsum('b i d, b j d -> b i j', qh, kh) * att.scale).softmax(dim=-1)
-            o = ldm_unet._merge_heads(th.einsum('b i j, b j d -> b i d', p, vh), h).reshape(M, inner)
-            oh = engine.wonly_rows(o, oplan, 1, inner, M, (0, 1, o.stride(0)))
-        return out_lin.forward_rows(oh, 1, 1, M, residual=rows)
+            return ldm_unet._merge_heads(th.einsum('b i j, b j d -> b i d', p, vh), h).reshape(M, inner)
+
+        st = lambda t: (t.stride(0), t.stride(1), d, 1)
+        return _wonly_attn_tail(fused, q, k, v, shape=(B, T, k.shape[1], h, d), strides=(st(q), st(k), st(v)), scale=att.scale,
+                                library=library, out_lin=out_lin, rows=rows)
 
     def _forward_wonly(self, x, context):
         """attention.py:229-231 in the weights-only state: every LayerNorm is qd_layernorm_h16 into the operand rows of its
@@ -1581,7 +1663,7 @@ class QuantResnetBlock(BaseQuantBlock):
         if temb is None:
             x, temb = x
         if _int_mode(self.conv1, self.conv2, self.temb_proj) and not _dropout_live(self):
-            return self._forward_int(x, temb, split, out_slot)
+            return _res_forward_int(_parts_of(self), x, temb, split, out_slot)
         if self._wonly_route(x, temb):
             return self._forward_wonly(x, temb, split)
         h = self.conv1(ddim_unet.nonlinearity(self.norm1(x)))
@@ -1597,84 +1679,22 @@ class QuantResnetBlock(BaseQuantBlock):
             x = self.conv_shortcut(x) if self.use_conv_shortcut else self.nin_shortcut(x, split=split)
         return x + h
 
+    def _parts(self):
+        """The block's parts for the shared routes: no resampling, no scale-shift."""
+        sk = None if self.in_channels == self.out_channels else self.conv_shortcut if self.use_conv_shortcut else self.nin_shortcut
+        return _ResParts(
+            block=self, norm1=self.norm1, conv1=self.conv1, norm2=self.norm2, conv2=self.conv2, skip=sk, cout1=True, kind="resnetblock",
+            emb_rows=self.temb_proj, emb_act=ddim_unet.nonlinearity,
+            # the 1x1 `nin_shortcut` is told the split and reads the tensor norm1 normalises; `conv_shortcut` (3x3) neither
+            skip_split=not self.use_conv_shortcut, skip_reads_x=not self.use_conv_shortcut, split_exact=True)
+
     def _wonly_route(self, x, temb):
         """This call takes _forward_wonly (engine.WEIGHT_ONLY_FUSE_DDIM on top of engine.WEIGHT_ONLY_FUSE): everything
-        _wonly_fuse_gate demands of the two 3x3 convolutions, two nn.GroupNorms, and both convolutions reading all their
-        channels (a multiple of 8: wonly_plain_plan) as one segment, keeping the map size and giving out_channels."""
-        if not engine.WEIGHT_ONLY_FUSE_DDIM or not torch.is_tensor(x) or x.dim() != 4:
-            return False
-        if not (isinstance(self.norm1, nn.GroupNorm) and isinstance(self.norm2, nn.GroupNorm)):
-            return False
-        conv1, conv2 = self.conv1, self.conv2
-        if not _wonly_fuse_gate(self, (conv1, conv2), (x, temb)):
-            return False
-        p1, p2 = conv1.wonly_plan(), conv2.wonly_plan()          # (not None: _wonly_fuse_gate asked wonly_ready())
-        H, W = x.shape[2], x.shape[3]
-        return (conv1.kind == 'conv2d' and conv2.kind == 'conv2d' and engine.wonly_plain_plan(p1, x.shape[1])
-                and engine.wonly_plain_plan(p2, self.out_channels) and p1.Cout == self.out_channels and p2.Cout == self.out_channels
-                and engine.conv_out_hw(H, W, p1) == (H, W) and engine.conv_out_hw(H, W, p2) == (H, W))
+        _res_wonly_route demands, the two 3x3 convolutions both giving out_channels."""
+        return engine.WEIGHT_ONLY_FUSE_DDIM and _res_wonly_route(_parts_of(self), x, temb) is not None
 
     def _forward_wonly(self, x, temb, split):
-        """Reference :318-338 in the weights-only state (the plain kind of QuantResBlock._forward_wonly): norm1 . swish ->
-        operand rows of conv1; conv1 with the embedding projection as a row bias; norm2 . swish -> operand rows of conv2; conv2
-        with the skip rows as the residual of its epilogue.  temb_proj and the shortcut (nin_shortcut with its two-segment
-        split, or conv_shortcut) keep their own module calls."""
-        B, C, H, W = x.shape
-        S = H * W
-        conv1, conv2 = self.conv1, self.conv2
-        rows = _nhwc_rows(x)
-        xh = engine.wonly_groupnorm_rows(rows, B, S, C, self.norm1, True, conv1.wonly_plan())
-        e = wonly_emb(self, temb)
-        if e is None:
-            e = self.temb_proj(ddim_unet.nonlinearity(temb)).float()
-        if e.stride(1) != 1:
-            e = e.contiguous()
-        h = conv1.forward_rows(xh, B, H, W, rowbias=e)
-        hh = engine.wonly_groupnorm_rows(h, B, S, self.out_channels, self.norm2, True, conv2.wonly_plan())
-        if self.in_channels != self.out_channels:
-            res = _nhwc_rows(self.conv_shortcut(x) if self.use_conv_shortcut else self.nin_shortcut(x, split=split))
-        else:
-            res = rows
-        out = conv2.forward_rows(hh, B, H, W, residual=res)
-        engine.wonly_count("resnetblock")
-        return _rows_to_nchw(out, B, H, W)
-
-    def _skip_plan(self, split, C):
-        """see QuantResBlock._skip_plan: the 1x1 `nin_shortcut` reads the tensor norm1 normalises"""
-        if self.in_channels == self.out_channels or self.use_conv_shortcut:
-            return None
-        sk = self.nin_shortcut
-        if not (_FUSE_SKIP_QUANT and isinstance(sk, QuantModule) and sk.kind == 'conv2d' and _int_mode(sk)):
-            return None
-        if (split != 0 and sk.split != split) or not all(q.inited for q in sk._act_quantizers()) or sk._geometry() != (1, 1, 1, 0):
-            return None
-        plan = sk.conv_plan()
-        return plan if engine.raw_quant_segs(plan, C) is not None else None
-
-    def _forward_int(self, x, temb, split, out_slot=None):
-        B, C, H, W = x.shape
-        S = H * W
-        rows = _nhwc_rows(x)
-        skp = self._skip_plan(split, C)
-        if skp is not None:
-            xq, skq = _gn_silu_to(self.conv1, rows, B, S, C, self.norm1, raw_plan=skp)
-        else:
-            xq = _gn_silu_to(self.conv1, rows, B, S, C, self.norm1)
-        grp = self.__dict__.get("_emb_group")
-        e = grp.get(self, temb) if grp is not None else None
-        if e is None:
-            e = self.temb_proj(ddim_unet.nonlinearity(temb)).float().contiguous()
-        h = self.conv1.forward_codes(xq, B, H, W, rowbias=e, gn_stats=True)
-        hq = _gn_silu_to(self.conv2, h, B, S, self.out_channels, self.norm2)
-        if skp is not None:
-            res = self.nin_shortcut.forward_codes(skq, B, H, W)
-        elif self.in_channels != self.out_channels:
-            sk = self.conv_shortcut(x) if self.use_conv_shortcut else self.nin_shortcut(x, split=split)
-            res = _nhwc_rows(sk)
-        else:
-            res = rows
-        out = self.conv2.forward_codes(hq, B, H, W, residual=res, gn_stats=True, slot=out_slot)
-        return _rows_to_nchw(out, B, H, W)
+        return _res_forward_wonly(_parts_of(self), x, temb, split)
 
 
 class QuantAttnBlock(BaseQuantBlock, _AttnQuant):
@@ -1726,9 +1746,8 @@ class QuantAttnBlock(BaseQuantBlock, _AttnQuant):
             return False
         C = x.shape[1]
         plans = [m.wonly_plan() for m in layers]                 # (not None: _wonly_fuse_gate asked wonly_ready())
-        one_tap = lambda p: (p.kh, p.kw, p.stride, p.pad) == (1, 1, 1, 0)
         pq = plans[0]
-        return (all(one_tap(p) and engine.wonly_plain_plan(p, C) and p.Cout == C for p in plans)
+        return (all(_one_tap(p) and engine.wonly_plain_plan(p, C) and p.Cout == C for p in plans)
                 and all(p.ldx == pq.ldx and p.act_dtype == pq.act_dtype for p in plans[1:3]))
 
     def _forward_wonly(self, x):
@@ -1743,18 +1762,14 @@ class QuantAttnBlock(BaseQuantBlock, _AttnQuant):
         fused = engine.WEIGHT_ONLY_ATTN is not None and engine.wonly_attn_wide_shape_ok(C)
         qdt = torch.float16 if fused and engine.WEIGHT_ONLY_ATTN == torch.float16 else torch.float32
         q, k, v = (m.forward_rows(xh, 1, 1, M, out_dtype=qdt) for m in (self.q, self.k, self.v))
-        oplan = self.proj_out.wonly_plan()
         scale = int(C) ** (-0.5)
-        if fused:
-            direct = oplan.act_dtype == torch.float16 and oplan.ldx == C
-            st = (T * C, C, C, 1)
-            o = engine.attention_h16(q, k, v, B, T, T, 1, C, st, st, st, scale, torch.float16 if direct else torch.float32)
-            oh = o if direct else engine.wonly_rows(o, oplan, 1, C, M, (0, 1, C))
-        else:
+
+        def library():
             w_ = F.softmax(th.bmm(q.view(B, T, C), k.view(B, T, C).transpose(1, 2)) * scale, dim=2)
-            o = th.bmm(w_, v.view(B, T, C)).reshape(M, C)
-            oh = engine.wonly_rows(o, oplan, 1, C, M, (0, 1, o.stride(0)))
-        out = self.proj_out.forward_rows(oh, 1, 1, M, residual=rows)
+            return th.bmm(w_, v.view(B, T, C)).reshape(M, C)
+
+        out = _wonly_attn_tail(fused, q, k, v, shape=(B, T, T, 1, C), strides=((T * C, C, C, 1),) * 3, scale=scale,
+                               library=library, out_lin=self.proj_out, rows=rows)
         engine.wonly_count("attnblock_ddim")
         return _rows_to_nchw(out, B, H, W)
 
@@ -1767,26 +1782,15 @@ class QuantAttnBlock(BaseQuantBlock, _AttnQuant):
         _, y = engine.groupnorm_silu_quant(rows, B, T, C, self.norm, False, plan=ws_plan, want_float=True,
                                            part=getattr(rows, "qd_gn_part", None))
         ap = self._attn_plan(self, int(C) ** (-0.5), 1.0, x.device)
-        po = self.proj_out
         if QKV_HEADS and T % 128 == 0:
-            # q / k / v write the attention operand bytes from their epilogues (one head as wide as the layer), the attention
-            # epilogue quantises for proj_out: no fp32 projections, no qd_quantize_heads, no zero fills
+            # q / k / v write the attention operand bytes from their epilogues (_attn_heads_tail: one head as wide as the layer)
             for m in (self.q, self.k, self.v):
                 m._init_act_quantizers(y)
             plans = [m.conv_plan() for m in (self.q, self.k, self.v)]
             if all(engine.heads_fusable(p, T, 1) and p.Cout == C for p in plans):
-                q8, k8, v8, vsum = engine.head_buffers(x.device, B, T, T, C)
-                vsum = engine.vsum_slice(id(self), x.device, tuple(vsum.shape))
-                members = [(plan, engine.quantize_rows(y, plan, 1, C, B * T, (0, y.stride(1), y.stride(0))), which, buf)
-                           for which, (plan, buf) in enumerate(zip(plans, (q8, k8, v8)))]
-                engine.project_heads_group(members, B, T, 1, ap, vsum)
-                if po.act_quantizer.inited and po.split == 0 and po.conv_plan().ldx == C and len(po.conv_plan().segs) == 1:
-                    o8 = engine.attention_codes(ap, q8, k8, v8, vsum, B, T, T, 1, C, out_plan=po.conv_plan())
-                    out = po.forward_codes(o8, B, H, W, residual=rows, gn_stats=True, slot=out_slot)
-                else:
-                    o = engine.attention_codes(ap, q8, k8, v8, vsum, B, T, T, 1, C)
-                    out = _linear_like_conv2d(po, o, B, H, W, residual=rows, gn_stats=True, slot=out_slot)
-                return _rows_to_nchw(out, B, H, W)
+                members = [(plan, engine.quantize_rows(y, plan, 1, C, B * T, (0, y.stride(1), y.stride(0)))) for plan in plans]
+                return _attn_heads_tail(self, ap, members=members, shape=(B, T, 1, C), po=self.proj_out, geom=(B, H, W),
+                                        fallback=_linear_like_conv2d, rows=rows, out_slot=out_slot, hw=(H, W))
         q = _linear_like_conv2d(self.q, y, B, H, W)
         k = _linear_like_conv2d(self.k, y, B, H, W)
         v = _linear_like_conv2d(self.v, y, B, H, W)
