@@ -458,6 +458,34 @@ int qd_fakequant_bwd(const float* x, const float* gy, int64_t n, const float* de
                      float* gx, float* gdelta_part, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Calibration: fused AdaRound quantiser of a weight tensor, forward, backward and rounding
+ *     regulariser, for the weight phase of block / layer reconstruction.  Replaces the autograd composition of
+ *     AdaRoundQuantizer.forward / get_soft_targets (qdiff/adaptive_rounding.py:39-74) and the second evaluation of the soft
+ *     targets by the regulariser of LossFunction.__call__ (qdiff/block_recon.py:217-229).
+ *     The quantiser is channel-wise: row r of `rows` is the `cols` floats at w + r * ldw (ldw >= cols: the two halves of a
+ *     split shortcut are read in place); gw of the backward likewise with row stride ldg >= cols (a half receives a channel
+ *     slice of the concatenated weight's gradient); delta / zero_point hold `rows` floats; alpha, w_hat, galpha are dense
+ *     [rows][cols] and 16-byte aligned.  w and gw need no alignment beyond their type: rows that do not start on 16 bytes
+ *     are read float by float.  rows * cols < 2^31.  fp32 only.  FP contraction is off; the operation order is autograd's.
+ *       base = floor(w / delta); s = 1 / (1 + exp(-alpha)); hr = s * (zeta - gamma) + gamma; h = clamp(hr, 0, 1);
+ *       c = base + h + zp;  w_hat = (clamp(c, 0, n_levels - 1) - zp) * delta
+ *     reg_b > 0: reg_part[k] = block k's share of sum(1 - (|h - 0.5| * 2)^reg_b), the fp32 terms added in fp64; the caller
+ *     sums qd_adaround_blocks(rows, cols) partials in fp64 and rounds once.  reg_b <= 0: no regulariser, reg_part may be null.
+ *     Backward (recomputes everything from w and alpha):
+ *       rec = gw * delta, 0 unless 0 <= c <= n_levels - 1, 0 unless 0 <= hr <= 1, * (zeta - gamma), * (1 - s) * s
+ *       reg = -greg[0] * (b * v^(b - 1)) * 2 * sgn(h - 0.5) with v = |h - 0.5| * 2, 0 unless 0 <= hr <= 1, * (zeta - gamma),
+ *             * (1 - s) * s          (only with greg, a DEVICE scalar d(loss)/d(reg sum), non-null and reg_b > 0)
+ *       galpha = rec + reg
+ * ------------------------------------------------------------------------------------------ */
+int64_t qd_adaround_blocks(int64_t rows, int64_t cols);
+int qd_adaround_fwd(const float* w, int64_t rows, int64_t cols, int64_t ldw, const float* alpha, const float* delta,
+                    const float* zero_point, int n_levels, float gamma, float zeta, float reg_b, float* w_hat, double* reg_part,
+                    void* stream);
+int qd_adaround_bwd(const float* gw, int64_t ldg, const float* w, int64_t rows, int64_t cols, int64_t ldw, const float* alpha,
+                    const float* delta, const float* zero_point, int n_levels, float gamma, float zeta, float reg_b,
+                    const float* greg, float* galpha, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * First-stage decoder: the convolutions of the KL-f8 / VQ-f4 `Decoder`
  *     (ldm/modules/diffusionmodules/model.py:465-572 `Decoder.forward`: conv_in, ResnetBlock :80-141, AttnBlock :144-196
  *     q/k/v/proj_out, Upsample :48-63 nearest-2x + conv, conv_out; called from ldm/models/autoencoder.py:330-333 `decode`

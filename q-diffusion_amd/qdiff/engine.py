@@ -580,6 +580,27 @@ def set_weight_only_splitk(on):
     _set_flag("WEIGHT_ONLY_SPLITK", on, "weight-only split-K")
 
 
+# Fused AdaRound: False (default) = the weight phase of calibration differentiates the elementwise
+# composition of AdaRoundQuantizer.forward; True = a soft-target 'learned_hard_sigmoid' quantiser under autograd runs ONE launch
+# forward (qd_adaround_fwd, which also sums the rounding regulariser the objective announced) and ONE backward
+# (qd_adaround_bwd).  Unlike the weights-only knobs it engages inside simulation(): recon.reconstruct runs there.
+# QDIFF_FUSED_ADAROUND=1, or engine.set_fused_adaround().
+FUSED_ADAROUND = _parse_flag(os.environ.get("QDIFF_FUSED_ADAROUND"), "QDIFF_FUSED_ADAROUND")
+
+# qd_adaround_fwd + qd_adaround_bwd launches (tests read it)
+ADAROUND_LAUNCHES = [0]
+
+
+def set_fused_adaround(on):
+    """True / False (or the strings QDIFF_FUSED_ADAROUND accepts)."""
+    _set_flag("FUSED_ADAROUND", on, "fused AdaRound")
+
+
+def adaround_device_ok(t):
+    """The fused AdaRound kernels run on GPU tensors only; anything else keeps the composition."""
+    return t.is_cuda
+
+
 def wonly_device_ok(t):
     """The weights-only kernel runs on GPU tensors only; anything else keeps the library path."""
     return t.is_cuda

@@ -67,6 +67,7 @@ EXPORTS = ["qd_abi_version", "qd_last_error", "qd_device_ok", "qd_box_probe", "q
            "qd_conv2d_i8_acc", "qd_groupnorm_ws_bytes", "qd_groupnorm_silu_quant", "qd_groupnorm_mod_silu_quant", "qd_layernorm_quant",
            "qd_geglu_quant", "qd_quantize_heads", "qd_attn_i8", "qd_attn_i8_qp", "qd_attn_keyterm", "qd_attn_uses_keyterm", "qd_attn_config", "qd_attn_ws_bytes", "qd_bmm_qk_i8", "qd_bmm_pv_i8", "qd_temb_mlp", "qd_temb_mlp_wq_h16",
            "qd_fakequant_blocks", "qd_fakequant_fwd", "qd_fakequant_bwd",
+           "qd_adaround_blocks", "qd_adaround_fwd", "qd_adaround_bwd",
            "qd_conv2d_bf16", "qd_pack_weights_bf16_bytes", "qd_pack_weights_bf16", "qd_groupnorm_silu_bf16",
            "qd_pack_weights_h16", "qd_groupnorm_silu_h16", "qd_conv2d_wq_h16", "qd_rows_to_h16",
            "qd_conv2d_wq_h16_splitk_ws_bytes", "qd_wq_h16_config",
@@ -128,6 +129,10 @@ def load():
     lib.qd_fakequant_blocks.argtypes = [i64]
     lib.qd_fakequant_fwd.argtypes = [vp, i64, vp, vp, i32, i32, vp, vp]
     lib.qd_fakequant_bwd.argtypes = [vp, vp, i64, vp, vp, i32, i32, vp, vp, vp]
+    lib.qd_adaround_blocks.restype = ctypes.c_int64
+    lib.qd_adaround_blocks.argtypes = [i64, i64]
+    lib.qd_adaround_fwd.argtypes = [vp, i64, i64, i64, vp, vp, vp, i32, f32, f32, f32, vp, vp, vp]
+    lib.qd_adaround_bwd.argtypes = [vp, i64, vp, i64, i64, i64, vp, vp, vp, i32, f32, f32, f32, vp, vp, vp]
     lib.qd_conv2d_bf16.argtypes = [ctypes.POINTER(ConvDesc), vp]
     lib.qd_pack_weights_bf16_bytes.restype = ctypes.c_int64
     lib.qd_pack_weights_bf16_bytes.argtypes = [i32, i32, i32]
@@ -726,6 +731,54 @@ def fakequant_bwd(x, gy, delta, zero_point, qmin, qmax):
     _check(load().qd_fakequant_bwd(_ptr(x, "x"), _ptr(gy, "gy"), x.numel(), _ptr(delta, "delta"), _ptr(zero_point, "zero_point"),
                                    int(qmin), int(qmax), _ptr(gx), _ptr(part), _stream()), "qd_fakequant_bwd")
     return gx, part.sum()
+
+
+def adaround_rows(w):
+    """(rows, cols, ldw) of a weight tensor or of a channel slice `weight[:, a:b]` of one, as qd_adaround_* read it in place:
+    None when the elements of a row are not consecutive in memory."""
+    rows = w.shape[0]
+    cols = w.numel() // max(rows, 1)
+    if w.dim() == 0 or rows == 0 or cols == 0 or not w[0].is_contiguous() or (rows > 1 and w.stride(0) < cols):
+        return None
+    return rows, cols, (w.stride(0) if rows > 1 else cols)
+
+
+def adaround_fwd(w, alpha, delta, zero_point, n_levels, gamma, zeta, reg_b=None):
+    """(w_hat, reg_sum) of the AdaRound quantiser with soft targets, one launch (calibration: adaptive_rounding.FusedAdaRound).
+    w: [rows, ...] or a channel slice of it, read in place; alpha: dense, w's shape; delta / zero_point: `rows` floats.
+    reg_b: exponent of the rounding regulariser, None = none (reg_sum is None); its fp64 block partials are summed here and the
+    total rounded to fp32 once."""
+    rows, cols, ldw = adaround_rows(w)
+    lib = load()
+    w_hat = torch.empty(w.shape, dtype=torch.float32, device=w.device)
+    part = None
+    if reg_b is not None:
+        part = torch.empty(int(lib.qd_adaround_blocks(rows, cols)), dtype=torch.float64, device=w.device)
+    _check(lib.qd_adaround_fwd(_ptr(w, "w"), rows, cols, ldw, _ptr(alpha, "alpha"), _ptr(delta, "delta"), _ptr(zero_point, "zero_point"),
+                               int(n_levels), float(gamma), float(zeta), float(reg_b) if reg_b is not None else 0.0, _ptr(w_hat),
+                               _ptr(part), _stream()), "qd_adaround_fwd")
+    from . import engine
+    engine.ADAROUND_LAUNCHES[0] += 1
+    return w_hat, (None if part is None else part.sum().float())
+
+
+def adaround_bwd(gw, w, alpha, delta, zero_point, n_levels, gamma, zeta, reg_b=None, greg=None):
+    """d loss / d alpha of adaround_fwd given d loss / d w_hat (w's shape; dense or, like w, a channel slice read in place)
+    and, with reg_b, the device scalar d loss / d reg_sum (None: the regulariser took no part in the loss).  One launch;
+    nothing but w and alpha is read back."""
+    rows, cols, ldw = adaround_rows(w)
+    grows = adaround_rows(gw)
+    if gw.dtype != torch.float32 or grows is None or grows[:2] != (rows, cols):
+        raise HipEngineError(f"adaround_bwd: gw must be fp32 rows of w's shape {tuple(w.shape)} (got {gw.dtype}, {tuple(gw.shape)}, strides {gw.stride()})")
+    ldg = grows[2]
+    galpha = torch.empty(alpha.shape, dtype=torch.float32, device=alpha.device)
+    _check(load().qd_adaround_bwd(_ptr(gw, "gw"), ldg, _ptr(w, "w"), rows, cols, ldw, _ptr(alpha, "alpha"), _ptr(delta, "delta"),
+                                  _ptr(zero_point, "zero_point"), int(n_levels), float(gamma), float(zeta),
+                                  float(reg_b) if reg_b is not None else 0.0, _ptr(greg, "greg") if reg_b is not None else None,
+                                  _ptr(galpha), _stream()), "qd_adaround_bwd")
+    from . import engine
+    engine.ADAROUND_LAUNCHES[0] += 1
+    return galpha
 
 
 def box_probe(device, kind, blocks, iters):
