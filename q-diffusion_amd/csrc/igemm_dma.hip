@@ -1407,7 +1407,6 @@ __global__ __launch_bounds__(256) void pack_t8_kernel(const float* __restrict__ 
 template __global__ void igemm_kernel<QD_PROBE_INSTANCE>(const ConvD);
 }  // namespace
 #else
-// tile shapes (MT, NT, WM, WN): block = (32*MT*WM) x (32*NT*WN)
 // two K-groups per block where a launch has at most one tile per CU (default) or never (QD_KGROUPS=0 / qd_conv_config(0): A/B
 // runs and the equality test)
 static int& kgroups_knob() {
@@ -1421,68 +1420,126 @@ static int& kgroups_knob() {
 // 1 x 1 1280 -> 1280 22.9 -> 19.8, 1 x 1 640 -> 640 at 32 x 32 (ten steps) 26.0 -> 24.7; SD step 19.84 -> 19.35 ms.
 constexpr int kgroups_min_steps() { return 8; }
 
-// qd_conv2d_i8_group runs every member through run() — all its checks, its tile choice — with this set: dispatch() then
-// records the finished kernel descriptor and the tile it would have launched instead of launching, and run() returns right
-// after it (no split-K finalise pass, no launch check).
-// qd_conv2d_i8_form probes the same way with `query` set: the tile choice then stays the single launch's own (a member of a
-// grouped launch takes 128 rows, want_mt2 in run()), and bm / bn / threads / nsplit describe the launch dispatch() withheld.
-struct GroupCapture { ConvD k; int out = 0, tile = 0; bool split = false, query = false; int bm = 0, bn = 0, threads = 0, nsplit = 0; };
-thread_local GroupCapture* g_capture = nullptr;
-constexpr int tile_code(int MT, int NT, int WM, int WN, int WB) { return (((MT * 16 + NT) * 8 + WM) * 8 + WN) * 32 + WB; }
-
-template <int MT, int NT, int WM, int WN, int WB = 4>
-int dispatch(ConvD& k, bool split, int out, hipStream_t st, int nsplit = 1) {
-    constexpr int BM = 32 * MT * WM, BN = 32 * NT * WN;
-    k.nblk_m = (k.M + BM - 1) / BM;
-    k.nblk_n = (k.Cout + BN - 1) / BN;
-    // a probe records the launch at the point where it would be made (so that the block form is known) and launches nothing
-    auto probe = [&](int threads) {
-        if (!g_capture) return false;
-        GroupCapture& c = *g_capture;
-        c.k = k; c.out = out; c.tile = nsplit == 1 ? tile_code(MT, NT, WM, WN, WB) : -1; c.split = split;
-        c.bm = BM; c.bn = BN; c.threads = threads; c.nsplit = nsplit;
-        return true;
-    };
-    // At most one tile per CU and a K loop worth splitting: two K-groups in a 512-thread block (igemm_body, KS = 2) — linear rows
-    // on every tile shape, split-K partials and the head-layout epilogues on the shapes the three UNets launch them with
-    if constexpr (WB <= 8 && (WM == 4 || (MT == 2 && NT == 5)) && (NT == 4 || NT == 5 || NT == 7) && (WB == 4 || NT == 4)) {
-        const long nb = (long)k.nblk_m * k.nblk_n * nsplit;
-        const int ksteps = out == O_PART ? k.it_per : k.taps * k.seg[0].nsteps_tap;
-        if (kgroups_knob() && !split && k.nseg == 1 && nb <= 256 && ksteps >= kgroups_min_steps()) {
-            dim3 grid2(k.nblk_m * k.nblk_n, nsplit), block2(512);
-#define QD_K2(O) { if (!probe(512)) hipLaunchKernelGGL((igemm_k2_kernel<MT, NT, WM, WN, O, WB>), grid2, block2, 0, st, k); return 0; }
-            if (out == O_F32) QD_K2(O_F32)
-            if constexpr (NT == 5 && MT == 1) { if (out == O_F16) QD_K2(O_F16) }        // (fp16 rows on the 256-row tiles spill: four-wave block)
-            if constexpr (MT == 1 && WM == 4 && ((WB == 4 && (NT == 5 || NT == 7)) || (WB == 8 && NT == 4))) { if (out == O_PART) QD_K2(O_PART) }
-            if constexpr (WB == 4 && NT == 5 && WM == 4) { if (out == O_HROWS) QD_K2(O_HROWS) if (out == O_HTR) QD_K2(O_HTR) }
-#undef QD_K2
-        }
-    }
-    dim3 grid(k.nblk_m * k.nblk_n, nsplit), block(256);
-#define QD_CASE(SP, O)                                                                              \
-    if (split == SP && out == O) {                                                                  \
-        if (!probe(256)) hipLaunchKernelGGL((igemm_kernel<MT, NT, WM, WN, SP, O, WB>), grid, block, 0, st, k); \
-        return 0;                                                                                   \
-    }
-    if constexpr (WB == 16) {
-        QD_CASE(false, O_F32) QD_CASE(false, O_BF16)
-    } else if constexpr (WB == 17) {
-        QD_CASE(false, O_F32) QD_CASE(false, O_F16)
-    } else {
-        QD_CASE(false, O_F32)
-        QD_CASE(false, O_F16)
-        if constexpr (MT == 1 && WM == 4) { QD_CASE(false, O_I32) QD_CASE(true, O_F32) QD_CASE(true, O_F16) QD_CASE(false, O_PART) }
-        // (int8 weights: the 128 x 128 tile only — the CIFAR attention block's q / k / v, 256 channels)
-        if constexpr ((WB == 4 && WM == 4) || (WB == 8 && MT == 1 && NT == 4)) { QD_CASE(false, O_HROWS) QD_CASE(false, O_HTR) }
-        if constexpr (NT == 4 && WB == 4 && WM == 4) { QD_CASE(false, O_GEGLU) }
-    }
-#undef QD_CASE
-    qd_set_error("qd_conv2d_%s: unsupported variant split=%d out=%d tile %dx%d", WB >= 16 ? "bf16" : "i8", (int)split, out, BM, BN);
-    return 1;
+// A tile (MT, NT, WM, WN, WB): WM x WN waves of (32*MT) x (32*NT) outputs each; WB = the weight bits the kernel is built for
+// (4, 8; 16 / 17: the bf16 / fp16 mode).
+struct TileId {
+    int mt, nt, wm, wn, wb;
+    constexpr int bm() const { return 32 * mt * wm; }
+    constexpr int bn() const { return 32 * nt * wn; }
+    constexpr bool operator==(const TileId& o) const { return mt == o.mt && nt == o.nt && wm == o.wm && wn == o.wn && wb == o.wb; }
+};
+template <int MT, int NT, int WM, int WN, int WB>
+struct Tile { static constexpr TileId id{MT, NT, WM, WN, WB}; };
+// THE list of tiles: f(Tile<...>{}) for the one `id` names; false if the library has none such.
+template <class F>
+bool visit_tile(const TileId& id, F f) {
+    auto among = [&](auto... t) { return ((decltype(t)::id == id && (f(t), true)) || ...); };
+    return among(Tile<1, 5, 4, 1, 4>{}, Tile<1, 7, 4, 1, 4>{}, Tile<1, 4, 4, 1, 4>{}, Tile<1, 2, 4, 1, 4>{}, Tile<2, 5, 4, 1, 4>{}, Tile<2, 4, 4, 1, 4>{}, Tile<2, 5, 2, 2, 4>{},
+                 Tile<1, 4, 4, 1, 8>{}, Tile<1, 2, 4, 1, 8>{}, Tile<2, 4, 4, 1, 8>{}, Tile<1, 4, 4, 1, 16>{}, Tile<1, 2, 4, 1, 16>{}, Tile<2, 4, 4, 1, 16>{},
+                 Tile<1, 4, 4, 1, 17>{}, Tile<1, 2, 4, 1, 17>{}, Tile<2, 4, 4, 1, 17>{});
 }
 
-// N-tile count of the 128-row kernel the dispatcher would pick for this width
-int nt_for(int N) { return N % 160 == 0 ? 5 : (N % 224 == 0 ? 7 : (N > 64 ? 4 : 2)); }
+// Which kernels are built on tile T: igemm_kernel (KS = 1, four waves) / igemm_k2_kernel (KS = 2: two K-groups in a 512-thread
+// block) for SPLIT (two segments) and the epilogue OUT.  plan_block() decides and refuses by it, launch() instantiates by it.
+template <class T>
+constexpr bool built(int KS, bool SPLIT, int OUT) {
+    constexpr int MT = T::id.mt, NT = T::id.nt, WM = T::id.wm, WB = T::id.wb;
+    constexpr bool rows128 = MT == 1 && WM == 4;
+    const bool rows = OUT == O_F32 || OUT == O_F16, heads = OUT == O_HROWS || OUT == O_HTR;
+    if (WB >= 16) return KS == 1 && !SPLIT && (OUT == O_F32 || OUT == (WB == 16 ? O_BF16 : O_F16));
+    // two K-groups: fp32 rows on every tile of 128 columns and more, fp16 rows on 128 x 160 (on the 256-row tiles they spill),
+    // split-K partials and the head-layout epilogues on the shapes the three UNets launch them with
+    if (KS == 2)
+        return !SPLIT && (WM == 4 || (MT == 2 && NT == 5)) && (NT == 4 || NT == 5 || NT == 7) && (WB == 4 || NT == 4) &&
+               (OUT == O_F32 || (OUT == O_F16 && NT == 5 && MT == 1) || (heads && WB == 4 && NT == 5 && WM == 4) ||
+                (OUT == O_PART && rows128 && (WB == 4 ? NT == 5 || NT == 7 : NT == 4)));
+    if (SPLIT) return rows && rows128;
+    // (head layouts behind int8 weights: the 128 x 128 tile only — the CIFAR attention block's q / k / v, 256 channels)
+    return rows || ((OUT == O_I32 || OUT == O_PART) && rows128) || (OUT == O_GEGLU && NT == 4 && WB == 4 && WM == 4) ||
+           (heads && ((WB == 4 && WM == 4) || (WB == 8 && MT == 1 && NT == 4)));
+}
+// ... and igemm_heads_group_kernel
+constexpr bool group_built(TileId t) { return t.mt == 1 && t.wm == 4 && (t.wb == 4 ? t.nt == 5 || t.nt == 7 || t.nt == 4 : t.wb == 8 && t.nt == 4); }
+
+template <int KS_, bool SPLIT_, int OUT_>
+struct Variant { static constexpr int KS = KS_, OUT = OUT_; static constexpr bool SPLIT = SPLIT_; };
+
+// One launch of the contraction as a plain value: plan() (run_bf16() for its mode) fills it without a HIP call, launch() issues it.
+struct Launch {
+    ConvD  k;                // the kernel's descriptor, block counts included
+    TileId tile;
+    int    out;              // O_*
+    bool   split;            // two segments
+    int    threads, nsplit;  // 256, or 512: two K-groups; K slices (grid.y) — >= 2: O_PART partials, the split-K finalise pass follows
+};
+
+// THE tile policy.  Width -> N tile: int4 weights 160 / 224 / 128 / 64 columns, everything else 128 / 64.  tall_ok: nothing but
+// the block count stands against 256-row tiles.  Split-K partials ask with out = O_PART and tall_ok = false: 128 rows.
+TileId choose_tile(int wbits, long M, int N, int out, bool two_seg, bool tall_ok, long Ktot) {
+    static const int wide_mink = getenv("QD_WIDE_MINK") ? atoi(getenv("QD_WIDE_MINK")) : 1280;
+    static const int wide_minblk = getenv("QD_WIDE_MINBLK") ? atoi(getenv("QD_WIDE_MINBLK")) : 200;
+    auto blocks = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
+    if (out == O_GEGLU) return {1, 4, 4, 1, wbits};            // (256-row GEGLU tiles: measured slower, profiles/r05_c4_ab_summary.txt)
+    const bool rows = out == O_F32 || out == O_F16 || out == O_BF16;
+    // 2 x 2 waves of 64 x 160: a 128 x 320 block moves 18 KB per K-step into LDS for 40960 MACs per K element where the
+    // 256 x 160 block of 4 x 1 waves moves 21 KB — the long-K convolutions are bound by exactly that L2 -> LDS traffic
+    // (profiles/r02_igemm_kstep_ablation.md).  Measured (profiles/r02b_igemm_tiles.md): -5 .. -13 % on the 32 x 32 level
+    // (M = 16384, N = 640), -5 .. -8 % on the 64 x 64 level (M = 65536, N = 320).  A 256 x 320 block of four 128 x 160
+    // waves (one wave per SIMD, 512 VGPRs) was 2.2x SLOWER.
+    if (wbits == 4 && N % 320 == 0 && rows && !two_seg && Ktot >= wide_mink && blocks(128, 320) >= wide_minblk) return {2, 5, 2, 2, 4};
+    // 256-row tiles (two 32-row tiles per wave: half the B-fragment reads and nibble unpacks per MFMA) whenever they still
+    // give every CU a block: int4 weights at 160 / 128 columns, the other weights at 128 columns behind row epilogues
+    const int nt = wbits < 8 && N % 160 == 0 ? 5 : (wbits < 8 && N % 224 == 0 ? 7 : (N > 64 ? 4 : 2));
+    const bool tall = tall_ok && (nt == 4 || nt == 5) && (wbits == 4 || rows) && blocks(256, 32 * nt) >= 256;
+    return {tall ? 2 : 1, nt, 4, 1, wbits};
+}
+
+// The end of every plan, once descriptor, epilogue, slices and tile are known: the block counts; two K-groups where the launch has at
+// most one tile per CU and a K loop worth splitting (and the tile builds them for this epilogue); the refusal of what is not built.
+int plan_block(Launch* L, TileId tile) {
+    ConvD& k = L->k;
+    k.nblk_m = (k.M + tile.bm() - 1) / tile.bm();
+    k.nblk_n = (k.Cout + tile.bn() - 1) / tile.bn();
+    const int ksteps = L->out == O_PART ? k.it_per : k.taps * k.seg[0].nsteps_tap;
+    const bool k2 = kgroups_knob() && !L->split && k.nseg == 1 && (long)k.nblk_m * k.nblk_n * L->nsplit <= 256 && ksteps >= kgroups_min_steps();
+    bool ok = false;
+    L->tile = tile;
+    visit_tile(tile, [&](auto t) {
+        L->threads = k2 && built<decltype(t)>(2, false, L->out) ? 512 : 256;
+        ok = built<decltype(t)>(L->threads / 256, L->split, L->out);
+    });
+    QD_REQUIRE(ok, "qd_conv2d_%s: unsupported variant split=%d out=%d tile %dx%d", tile.wb >= 16 ? "bf16" : "i8", (int)L->split, L->out, tile.bm(), tile.bn());
+    return 0;
+}
+
+// The only place that launches igemm_kernel / igemm_k2_kernel: the instantiation whose tile, K-groups, segments and epilogue
+// are the plan's, checked against the plan's block counts.
+int launch(const Launch& L, hipStream_t st) {
+    const ConvD& k = L.k;
+    const dim3 grid(k.nblk_m * k.nblk_n, L.nsplit), block(L.threads);
+    bool done = false;
+    visit_tile(L.tile, [&](auto t) {
+        using T = decltype(t);
+        constexpr TileId I = T::id;
+        auto variant = [&](auto v) {
+            using V = decltype(v);
+            if constexpr (built<T>(V::KS, V::SPLIT, V::OUT)) {
+                if (L.threads != 256 * V::KS || L.split != V::SPLIT || L.out != V::OUT) return;
+                if (k.nblk_m != (k.M + I.bm() - 1) / I.bm() || k.nblk_n != (k.Cout + I.bn() - 1) / I.bn()) return;
+                if constexpr (V::KS == 2) hipLaunchKernelGGL((igemm_k2_kernel<I.mt, I.nt, I.wm, I.wn, V::OUT, I.wb>), grid, block, 0, st, k);
+                else hipLaunchKernelGGL((igemm_kernel<I.mt, I.nt, I.wm, I.wn, V::SPLIT, V::OUT, I.wb>), grid, block, 0, st, k);
+                done = true;
+            }
+        };
+        // every (KS, SPLIT, OUT) that built() admits on some tile
+        variant(Variant<2, false, O_F32>{}); variant(Variant<2, false, O_F16>{}); variant(Variant<2, false, O_PART>{}); variant(Variant<2, false, O_HROWS>{});
+        variant(Variant<2, false, O_HTR>{}); variant(Variant<1, false, O_F32>{}); variant(Variant<1, false, O_F16>{}); variant(Variant<1, false, O_BF16>{});
+        variant(Variant<1, false, O_I32>{}); variant(Variant<1, false, O_PART>{}); variant(Variant<1, false, O_HROWS>{}); variant(Variant<1, false, O_HTR>{});
+        variant(Variant<1, false, O_GEGLU>{}); variant(Variant<1, true, O_F32>{}); variant(Variant<1, true, O_F16>{});
+    });
+    QD_REQUIRE(done, "qd_conv2d: the launch plan names no built kernel (tile %dx%d, %d threads, split=%d out=%d)", L.tile.bm(), L.tile.bn(), L.threads, (int)L.split, L.out);
+    return 0;
+}
 
 // Split-K policy.  Worth it only when the plain launch cannot fill the chip (<= 1 block per CU) AND the
 // K loop is long enough that the extra int32 partial traffic (2 * 4 * M * N bytes per split) is paid back.
@@ -1491,7 +1548,7 @@ int choose_splitk(const qd_conv_desc* d, int* it_per) {
     if (d->nseg != 1 || d->epilogue != QD_EPI_LINEAR) return 1;
     if (d->res_period != 0) return 1;             // the periodic residual lives in the fused epilogue only: never split (same bytes)
     const long M = (long)d->B * d->Ho * d->Wo;
-    const int  N = d->Cout, bn = 32 * (d->wbits == 8 ? (N > 64 ? 4 : 2) : nt_for(N));
+    const int  N = d->Cout, bn = choose_tile(d->wbits, M, N, O_PART, false, false, 0).bn();
     const long blocks0 = ((M + 127) / 128) * ((N + bn - 1) / bn);
     const int  total = d->kh * d->kw * ((d->seg[0].clen + 63) / 64);
     if (blocks0 > 256) return 1;
@@ -1509,7 +1566,17 @@ int choose_splitk(const qd_conv_desc* d, int* it_per) {
     return (total + *it_per - 1) / *it_per;
 }
 
-int run(const qd_conv_desc* d, int32_t* iout, void* stream) {
+// the geometry every mode of the kernel shares (the caller has checked the shape)
+void fill_geometry(ConvD& k, const qd_conv_desc* d) {
+    k.B = d->B; k.H = d->H; k.W = d->W; k.Ho = d->Ho; k.Wo = d->Wo; k.Cout = d->Cout;
+    k.kh = d->kh; k.kw = d->kw; k.stride = d->stride; k.pad_t = d->pad_t; k.pad_l = d->pad_l;
+    k.M = d->B * d->Ho * d->Wo; k.taps = d->kh * d->kw; k.nseg = d->nseg; k.ntiles = (d->Cout + 31) / 32; k.ups = d->upsample2x ? 1 : 0;
+    k.pointwise = k.taps == 1 && d->stride == 1 && d->pad_t == 0 && d->pad_l == 0 && d->H == d->Ho && d->W == d->Wo;
+}
+
+// Everything qd_conv2d_i8 / _acc decides about a launch — every check, the kernel descriptor, split-K or one pass, the tile, the
+// K-groups — without a HIP call.  group_member: the plan of a member of a grouped launch (128-row tiles).
+int plan(const qd_conv_desc* d, int32_t* iout, bool group_member, Launch* L) {
     QD_REQUIRE(d != nullptr, "qd_conv2d_i8: null descriptor");
     QD_REQUIRE(d->x && d->w && (d->out || iout), "qd_conv2d_i8: null tensor pointer");
     QD_REQUIRE(d->w_tiled, "qd_conv2d_i8: weights must be in the tile order of qd_pack_weights_t4 / _t8 (w_tiled = 1)");
@@ -1525,15 +1592,12 @@ int run(const qd_conv_desc* d, int32_t* iout, void* stream) {
     QD_REQUIRE(!w8 || d->epilogue == QD_EPI_LINEAR || ((d->epilogue == QD_EPI_HEADS_I8 || d->epilogue == QD_EPI_HEADS_T_I8) && d->Cout > 64),
                "qd_conv2d_i8: int8 weights take the linear epilogue, or the head-layout epilogues on more than 64 output channels");
     QD_REQUIRE(d->ldx % 16 == 0 && qd_aligned(d->x, 16) && qd_aligned(d->w, 16), "qd_conv2d_i8: x/w must be 16-byte aligned, ldx %% 16 == 0");
-    ConvD k{};
+    *L = Launch{};
+    ConvD& k = L->k;
     k.x = d->x; k.wt = d->w; k.out = d->out; k.iout = iout;
     k.bias = d->bias; k.rowbias = d->rowbias; k.residual = d->residual;
     k.ldx = d->ldx; k.ldo = d->ldo; k.ldr = d->ldr; k.ldrb = d->ld_rowbias;
-    k.B = d->B; k.H = d->H; k.W = d->W; k.Ho = d->Ho; k.Wo = d->Wo; k.Cout = d->Cout;
-    k.kh = d->kh; k.kw = d->kw; k.stride = d->stride; k.pad_t = d->pad_t; k.pad_l = d->pad_l;
-    k.M = d->B * d->Ho * d->Wo; k.taps = d->kh * d->kw; k.nseg = d->nseg;
-    k.pointwise = k.taps == 1 && d->stride == 1 && d->pad_t == 0 && d->pad_l == 0 && d->H == d->Ho && d->W == d->Wo;
-    k.ups = d->upsample2x ? 1 : 0;
+    fill_geometry(k, d);
     if (d->res_period != 0) {
         QD_REQUIRE(d->epilogue == QD_EPI_LINEAR && !iout, "qd_conv2d_i8: res_period needs the linear epilogue (fp32 / fp16 rows)");
         QD_REQUIRE(d->residual != nullptr, "qd_conv2d_i8: res_period without a residual");
@@ -1541,7 +1605,6 @@ int run(const qd_conv_desc* d, int32_t* iout, void* stream) {
                    "qd_conv2d_i8: res_period (%d) must divide M (%d) and be a multiple of Ho*Wo (%d)", d->res_period, k.M, d->Ho * d->Wo);
         k.res_period = d->res_period;
     }
-    k.ntiles = (d->Cout + 31) / 32;
     for (int s = 0; s < d->nseg; ++s) {
         const qd_conv_seg& g = d->seg[s];
         QD_REQUIRE(g.clen > 0 && g.clen % 16 == 0 && g.c0 % 16 == 0, "qd_conv2d_i8: segment %d c0/clen must be multiples of 16", s);
@@ -1605,11 +1668,9 @@ int run(const qd_conv_desc* d, int32_t* iout, void* stream) {
         k.oq = d->oq_params; k.oqmin = (float)d->oq_min; k.oqmax = (float)d->oq_max; k.oqoff = d->oq_off;
     }
     QD_REQUIRE(!(iout && split), "qd_conv2d_i8_acc: single segment only");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    L->out = out; L->split = split; L->nsplit = 1;
     const int N = d->Cout;
     const long M = k.M;
-    int rc;
-    auto blocks = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
     int it_per = 0;
     const int nsplit = (iout || !d->splitk_ws || d->gn_part) ? 1 : choose_splitk(d, &it_per);   // gn_part: fused epilogue only
     if (nsplit >= 2 && d->splitk_ws_bytes >= (int64_t)nsplit * M * N * 4) {
@@ -1617,72 +1678,37 @@ int run(const qd_conv_desc* d, int32_t* iout, void* stream) {
         k.iout = reinterpret_cast<int32_t*>(d->splitk_ws);
         k.it_per = it_per;
         k.vec = N % 4 == 0;
-        if (w8) rc = N > 64 ? dispatch<1, 4, 4, 1, 8>(k, false, O_PART, st, nsplit) : dispatch<1, 2, 4, 1, 8>(k, false, O_PART, st, nsplit);
-        else switch (nt_for(N)) {
-            case 5:  rc = dispatch<1, 5, 4, 1>(k, false, O_PART, st, nsplit); break;
-            case 7:  rc = dispatch<1, 7, 4, 1>(k, false, O_PART, st, nsplit); break;
-            case 4:  rc = dispatch<1, 4, 4, 1>(k, false, O_PART, st, nsplit); break;
-            default: rc = dispatch<1, 2, 4, 1>(k, false, O_PART, st, nsplit); break;
-        }
-        // a grouped launch's probe (g_capture set) launches nothing: the finalise pass would read stale partials, write `out`
-        // and, with out == residual, corrupt the residual the member's real launch reads next
-        if (rc || g_capture) return rc;
+        L->out = O_PART; L->split = false; L->nsplit = nsplit;
+        return plan_block(L, choose_tile(d->wbits, M, N, O_PART, false, false, 0));
+    }
+    // (too small a workspace: one pass.)  A block of a head layout must stay inside one sample.  Members of a grouped launch take
+    // 128-row tiles: three times the blocks fill the chip anyway, and the smaller tile's epilogue tail is shorter (heads_i8_out
+    // 1.82 -> 1.74 ms per SD evaluation, profiles/r06_group_ab.md)
+    const bool tall_ok = !split && mt2_ok && out != O_I32 && !group_member;
+    return plan_block(L, choose_tile(d->wbits, M, N, out, split, tall_ok, (long)k.taps * d->seg[0].clen));
+}
+
+// qd_conv2d_i8 / _acc: the plan, its launch and, behind K slices, the pass that sums them and applies the float epilogue.
+int run(const qd_conv_desc* d, int32_t* iout, void* stream) {
+    Launch L;
+    if (const int rc = plan(d, iout, false, &L)) return rc;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (const int rc = launch(L, st)) return rc;
+    if (L.nsplit >= 2) {
+        const ConvD& k = L.k;
         const SegD& sg = k.seg[0];
-        const long MN = M * N;
+        const long MN = (long)k.M * k.Cout;
         dim3 grid((unsigned)((MN + 255) / 256)), block(256);
         // (an 8-outputs-per-thread form of this pass for fp16 rows was measured +15 us per launch: the pass is bound by its
         //  nsplit int32 reads per output, of which the one-output-per-thread form keeps eight times more in flight)
-        if (d->out_dtype == QD_F16)
-            hipLaunchKernelGGL(splitk_finalize_kernel<__half>, grid, block, 0, st, k.iout, nsplit, MN, N, d->Ho * d->Wo, sg.scale, sg.zc, sg.zw,
-                               sg.zfill, k.bias, k.rowbias, k.ldrb, (const __half*)k.residual, k.ldr, (__half*)k.out, k.ldo);
-        else
-            hipLaunchKernelGGL(splitk_finalize_kernel<float>, grid, block, 0, st, k.iout, nsplit, MN, N, d->Ho * d->Wo, sg.scale, sg.zc, sg.zw,
-                               sg.zfill, k.bias, k.rowbias, k.ldrb, (const float*)k.residual, k.ldr, (float*)k.out, k.ldo);
-        QD_LAUNCH_CHECK("qd_conv2d_i8 (split-K)");
-        return 0;
+        auto finalize = [&](auto* out) {
+            using TO = std::remove_pointer_t<decltype(out)>;
+            hipLaunchKernelGGL(splitk_finalize_kernel<TO>, grid, block, 0, st, k.iout, L.nsplit, MN, k.Cout, d->Ho * d->Wo, sg.scale, sg.zc, sg.zw,
+                               sg.zfill, k.bias, k.rowbias, k.ldrb, (const TO*)k.residual, k.ldr, out, k.ldo);
+        };
+        if (d->out_dtype == QD_F16) finalize((__half*)k.out); else finalize((float*)k.out);
     }
-    static const int wide_mink = getenv("QD_WIDE_MINK") ? atoi(getenv("QD_WIDE_MINK")) : 1280;
-    static const int wide_minblk = getenv("QD_WIDE_MINBLK") ? atoi(getenv("QD_WIDE_MINBLK")) : 200;
-    const long Ktot = (long)k.taps * d->seg[0].clen;
-    const bool linear_out = out == O_F32 || out == O_F16;
-    // 256-row tiles (two 32-row tiles per wave: half the B-fragment reads and nibble unpacks per MFMA) whenever they still
-    // give every CU a block
-    auto want_mt2 = [&](int bn) {
-        if (split || !mt2_ok || out == O_I32) return false;
-        // members of a grouped launch take 128-row tiles: three times the blocks fill the chip anyway, and the smaller tile's
-        // epilogue tail is shorter (heads_i8_out 1.82 -> 1.74 ms per SD evaluation, profiles/r06_group_ab.md)
-        if (g_capture && !g_capture->query) return false;
-        return blocks(256, bn) >= 256;
-    };
-    if (w8) {                                      // int8 weights (CIFAR W8A8): 128-wide N tiles
-        if (N > 64) {
-            if (linear_out && want_mt2(128)) rc = dispatch<2, 4, 4, 1, 8>(k, split, out, st);
-            else rc = dispatch<1, 4, 4, 1, 8>(k, split, out, st);
-        } else {
-            rc = dispatch<1, 2, 4, 1, 8>(k, split, out, st);
-        }
-    } else if (geglu) {
-        rc = dispatch<1, 4, 4, 1>(k, split, out, st);          // (256-row GEGLU tiles: measured slower, profiles/r05_c4_ab_summary.txt)
-    } else if (N % 320 == 0 && (out == O_F32 || out == O_F16) && !split && Ktot >= wide_mink && blocks(128, 320) >= wide_minblk) {
-        // 2 x 2 waves of 64 x 160: a 128 x 320 block moves 18 KB per K-step into LDS for 40960 MACs per K element where the
-        // 256 x 160 block of 4 x 1 waves moves 21 KB — the long-K convolutions are bound by exactly that L2 -> LDS traffic
-        // (profiles/r02_igemm_kstep_ablation.md).  Measured (profiles/r02b_igemm_tiles.md): -5 .. -13 % on the 32 x 32 level
-        // (M = 16384, N = 640), -5 .. -8 % on the 64 x 64 level (M = 65536, N = 320).  A 256 x 320 block of four 128 x 160
-        // waves (one wave per SIMD, 512 VGPRs) was 2.2x SLOWER.
-        rc = dispatch<2, 5, 2, 2>(k, split, out, st);
-    } else if (N % 160 == 0) {
-        if (want_mt2(160)) rc = dispatch<2, 5, 4, 1>(k, split, out, st);
-        else rc = dispatch<1, 5, 4, 1>(k, split, out, st);
-    } else if (N % 224 == 0) {
-        rc = dispatch<1, 7, 4, 1>(k, split, out, st);
-    } else if (N > 64) {
-        if (want_mt2(128)) rc = dispatch<2, 4, 4, 1>(k, split, out, st);
-        else rc = dispatch<1, 4, 4, 1>(k, split, out, st);
-    } else {
-        rc = dispatch<1, 2, 4, 1>(k, split, out, st);
-    }
-    if (rc || g_capture) return rc;
-    QD_LAUNCH_CHECK("qd_conv2d_i8");
+    QD_LAUNCH_CHECK(L.nsplit >= 2 ? "qd_conv2d_i8 (split-K)" : "qd_conv2d_i8");
     return 0;
 }
 
@@ -1705,16 +1731,12 @@ int run_bf16(const qd_conv_desc* d, void* stream) {
     QD_REQUIRE(d->ldx % 8 == 0 && qd_aligned(d->x, 16) && qd_aligned(d->w, 16), "qd_conv2d_bf16: x/w must be 16-byte aligned, ldx %% 8 == 0");
     const qd_conv_seg& g = d->seg[0];
     QD_REQUIRE(g.clen > 0 && g.clen % 8 == 0 && g.c0 % 8 == 0 && g.c0 + g.clen <= d->ldx, "qd_conv2d_bf16: c0/clen must be multiples of 8 inside the row");
-    ConvD k{};
+    Launch L{};
+    ConvD& k = L.k;
     k.x = reinterpret_cast<const int8_t*>(d->x); k.wt = d->w; k.out = d->out;
     k.bias = d->bias; k.residual = d->residual;
     k.ldx = d->ldx * 2; k.ldo = d->ldo; k.ldr = d->ldr;
-    k.B = d->B; k.H = d->H; k.W = d->W; k.Ho = d->Ho; k.Wo = d->Wo; k.Cout = d->Cout;
-    k.kh = d->kh; k.kw = d->kw; k.stride = d->stride; k.pad_t = d->pad_t; k.pad_l = d->pad_l;
-    k.M = d->B * d->Ho * d->Wo; k.taps = d->kh * d->kw; k.nseg = 1;
-    k.pointwise = k.taps == 1 && d->stride == 1 && d->pad_t == 0 && d->pad_l == 0 && d->H == d->Ho && d->W == d->Wo;
-    k.ups = d->upsample2x ? 1 : 0;
-    k.ntiles = (d->Cout + 31) / 32;
+    fill_geometry(k, d);
     k.seg[0] = SegD{g.c0 * 2, g.clen * 2, g.kstep0, (g.clen * 2 + 63) / 64, nullptr, nullptr, nullptr, nullptr, nullptr};
     const size_t esz = d->out_dtype == QD_F32 ? 4 : 2;
     k.vec = d->Cout % 4 == 0 && d->ldo % 4 == 0 && qd_aligned(d->out, 4 * esz) &&
@@ -1726,19 +1748,10 @@ int run_bf16(const qd_conv_desc* d, void* stream) {
         QD_REQUIRE(d->gn_ld == 0 || d->gn_ld >= d->Cout, "qd_conv2d_bf16: gn_ld must be 0 or >= Cout");
         k.gn_ld = d->gn_ld ? (long)d->gn_ld : (long)d->Cout;
     }
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int N = d->Cout, out = d->out_dtype == QD_BF16 ? O_BF16 : d->out_dtype == QD_F16 ? O_F16 : O_F32;
-    const long M = k.M;
-    const bool mt2 = ((M + 255) / 256) * ((N + 127) / 128) >= 256;
-    int rc;
-    if (fh) {
-        if (N > 64) rc = mt2 ? dispatch<2, 4, 4, 1, 17>(k, false, out, st) : dispatch<1, 4, 4, 1, 17>(k, false, out, st);
-        else rc = dispatch<1, 2, 4, 1, 17>(k, false, out, st);
-    } else {
-        if (N > 64) rc = mt2 ? dispatch<2, 4, 4, 1, 16>(k, false, out, st) : dispatch<1, 4, 4, 1, 16>(k, false, out, st);
-        else rc = dispatch<1, 2, 4, 1, 16>(k, false, out, st);
-    }
-    if (rc) return rc;
+    L.out = d->out_dtype == QD_BF16 ? O_BF16 : d->out_dtype == QD_F16 ? O_F16 : O_F32;
+    L.split = false; L.nsplit = 1;
+    if (const int rc = plan_block(&L, choose_tile(d->wbits, k.M, d->Cout, L.out, false, true, (long)k.taps * k.seg[0].clen))) return rc;
+    if (const int rc = launch(L, reinterpret_cast<hipStream_t>(stream))) return rc;
     QD_LAUNCH_CHECK("qd_conv2d_bf16");
     return 0;
 }
@@ -1808,64 +1821,50 @@ extern "C" int64_t qd_conv2d_i8_splitk_ws_bytes(const qd_conv_desc* d) {
     return S < 2 ? 0 : (int64_t)S * d->B * d->Ho * d->Wo * d->Cout * 4;
 }
 
-template <int MT, int NT, int WM, int WN, int WB>
-void launch_group(const ConvG& g, int n, hipStream_t st) {
-    dim3 grid(g.d[0].nblk_m * g.d[0].nblk_n, n), block(256);
-    hipLaunchKernelGGL((igemm_heads_group_kernel<MT, NT, WM, WN, WB>), grid, block, 0, st, g);
-}
-
-// Up to three projections of ONE shape with head-layout epilogues as one launch (see igemm_heads_group_kernel); whatever does
-// not qualify — different shapes / tiles, another epilogue, a tile the group kernel is not built for — runs as
-// the n single launches it always was: same bytes either way.
+// Up to three projections of ONE shape with head-layout epilogues as one launch (see igemm_heads_group_kernel).  Every member is
+// planned, as a member, before anything is launched: a member the launcher refuses refuses the whole call with nothing run.
+// Plans that do not qualify together — different shapes / tiles, another epilogue, K slices, a tile the group kernel is not built
+// for — run as the n single launches they always were, each with the tile of its own single launch: same bytes either way.
 int run_group(const qd_conv_desc* const* descs, int n, void* stream) {
     QD_REQUIRE(descs && n >= 1 && n <= 3, "qd_conv2d_i8_group: 1..3 descriptors");
     for (int i = 0; i < n; ++i)
         QD_REQUIRE(!descs[i] || descs[i]->res_period == 0, "qd_conv2d_i8_group: res_period is not supported (head-layout epilogues)");
-    GroupCapture cap[3] = {};
-    bool ok = n >= 2;
-    for (int i = 0; i < n && ok; ++i) {
+    if (n == 1) return run(descs[0], nullptr, stream);
+    Launch L[3];
+    bool ok = true;
+    for (int i = 0; i < n; ++i) {
         QD_REQUIRE(descs[i] != nullptr, "qd_conv2d_i8_group: null descriptor");
-        g_capture = &cap[i];
-        const int rc = run(descs[i], nullptr, stream);
-        g_capture = nullptr;
-        if (rc) return rc;
-        const ConvD &a = cap[i].k, &b = cap[0].k;
-        ok = cap[i].tile >= 0 && !cap[i].split && (cap[i].out == O_HROWS || cap[i].out == O_HTR) && cap[i].tile == cap[0].tile &&
+        if (const int rc = plan(descs[i], nullptr, true, &L[i])) return rc;
+        const ConvD &a = L[i].k, &b = L[0].k;
+        ok = ok && L[i].nsplit == 1 && !L[i].split && (L[i].out == O_HROWS || L[i].out == O_HTR) && L[i].tile == L[0].tile &&
              a.M == b.M && a.Cout == b.Cout && a.nblk_m == b.nblk_m && a.nblk_n == b.nblk_n;
     }
-    if (ok) {
-        ConvG g{};
-        for (int i = 0; i < n; ++i) { g.d[i] = cap[i].k; g.out[i] = cap[i].out; }
-        hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-        switch (cap[0].tile) {
-            case tile_code(1, 5, 4, 1, 4): launch_group<1, 5, 4, 1, 4>(g, n, st); break;
-            case tile_code(1, 7, 4, 1, 4): launch_group<1, 7, 4, 1, 4>(g, n, st); break;
-            case tile_code(1, 4, 4, 1, 4): launch_group<1, 4, 4, 1, 4>(g, n, st); break;
-            case tile_code(1, 4, 4, 1, 8): launch_group<1, 4, 4, 1, 8>(g, n, st); break;
-            default: ok = false; break;
+    bool grouped = false;
+    if (ok) visit_tile(L[0].tile, [&](auto t) {
+        constexpr TileId I = decltype(t)::id;
+        if constexpr (group_built(I)) {
+            ConvG g{};
+            for (int i = 0; i < n; ++i) { g.d[i] = L[i].k; g.out[i] = L[i].out; }
+            dim3 grid(g.d[0].nblk_m * g.d[0].nblk_n, n), block(256);
+            hipLaunchKernelGGL((igemm_heads_group_kernel<I.mt, I.nt, I.wm, I.wn, I.wb>), grid, block, 0, reinterpret_cast<hipStream_t>(stream), g);
+            grouped = true;
         }
-        if (ok) {
-            QD_LAUNCH_CHECK("qd_conv2d_i8_group");
-            return 0;
-        }
+    });
+    if (grouped) {
+        QD_LAUNCH_CHECK("qd_conv2d_i8_group");
+        return 0;
     }
-    for (int i = 0; i < n; ++i) {
-        const int rc = run(descs[i], nullptr, stream);
-        if (rc) return rc;
-    }
+    for (int i = 0; i < n; ++i)
+        if (const int rc = run(descs[i], nullptr, stream)) return rc;
     return 0;
 }
 
-// The launch form qd_conv2d_i8(d) would take now, found by running run() itself as a probe: no second copy of the policy.
+// The launch form qd_conv2d_i8(d) would take now: its plan.
 extern "C" int qd_conv2d_i8_form(const qd_conv_desc* d, int32_t* form4) {
     QD_REQUIRE(form4 != nullptr, "qd_conv2d_i8_form: null form4");
-    GroupCapture cap{};
-    cap.query = true;
-    g_capture = &cap;
-    const int rc = run(d, nullptr, nullptr);
-    g_capture = nullptr;
-    if (rc) return rc;
-    form4[0] = cap.bm; form4[1] = cap.bn; form4[2] = cap.threads; form4[3] = cap.nsplit;
+    Launch L;
+    if (const int rc = plan(d, nullptr, false, &L)) return rc;
+    form4[0] = L.tile.bm(); form4[1] = L.tile.bn(); form4[2] = L.threads; form4[3] = L.nsplit;
     return 0;
 }
 
@@ -1879,36 +1878,32 @@ extern "C" int qd_conv2d_i8_acc(const qd_conv_desc* d, int32_t* iout, void* stre
     return run(d, iout, stream);
 }
 
-extern "C" int qd_pack_weights_t4(const float* w, const float* alpha, const float* delta, const float* zp, int Cout,
-                                  int Cin_total, int taps, int c0, int clen, int clen_pad, int n_levels, uint8_t* wt,
-                                  int kstep0, int ntiles, int32_t* wsum, void* stream) {
-    QD_REQUIRE(w && delta && zp && wt, "qd_pack_weights_t4: null pointer");
-    QD_REQUIRE(Cout > 0 && taps > 0 && clen > 0 && c0 >= 0 && c0 + clen <= Cin_total, "qd_pack_weights_t4: bad shape");
-    QD_REQUIRE(clen_pad % 16 == 0 && clen_pad >= clen, "qd_pack_weights_t4: clen_pad must be a multiple of 16");
-    QD_REQUIRE(n_levels >= 2 && n_levels <= 16, "qd_pack_weights_t4: n_levels %d does not fit a nibble", n_levels);
-    QD_REQUIRE(ntiles == (Cout + 31) / 32 && qd_aligned(wt, 16), "qd_pack_weights_t4: bad tile layout");
+// qd_pack_weights_t4 / _t8 (fn: the entry's name for its messages; bits: 4 or 8)
+static int pack_weights_tiled(const char* fn, int bits, const float* w, const float* alpha, const float* delta, const float* zp, int Cout, int Cin_total,
+                              int taps, int c0, int clen, int clen_pad, int n_levels, uint8_t* wt, int kstep0, int ntiles, int32_t* wsum, void* stream) {
+    QD_REQUIRE(w && delta && zp && wt, "%s: null pointer", fn);
+    QD_REQUIRE(Cout > 0 && taps > 0 && clen > 0 && c0 >= 0 && c0 + clen <= Cin_total, "%s: bad shape", fn);
+    QD_REQUIRE(clen_pad % 16 == 0 && clen_pad >= clen, "%s: clen_pad must be a multiple of 16", fn);
+    QD_REQUIRE(n_levels >= 2 && n_levels <= (1 << bits), "%s: n_levels %d does not fit a %s", fn, n_levels, bits == 4 ? "nibble" : "byte");
+    QD_REQUIRE(ntiles == (Cout + 31) / 32 && qd_aligned(wt, 16), "%s: bad tile layout", fn);
     const int nsteps_tap = (clen_pad + 63) / 64;
     const long total = (long)taps * nsteps_tap * ntiles * 128;
-    hipLaunchKernelGGL(pack_t4_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       w, alpha, delta, zp, Cout, Cin_total, taps, c0, clen, clen_pad, n_levels, wt, kstep0, ntiles, nsteps_tap, wsum);
-    QD_LAUNCH_CHECK("qd_pack_weights_t4");
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (bits == 4)
+        hipLaunchKernelGGL(pack_t4_kernel, grid, block, 0, st, w, alpha, delta, zp, Cout, Cin_total, taps, c0, clen, clen_pad, n_levels, wt, kstep0, ntiles, nsteps_tap, wsum);
+    else
+        hipLaunchKernelGGL(pack_t8_kernel, grid, block, 0, st, w, alpha, delta, zp, Cout, Cin_total, taps, c0, clen, n_levels, wt, kstep0, ntiles, nsteps_tap, wsum);
+    QD_LAUNCH_CHECK(fn);
     return 0;
 }
-
-extern "C" int qd_pack_weights_t8(const float* w, const float* alpha, const float* delta, const float* zp, int Cout,
-                                  int Cin_total, int taps, int c0, int clen, int clen_pad, int n_levels, uint8_t* wt,
-                                  int kstep0, int ntiles, int32_t* wsum, void* stream) {
-    QD_REQUIRE(w && delta && zp && wt, "qd_pack_weights_t8: null pointer");
-    QD_REQUIRE(Cout > 0 && taps > 0 && clen > 0 && c0 >= 0 && c0 + clen <= Cin_total, "qd_pack_weights_t8: bad shape");
-    QD_REQUIRE(clen_pad % 16 == 0 && clen_pad >= clen, "qd_pack_weights_t8: clen_pad must be a multiple of 16");
-    QD_REQUIRE(n_levels >= 2 && n_levels <= 256, "qd_pack_weights_t8: n_levels %d does not fit a byte", n_levels);
-    QD_REQUIRE(ntiles == (Cout + 31) / 32 && qd_aligned(wt, 16), "qd_pack_weights_t8: bad tile layout");
-    const int nsteps_tap = (clen_pad + 63) / 64;
-    const long total = (long)taps * nsteps_tap * ntiles * 128;
-    hipLaunchKernelGGL(pack_t8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
-                       w, alpha, delta, zp, Cout, Cin_total, taps, c0, clen, n_levels, wt, kstep0, ntiles, nsteps_tap, wsum);
-    QD_LAUNCH_CHECK("qd_pack_weights_t8");
-    return 0;
+extern "C" int qd_pack_weights_t4(const float* w, const float* alpha, const float* delta, const float* zp, int Cout, int Cin_total, int taps, int c0,
+                                  int clen, int clen_pad, int n_levels, uint8_t* wt, int kstep0, int ntiles, int32_t* wsum, void* stream) {
+    return pack_weights_tiled("qd_pack_weights_t4", 4, w, alpha, delta, zp, Cout, Cin_total, taps, c0, clen, clen_pad, n_levels, wt, kstep0, ntiles, wsum, stream);
+}
+extern "C" int qd_pack_weights_t8(const float* w, const float* alpha, const float* delta, const float* zp, int Cout, int Cin_total, int taps, int c0,
+                                  int clen, int clen_pad, int n_levels, uint8_t* wt, int kstep0, int ntiles, int32_t* wsum, void* stream) {
+    return pack_weights_tiled("qd_pack_weights_t8", 8, w, alpha, delta, zp, Cout, Cin_total, taps, c0, clen, clen_pad, n_levels, wt, kstep0, ntiles, wsum, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -355,11 +355,13 @@ def splitk_ws_bytes(c):
     return 0
 
 
-def conv2d_i8_form(c, kgroups=None):
+def conv2d_i8_form(c, kgroups=None, slices=1):
     """qd_conv2d_i8_form for a descriptor the launcher accepts: (rows per block, columns per block, threads per block, K slices).
-    The emulation never splits K, so this is the one-pass launch (K slices = 1, what the library answers without a split-K
-    workspace).  Written from DESIGN.md's description of the tile choice, NOT from the launcher's code: test_host_logic.py holds
-    the library's answer against it over a sweep of shapes, so a change of policy has to be stated twice to pass.
+    The emulation never splits K, so by default this is the one-pass launch (K slices = 1, what the library answers without a
+    split-K workspace); `slices` >= 2 asks for the form of the launch that writes that many K slices (how many is the split-K
+    policy's answer, qd_conv2d_i8_splitk_ws_bytes: not restated here).  Written from DESIGN.md's description of the tile choice,
+    NOT from the launcher's code: test_host_logic.py holds the library's answer against it over a sweep of shapes, so a change of
+    policy has to be stated twice to pass.
     kgroups: the qd_conv_config state (None = the library's start-up value, QD_KGROUPS)."""
     import os
     env = lambda name, default: int(os.environ.get(name, default))
@@ -371,6 +373,18 @@ def conv2d_i8_form(c, kgroups=None):
     linear = epi == 0
     f16 = linear and c.out is not None and c.out.dtype == torch.float16
     blocks = lambda bm, bn: -(-M // bm) * -(-N // bn)
+    if slices >= 2:
+        # split-K partials: 128-row blocks, columns by the width alone; two K-groups where the tile builds them for partials (int4
+        # weights at 160 / 224 columns, int8 weights at 128), the slices together leave at most one block per CU and one slice
+        # has at least eight K-steps
+        assert linear and not two_seg
+        if c.wbits == 8:
+            cols = 128 if N > 64 else 64
+        else:
+            cols = 160 if N % 160 == 0 else 224 if N % 224 == 0 else 128 if N > 64 else 64
+        steps = -(-taps * ((c.segs[0]["clen"] + 63) // 64) // slices)
+        k2 = bool(kgroups) and blocks(128, cols) * slices <= 256 and steps >= 8 and (cols == 128 if c.wbits == 8 else cols in (160, 224))
+        return (128, cols, 512 if k2 else 256, slices)
     # 256-row blocks wherever they still give each of the 256 CUs one: one segment, and with a head-layout epilogue whole blocks
     # inside one sample
     tall = lambda bn: not two_seg and (not heads or c.heads["T"] % 256 == 0) and blocks(256, bn) >= 256

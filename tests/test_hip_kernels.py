@@ -1013,6 +1013,50 @@ def _heads_epilogue_case(cuda, T, N, K, H, wbits):
     assert torch.equal(vs_g, vs_s)
 
 
+def test_grouped_projections_where_the_single_launch_takes_the_tall_tile(cuda):
+    """M = 2 x 16384 rows, N = 320, int4 weights: the smallest M at which a single launch takes 256-row tiles (256 of them: one
+    per CU) while a member of a grouped launch takes 128-row tiles.  (a) the q / k / v group of one shape writes exactly the
+    bytes and V column sums of three single launches; (b) so does the group whose q member has N = 640 — a shape mismatch, which
+    makes the library run every member as the single launch it would be on its own."""
+    from qdiff import engine, hip
+    B, T, H, K = 2, 16384, 8, 64
+    g = torch.Generator().manual_seed(77)
+    mkq = lambda dl, zp: NS(delta=torch.tensor(dl), zero_point=torch.tensor(float(zp)), n_bits=8, sym=False)
+    ap = engine.build_attn_plan(mkq(0.05, 128), mkq(0.05, 120), mkq(0.04, 131), NS(delta=torch.tensor(1.0 / 65535), zero_point=torch.tensor(0.0), n_bits=16, sym=False),
+                                1.0, 0.7, cuda)
+
+    def member(N):
+        wi = torch.randn(N, K, generator=g) * 0.05
+        xi = torch.randn(B * T, K, generator=g)
+        pk = engine.pack_module_weights(wi.to(cuda), [_weight_quantizer(wi, 4, True, g)], 0)
+        di, zi = R.uaq_init_scale(xi, 8, False, False, "max")
+        pl = engine.build_conv_plan(pk, [_aq(di, zi)], 1, 1, 1, 0, (torch.randn(N, generator=g) * 0.1).to(cuda))
+        assert engine.heads_fusable(pl, T, H)
+        return pl, engine.quantize_rows(xi.to(cuda), pl, 1, K, B * T, (0, 1, K))
+
+    q320, q640, k320, v320 = member(320), member(640), member(320), member(320)
+    probe = torch.zeros((B * H, engine.pad32(T), engine.pad32(40)), dtype=torch.int8, device=cuda)
+    assert hip.conv2d_i8_form(engine._heads_call(*q320, B, T, H, ap, 0, probe, None))[:2] == (256, 160)
+    for q in (q320, q640):
+        bufs = {}
+        for how in ("group", "single"):
+            outs = []
+            for (pl, xq), which in zip((q, k320, v320), (0, 1, 2)):
+                dpad = engine.pad32(pl.Cout // H)
+                shape = (B * H, dpad, engine.pad32(T)) if which == 2 else (B * H, engine.pad32(T), dpad)
+                outs.append(torch.zeros(shape, dtype=torch.int8, device=cuda))
+            vs = torch.full((B * H, engine.pad32(40)), 5 if how == "group" else 9, dtype=torch.int32, device=cuda)
+            if how == "group":
+                engine.project_heads_group([(pl, xq, which, o) for ((pl, xq), which, o) in zip((q, k320, v320), (0, 1, 2), outs)], B, T, H, ap, vs)
+            else:
+                for (pl, xq), which, o in zip((q, k320, v320), (0, 1, 2), outs):
+                    engine.project_heads(pl, xq, B, T, H, ap, which, o, vs)
+            bufs[how] = outs + [vs]
+        torch.cuda.synchronize()
+        for a, b in zip(bufs["group"], bufs["single"]):
+            assert torch.equal(a, b) and a.float().abs().max() > 0, q[0].Cout
+
+
 def test_attention_quantised_output_matches_quantise_rows(cuda):
     """qd_attn_i8 with out8: the bytes equal K1 applied to its own fp32 output (same float, same rounding)."""
     from qdiff import engine

@@ -138,11 +138,28 @@ def test_conv_launch_form_query_states_the_tile_policy(conv_lib):
     two segments, every epilogue), with and without two K-groups, and on the benchmark's own hot launches: whoever changes the
     policy changes this statement of it too, and the GPU tests that assert their tile by the query keep meaning what they say."""
     lib = conv_lib
+    cases = _form_sweep_cases()
+    seen = set()
+    for kg in (1, 0):
+        lib.qd_conv_config(kg)
+        for d, call in cases:
+            got = _form(lib, d)
+            assert got == abi_emulator.conv2d_i8_form(call, kgroups=kg), (kg, call.B, call.Ho, call.Wo, call.Cout, call.kh, [s["clen"] for s in call.segs],
+                                                                        call.wbits, call.out.dtype, call.epilogue, got)
+            seen.add(got[:3])
+    # the sweep reaches every block form the launcher has for these weights
+    assert {(256, 160, 256), (256, 128, 256), (128, 160, 256), (128, 160, 512), (128, 128, 512), (128, 320, 256), (128, 224, 256), (128, 64, 256),
+            (256, 160, 512), (256, 128, 512)} <= seen, sorted(seen)
+
+
+def _form_sweep_cases():
+    """[(descriptor on fake pointers, its ConvCall)] across the break points of the tile policy; the two named shapes of the
+    sliced-launch test (a short-slice and a 512-thread split) are among them."""
     cases = []
-    for M_shape in ((1, 1, 96), (2, 16, 16), (8, 16, 16), (16, 32, 32), (31, 16, 16), (32, 16, 16), (51, 16, 16), (52, 16, 16), (125, 8, 8),
+    for M_shape in ((1, 1, 96), (2, 16, 16), (8, 16, 16), (16, 8, 8), (16, 32, 32), (31, 16, 16), (32, 16, 16), (51, 16, 16), (52, 16, 16), (125, 8, 8),
                     (130, 10, 10), (1, 1, 13256), (16, 64, 64)):
         for N in (32, 64, 96, 128, 160, 224, 320, 448, 640, 800, 1000, 1002, 1024, 1280):
-            for k, clens in ((1, [64]), (1, [320]), (1, [512]), (3, [16]), (3, [80]), (3, [320]), (3, [640]), (1, [320, 160]), (3, [64, 64])):
+            for k, clens in ((1, [64]), (1, [320]), (1, [512]), (3, [16]), (3, [80]), (3, [320]), (3, [640]), (3, [1280]), (1, [320, 160]), (3, [64, 64])):
                 for wbits in (4, 8):
                     for f16 in (False, True):
                         cases.append(_form_case(M_shape, N, k, clens, wbits, f16))
@@ -156,17 +173,62 @@ def test_conv_launch_form_query_states_the_tile_policy(conv_lib):
                         cases.append(_form_case((B, 1, T), N, 1, [clen], 8, False, epi, T, heads))
     for M in (128, 4096, 32768):
         cases.append(_form_case((1, 1, M), 2560, 1, [320], 4, False, hip.EPI_GEGLU_I8))
+    return cases
+
+
+def test_conv_launch_form_query_with_a_splitk_workspace(conv_lib):
+    """The same sweep with a split-K workspace offered (a fake pointer and ample bytes: the query follows no pointer).  The K
+    slices of the form are those qd_conv2d_i8_splitk_ws_bytes sized the workspace for — one pass exactly where it answers 0 —
+    and a sliced launch has the form DESIGN.md §4.1 states for it (abi_emulator.conv2d_i8_form with `slices`): 128 rows, columns
+    by the width alone, 512 threads exactly when K-groups are on, tiles x slices <= 256, a slice has at least eight K-steps and
+    the tile builds two-group partials (int4 at 160 / 224 columns, int8 at 128).  With and without K-groups.
+    The two named shapes, as the library answers them: 3 x 3 320 -> 320 at (2, 16, 16) is cut into 15 slices of 3 K-steps —
+    too short for two groups, 256 threads; 3 x 3 1280 -> 1280 at (16, 8, 8) into 4 slices of 45 steps on 64 tiles — 512 threads.
+    A launch that emits GroupNorm statistics, one with a periodic residual and one of two segments stay one pass."""
+    lib = conv_lib
+    cases = _form_sweep_cases()
+    named = {((2, 16, 16), 320, 3, 320): {1: (128, 160, 256, 15), 0: (128, 160, 256, 15)},
+             ((16, 8, 8), 1280, 3, 1280): {1: (128, 160, 512, 4), 0: (128, 160, 256, 4)}}
+    found = set()
+    for d, _ in cases:
+        d.splitk_ws, d.splitk_ws_bytes = _FAKE, 1 << 40
     seen = set()
     for kg in (1, 0):
         lib.qd_conv_config(kg)
         for d, call in cases:
             got = _form(lib, d)
-            assert got == abi_emulator.conv2d_i8_form(call, kgroups=kg), (kg, call.B, call.Ho, call.Wo, call.Cout, call.kh, [s["clen"] for s in call.segs],
-                                                                        call.wbits, call.out.dtype, call.epilogue, got)
-            seen.add(got[:3])
-    # the sweep reaches every block form the launcher has for these weights
-    assert {(256, 160, 256), (256, 128, 256), (128, 160, 256), (128, 160, 512), (128, 128, 512), (128, 320, 256), (128, 224, 256), (128, 64, 256),
-            (256, 160, 512), (256, 128, 512)} <= seen, sorted(seen)
+            what = (kg, call.B, call.Ho, call.Wo, call.Cout, call.kh, [s["clen"] for s in call.segs], call.wbits, call.out.dtype, call.epilogue, got)
+            M, N = call.B * call.Ho * call.Wo, call.Cout
+            need = int(lib.qd_conv2d_i8_splitk_ws_bytes(ctypes.byref(d)))
+            assert (got[3] == 1) == (need == 0), what
+            if need:
+                assert got[3] * M * N * 4 == need and got[0] == 128, what
+                assert got[1] == ((128 if N > 64 else 64) if call.wbits == 8 else 160 if N % 160 == 0 else 224 if N % 224 == 0 else 128 if N > 64 else 64), what
+                seen.add((call.wbits,) + got[1:3])
+            assert got == abi_emulator.conv2d_i8_form(call, kgroups=kg, slices=got[3]), what
+            key = ((call.B, call.Ho, call.Wo), N, call.kh, call.segs[0]["clen"])
+            if key in named and call.wbits == 4 and len(call.segs) == 1 and call.out.dtype == torch.float32 and not call.epilogue:
+                assert got == named[key][kg], what
+                found.add((key, kg))
+    assert len(found) == 4, found
+    # sliced launches of every width class, on the four-wave block and (where built) on two K-groups
+    assert {(4, 160, 256), (4, 160, 512), (4, 224, 256), (4, 224, 512), (4, 128, 256), (4, 64, 256), (8, 128, 256), (8, 128, 512), (8, 64, 256)} == seen, sorted(seen)
+    # never sliced, whatever the workspace: GroupNorm statistics from the epilogue, a periodic residual, two segments — on a shape
+    # that is sliced without them
+    lib.qd_conv_config(1)
+    plain, call = _form_case((2, 16, 16), 320, 3, [320])
+    plain.splitk_ws, plain.splitk_ws_bytes = _FAKE, 1 << 40
+    assert _form(lib, plain)[3] >= 2
+    one_pass = abi_emulator.conv2d_i8_form(call, kgroups=1)
+    for fields in (dict(gn_part=_FAKE), dict(residual=_FAKE, ldr=320, res_period=256)):
+        d, _ = _form_case((2, 16, 16), 320, 3, [320])
+        d.splitk_ws, d.splitk_ws_bytes = _FAKE, 1 << 40
+        for name, value in fields.items():
+            setattr(d, name, value)
+        assert _form(lib, d) == one_pass and one_pass[3] == 1, fields
+    d, call = _form_case((2, 16, 16), 320, 3, [320, 320])
+    d.splitk_ws, d.splitk_ws_bytes = _FAKE, 1 << 40
+    assert _form(lib, d) == abi_emulator.conv2d_i8_form(call, kgroups=1) and _form(lib, d)[3] == 1
 
 
 def test_conv_launch_form_query_on_the_benchmark_shapes(conv_lib):
