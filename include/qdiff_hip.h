@@ -373,6 +373,8 @@ int qd_geglu_quant(const void* h, int h_dtype, int64_t M, int F, int64_t ldh,
  *     out8 != NULL: O is not written as fp32 but quantised with oq_* = the act quantiser of the Linear that
  *           consumes it (to_out[0], quant_block.py:221 -> quant_layer.py:256) and stored as its int8 input rows
  *           out8[b*T+t][ldo8] (K1 semantics; H*d must already be that Linear's padded input width).
+ *           The row stride of the output written (ldo8, else ldo) must be below 2^24 elements: the epilogue addresses
+ *           the 32 rows of a wave with 32-bit byte offsets from one 64-bit row base.
  *     q_asym: 0 when zq' == 0 (symmetric q quantiser), else 1: the kernel then restores the per-key term
  *           -zq' * sum_d k'[j][d].  qsum is ignored (may be NULL): the per-query terms -zk'*qsum_i + d*zq'*zk' are
  *           constant along a softmax row and cancel exactly.

@@ -62,44 +62,99 @@ __device__ __forceinline__ int attn_q_head(const AttnK& p, int bh) { return bh <
 //     with v_cvt_f32_i32; the 64-bit form (emulated i64 -> f32 conversion: a third of the epilogue's instructions, and the
 //     epilogue is half of a 77-key cross-attention call) stays for grids where the bound does not hold.  Same value either
 //     way: one correctly rounded conversion of the same integer.
+// The body is VALU work per stored element, so everything that does not depend on the element is decided or computed before
+// the element loop (profiles/attn_epilogue_isa.txt):
+//   * int8 or fp32 rows, the quantiser's fast flag, the 32- / 64-bit restoration and "all 32 queries of the wave exist" are
+//     compile-time tags, dispatched once: the copy a wave runs has no branch per element, and the full wave (q0 + 32 <= T,
+//     every wave of a T that is a multiple of 32) has no row predicate at all;
+//   * dd < d is constant per lane and column tile: it is tested once per tile, around the 16 elements as one block;
+//   * zv * us[r] is formed once per query, not once per element; the hi accumulators are added unconditionally: a caller that
+//     passes !hi_live has skipped every hi MFMA, so they still hold their initial zeros;
+//   * addresses: one 64-bit row base per wave (scalar), the lane's byte offset 4*half*ld + frow in 32 bits (the launcher
+//     bounds ld); a store costs one 64-bit add of the scalar row step ((r&3) + 8*(r>>2)) * ld, the column tile is its immediate;
+//   * two queries per step through the packed quantiser qd_bytes2_t (the bytes of qd_code_t by construction, common.h).
 template <int DT, bool P16>
 __device__ __forceinline__ void attn_write_rows(const AttnK& p, const v16i (&ol)[DT], const v16i (&oh)[P16 ? DT : 1], const int (&us)[16],
                                                 bool hi_live, int bh, int q0, int frow, int half, float dw, float zpw, float oscale, int zv) {
+#pragma clang fp contract(off)
     const int b = bh / p.H, hh = bh % p.H;
     const int izpw = (int)zpw;
+    const int q0u = __builtin_amdgcn_readfirstlane(q0);           // wave-uniform: the row base lives in scalar registers
     const QP oqp = p.out8 ? qd_load_qp(p.oq) : QP{1.f, 0.f, 1.f, false};
     const long kconst = (hi_live ? 256L * 128L : 0L) + 128L + (long)p.iwmin - (long)izpw;     // multiplies vsum
     const float code_sum = (1.0f / dw) * 1.01f + 0.5f * (float)p.S + (float)p.S * fmaxf(0.f, p.wmin - zpw) + 16.f;
     const bool small = code_sum * 255.f < 2.0e9f;                 // grid-uniform
-    auto epi = [&](auto ft, auto st) __attribute__((always_inline)) {
-    constexpr bool FAST = decltype(ft)::value, SMALL = decltype(st)::value;
+    const int nlive = p.T - q0u - 4 * half;                       // row step c of this lane exists iff c < nlive
+    const long row0 = (long)b * p.T + q0u;
+    auto epi = [&](auto o8t, auto ft, auto st, auto fullt) __attribute__((always_inline)) {
+    constexpr bool OUT8 = decltype(o8t)::value, FAST = decltype(ft)::value, SMALL = decltype(st)::value, FULL = decltype(fullt)::value;
+    constexpr unsigned ES = OUT8 ? 1u : 4u;                        // bytes per stored element
+    const long ld = OUT8 ? p.ldo8 : p.ldo;
+    char* const base = (OUT8 ? reinterpret_cast<char*>(p.out8) : reinterpret_cast<char*>(p.out)) + (row0 * ld + hh * p.d) * (long)ES;
+    const unsigned ldb = (unsigned)ld * ES;                        // 32 * ldb < 2^31 (launcher)
+    const unsigned lofs = (unsigned)(4 * half) * ldb + (unsigned)frow * ES;
+    const QB oqb = qd_bytes_setup(oqp, p.oqmin, p.oqmax, p.oqoff);
+    const v2f osc = qd_splat2(oscale);
+    unsigned nzu[SMALL ? 16 : 1];                                  // -zv * us[r] (the 64-bit form is rare: it multiplies per element)
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+        if constexpr (SMALL) nzu[r] = 0u - (unsigned)zv * (unsigned)us[r];
 #pragma unroll
     for (int t = 0; t < DT; ++t) {
         const int dd = t * 32 + frow;
-        const long vs = (dd < p.d) ? p.vsum[(long)bh * p.dpad + dd] : 0;
-        const long ct = kconst * vs + (long)p.S * izpw * zv;      // the column's share
+        if (dd >= p.d) continue;                                   // once per column tile: the lane takes part in all of it or in none
+        const int vsi = p.vsum[(long)bh * p.dpad + dd];
+        // the column's share; the 32-bit form is the low word of the 64-bit one
+        const long ctl = SMALL ? 0L : kconst * (long)vsi + (long)p.S * izpw * zv;
+        const unsigned ctu = (unsigned)kconst * (unsigned)vsi + (unsigned)p.S * (unsigned)izpw * (unsigned)zv;
+        // lane address of row 0 of the column tile; a row adds its scalar step, the tile is the store's immediate
+        char* const cp = base + (unsigned long)lofs + (unsigned)t * 32u * ES;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int il = (r & 3) + 8 * (r >> 2) + 4 * half;
-            const int i = q0 + il;
-            if (dd >= p.d || i >= p.T) continue;
-            float o;
-            if (SMALL) {
-                unsigned I = (unsigned)ol[t][r] + (unsigned)ct - (unsigned)zv * (unsigned)us[r];
-                if (P16 && hi_live) I += (unsigned)oh[P16 ? t : 0][r] << 8;
-                o = (float)(int)I * oscale;
+        for (int r = 0; r < 16; r += 2) {                          // two queries per step: the float math runs packed
+            v2f f;
+            if constexpr (SMALL) {
+                unsigned I0 = (unsigned)ol[t][r] + ctu + nzu[r], I1 = (unsigned)ol[t][r + 1] + ctu + nzu[r + 1];
+                if (P16) {
+                    I0 += (unsigned)oh[P16 ? t : 0][r] << 8;
+                    I1 += (unsigned)oh[P16 ? t : 0][r + 1] << 8;
+                }
+                f = v2f{(float)(int)I0, (float)(int)I1};
             } else {
-                long I = (long)ol[t][r] + ct - (long)zv * us[r];
-                if (P16 && hi_live) I += 256L * (long)oh[P16 ? t : 0][r];
-                o = (float)I * oscale;
+                long I0 = (long)ol[t][r] + ctl - (long)zv * us[r], I1 = (long)ol[t][r + 1] + ctl - (long)zv * us[r + 1];
+                if (P16) {
+                    I0 += 256L * (long)oh[P16 ? t : 0][r];
+                    I1 += 256L * (long)oh[P16 ? t : 0][r + 1];
+                }
+                f = v2f{(float)I0, (float)I1};
             }
-            if (p.out8) p.out8[((long)b * p.T + i) * p.ldo8 + hh * p.d + dd] = (int8_t)(qd_code_t<FAST>(o, oqp, p.oqmin, p.oqmax) - p.oqoff);
-            else p.out[((long)b * p.T + i) * p.ldo + hh * p.d + dd] = o;
+            const v2f o = f * osc;
+            int b0 = 0, b1 = 0;
+            if constexpr (OUT8) qd_bytes2_t<FAST>(o, oqp, oqb, b0, b1);
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int c = ((r + e) & 3) + 8 * ((r + e) >> 2);
+                if (!FULL && c >= nlive) continue;
+                char* const ep = cp + (unsigned long)((unsigned)c * ldb);
+                if constexpr (OUT8) *reinterpret_cast<int8_t*>(ep) = (int8_t)(e ? b1 : b0);
+                else *reinterpret_cast<float*>(ep) = e ? o.y : o.x;
+            }
+            // the widest instances (256 accumulators, one wave per SIMD) keep the pairs apart: hoisted accumulator reads cost them scratch
+            if constexpr (DT * (P16 ? 2 : 1) >= 16) __builtin_amdgcn_sched_barrier(0);
         }
     }
     };
-    if (small) QD_FAST_DISPATCH(oqp.fast, [&](auto ft) __attribute__((always_inline)) { epi(ft, std::true_type{}); });
-    else QD_FAST_DISPATCH(oqp.fast, [&](auto ft) __attribute__((always_inline)) { epi(ft, std::false_type{}); });
+    auto pick = [&](auto o8t, auto ft) __attribute__((always_inline)) {
+        const bool full = q0u + 32 <= p.T;
+        if (small) {
+            if (full) epi(o8t, ft, std::true_type{}, std::true_type{});
+            else epi(o8t, ft, std::true_type{}, std::false_type{});
+        } else {
+            if (full) epi(o8t, ft, std::false_type{}, std::true_type{});
+            else epi(o8t, ft, std::false_type{}, std::false_type{});
+        }
+    };
+    if (p.out8) QD_FAST_DISPATCH(oqp.fast, [&](auto ft) __attribute__((always_inline)) { pick(std::true_type{}, ft); });
+    else pick(std::false_type{}, std::false_type{});
 }
 
 // prm layout (device floats): 0 cs = dq*dk*scale | 1 zq' | 2 zk' | 3 dw | 4 zpw | 5 dw*dv | 6 zv'
@@ -1315,6 +1370,9 @@ extern "C" int qd_attn_i8_qp(const int8_t* q, const int8_t* k, const int8_t* vt,
     QD_REQUIRE(q && k && vt && vsum && prm && (out || out8), "qd_attn_i8: null pointer");
     QD_REQUIRE(!out8 || (oq_params && ldo8 >= (int64_t)H * d && oq_max - oq_off <= 127 && oq_min - oq_off >= -128),
                "qd_attn_i8: quantised output needs oq_params, ldo8 >= H*d and a grid that fits int8");
+    // the epilogue addresses the 32 rows of a wave with 32-bit byte offsets from a 64-bit row base (attn_write_rows)
+    QD_REQUIRE(out8 ? ldo8 < (1L << 24) : (ldo >= 0 && ldo < (1L << 24)), "qd_attn_i8: output row stride must be below 2^24 elements (got %ld)",
+               (long)(out8 ? ldo8 : ldo));
     QD_REQUIRE(BH > 0 && H > 0 && BH % H == 0 && T > 0 && S > 0 && d > 0, "qd_attn_i8: bad shape");
     QD_REQUIRE(q_heads > 0 && BH % q_heads == 0 && q_heads % H == 0,
                "qd_attn_i8_qp: q_heads (%d) must divide BH (%d) and be a multiple of H (%d)", q_heads, BH, H);

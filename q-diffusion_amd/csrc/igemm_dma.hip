@@ -680,17 +680,19 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             const int rbase = wrow0 + i * 32;
+            int as[16];
+            row_terms(rbase, as);                      // once per row tile: four 16-byte reads, not one 4-byte read per element
 #pragma unroll
             for (int jp = 0; jp < NT / 2; ++jp) {
                 const int lv = wn * WCOLS + (2 * jp) * 32 + frow, lg = lv + 32;     // tile-local channel of value / gate
                 const float sv = sScale[lv], sgt = sScale[lg];
-                const int zcv = sZc[lv], zcg = sZc[lg];
                 const int zwv = sZw[lv], zwg = sZw[lg];
+                const int zcv = sZc[lv] - zwv * kz, zcg = sZc[lg] - zwg * kz;       // kz folded into the channel constant (row_terms)
                 const float bv = sBias[lv], bg = sBias[lg];
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {      // two rows per step: the float math runs packed (v_pk_*_f32)
                     const int rl0 = crow(r) + 4 * fhalf, rl1 = crow(r + 1) + 4 * fhalf;
-                    const int as0 = sAsum[rbase + rl0] - kz, as1 = sAsum[rbase + rl1] - kz;
+                    const int as0 = as[r], as1 = as[r + 1];
                     const v2f vi = {(float)(acc[i][2 * jp][r] - zcv - __mul24(zwv, as0)), (float)(acc[i][2 * jp][r + 1] - zcv - __mul24(zwv, as1))};
                     const v2f gi = {(float)(acc[i][2 * jp + 1][r] - zcg - __mul24(zwg, as0)), (float)(acc[i][2 * jp + 1][r + 1] - zcg - __mul24(zwg, as1))};
                     const v2f val = qd_fma2(vi, qd_splat2(sv), qd_splat2(bv)), gate = qd_fma2(gi, qd_splat2(sgt), qd_splat2(bg));
@@ -843,6 +845,7 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
     }
     if constexpr (OUT == O_HTR) {
         const QP oqp = qd_load_qp(p.oq);
+        const QB oqb = qd_bytes_setup(oqp, p.oqmin, p.oqmax, p.oqoff);
         int8_t* o8 = reinterpret_cast<int8_t*>(p.out);
         const int bidx = m0 / p.hdT, t0 = m0 - bidx * p.hdT;
         int* sPart = reinterpret_cast<int*>(smem);            // [4][WCOLS] column-sum partials (the ring is dead by now)
@@ -856,27 +859,33 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
             const int nn = nok ? n0 + cl : 0;
             const int h = (int)__umulhi((unsigned)nn, p.hdrcp), dd = nn - h * p.hdd;     // nn / hdd (exact: nn < 2^16)
             const float sc = sScale[cl];
-            const int zc_n = sZc[cl], zw_n = sZw[cl];
+            const int zw_n = sZw[cl];
+            const int zc2 = sZc[cl] - zw_n * kz;       // kz folded into the channel constant (row_terms)
             const float bias_n = sBias[cl];
             int8_t* ob = o8 + (((long)bidx * p.hdH + h) * p.hddpad + dd) * p.hdTpad + t0 + fhalf * 16;
             int csum = 0;
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 const int tile0 = wrow0 + i * 32;      // first row of this 32-key tile inside the block
+                int as[16];
+                row_terms(tile0, as);
                 v4i pk;
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    unsigned w = 0;
+                    // four codes per word through the packed quantiser (the bytes of qd_code_t - off, common.h); the projection is
+                    // the fused multiply-add this expression has always compiled to, written out so that it stays one
+                    v2f v01, v23;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
+                    for (int e = 0; e < 4; e += 2) {
                         const int r = 4 * g + e;
-                        const int rowl = tile0 + 4 * fhalf + crow(r);
-                        const int I = acc[i][j][r] - zc_n - __mul24(zw_n, sAsum[rowl] - kz);
-                        const float v = (float)I * sc + bias_n;
-                        const int code = qd_code_t<FAST>(v * p.oqpre, oqp, p.oqmin, p.oqmax) - p.oqoff;
-                        csum += code;
-                        w |= (unsigned)(code & 0xff) << (8 * e);
+                        const int I0 = acc[i][j][r] - zc2 - __mul24(zw_n, as[r]);
+                        const int I1 = acc[i][j][r + 1] - zc2 - __mul24(zw_n, as[r + 1]);
+                        const v2f v = qd_fma2(v2f{(float)I0, (float)I1}, qd_splat2(sc), qd_splat2(bias_n)) * qd_splat2(p.oqpre);
+                        if (e == 0) v01 = v;
+                        else v23 = v;
                     }
+                    const unsigned w = qd_pack4_t<FAST>(v01.x, v01.y, v23.x, v23.y, oqp, oqb);
+                    csum = __builtin_amdgcn_sdot4((int)w, 0x01010101, csum, false);     // the same integer sum of the signed stored codes
                     pk[g] = (int)w;
                 }
                 // key slot p = half*16 + r  <->  key (r&3) + 8*(r>>2) + 4*half of the tile (attn_i8.hip): the
