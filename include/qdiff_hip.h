@@ -379,10 +379,13 @@ int qd_geglu_quant(const void* h, int h_dtype, int64_t M, int F, int64_t ldh,
  *           -zq' * sum_d k'[j][d].  qsum is ignored (may be NULL): the per-query terms -zk'*qsum_i + d*zq'*zk' are
  *           constant along a softmax row and cancel exactly.
  *     kterm (ABI 18; the slot that used to be `ksum`): NULL, or the table qd_attn_keyterm wrote for THIS k operand and
- *           THIS prm.  Shapes with qd_attn_uses_keyterm(d, S, q_asym) == 1 (d < 64, d % 32 != 0, S >= 512: SD's 4096-token level)
+ *           THIS prm.  Shapes with qd_attn_uses_keyterm(d, S, q_asym) == 1 (SD's 4096-token level; the rule: next paragraph)
  *           then seed the score accumulators from the table instead of issuing constant-operand MFMAs (2 of the 4
  *           score MFMAs of a 32x32 tile carried no data); results are bit-identical with and without it.  Other shapes
  *           ignore it.
+ *     Which kernel runs: ONE rule, the table of DESIGN.md §4.4 (head dim, key count, q symmetry, table present, the knobs of
+ *           qd_attn_config -> kernel family / per-key term mode / launches).  qd_attn_i8_form answers it for a call;
+ *           qd_attn_uses_keyterm and qd_attn_ws_bytes are its corollaries for a shape.
  *     qd_attn_keyterm: kterm[bh][j] = 0x4B400000 - zq' * sum_{c < dpad} k[bh][j][c]  (int32 [BH][Spad], dpad 32, 64 or 96; pad
  *           bytes of k are zero).  One pass over the K operand; recompute whenever k or prm[1] changes — a cross-attention
  *           whose context is constant over a sampling run computes it once (quant_block.py:193-195 recomputes k per step).
@@ -426,6 +429,20 @@ int qd_attn_i8_qp(const int8_t* q, const int8_t* k, const int8_t* vt,
                   float* out, int64_t ldo,
                   int8_t* out8, int64_t ldo8, const float* oq_params, int oq_min, int oq_max, int oq_off,
                   void* ws, int64_t ws_bytes, void* stream, int q_heads);
+/* qd_attn_i8_form (additive in ABI 20): the launch form qd_attn_i8_qp would take for these arguments under the current knobs —
+ * the launcher's own checks and kernel choice with the launch withheld: no HIP call, no pointer followed; it refuses what the
+ * launcher refuses, with the launcher's message.  The stream's slot holds form4 (4 ints, host memory):
+ *   form4[0] kernel family: 0 attn_kernel, 1 register-fed lean kernel, 2 LDS-staged (statistics + two P.V launches)
+ *   form4[1] DT = dpad / 32
+ *   form4[2] families 1, 2: per-key term mode, 0 none (symmetric q) / 1 constant-operand MFMAs / 2 key-term table; family 0: q_asym
+ *   form4[3] launches: 1, or 3 for family 2 */
+int qd_attn_i8_form(const int8_t* q, const int8_t* k, const int8_t* vt,
+                    const int32_t* qsum, const int32_t* kterm, const int32_t* vsum,
+                    int BH, int H, int T, int S, int d, int Tpad, int Spad, int dpad,
+                    const float* prm, int wbits, int wmin, int wmax, int q_asym,
+                    float* out, int64_t ldo,
+                    int8_t* out8, int64_t ldo8, const float* oq_params, int oq_min, int oq_max, int oq_off,
+                    void* ws, int64_t ws_bytes, int32_t* form4, int q_heads);
 
 /* ------------------------------------------------------------------------------------------
  * K7s/K8s  the two attention contractions as standalone batched integer GEMMs, for callers that use

@@ -1238,34 +1238,6 @@ __global__ __launch_bounds__(256) void attn_keyterm_rows_kernel(const int8_t* __
     kterm[r] = QD_MAGICI + nzq * s;
 }
 
-// The LDS-staged path: statistics, then the two P.V launches (every block runs in exactly one of them).  kt: 0 = symmetric q
-// (no per-key term), 2 = key-term table (AttnK::kterm).  ws: [BH][Tpad] AttnStat + one int per block.
-template <int DT>
-int launch_lds(const AttnK& k, bool p16, int kt, void* ws, hipStream_t st) {
-    dim3 grid((unsigned)(k.gx * k.BH));
-    AttnStat* stat = reinterpret_cast<AttnStat*>(ws);
-    int* flag = reinterpret_cast<int*>(stat + (long)k.BH * k.Tpad);
-    if (kt == 2) hipLaunchKernelGGL((attn_stats_kernel<DT, 2>), grid, dim3(256), 0, st, k, stat, flag, p16 ? 1 : 0);
-    else hipLaunchKernelGGL((attn_stats_kernel<DT, 0>), grid, dim3(256), 0, st, k, stat, flag, p16 ? 1 : 0);
-#define QD_PV_CASE(P, K)                                                                                          \
-    if (p16 == P && kt == K) {                                                                                    \
-        hipLaunchKernelGGL((attn_pv_kernel<DT, P, K, false>), grid, dim3(256), 0, st, k, (const AttnStat*)stat, (const int*)flag); \
-        hipLaunchKernelGGL((attn_pv_kernel<DT, P, K, true>), grid, dim3(256), 0, st, k, (const AttnStat*)stat, (const int*)flag);  \
-    }
-    QD_PV_CASE(true, 0) QD_PV_CASE(true, 2) QD_PV_CASE(false, 0) QD_PV_CASE(false, 2)
-#undef QD_PV_CASE
-    return 0;
-}
-
-template <int DT>
-int launch_lean(const AttnK& k, bool p16, int kt, hipStream_t st) {
-    dim3 grid((unsigned)(k.gx * k.BH));
-#define QD_LEAN_CASE(P, K) if (p16 == P && kt == K) hipLaunchKernelGGL((attn_lean_kernel<DT, P, K>), grid, dim3(256), 0, st, k);
-    QD_LEAN_CASE(true, 0) QD_LEAN_CASE(true, 1) QD_LEAN_CASE(true, 2) QD_LEAN_CASE(false, 0) QD_LEAN_CASE(false, 1) QD_LEAN_CASE(false, 2)
-#undef QD_LEAN_CASE
-    return 0;
-}
-
 // one thread per 16-byte chunk of a K row: row sums by v_dot4 + a butterfly over the CPR lanes of a row
 template <int CPR>
 __global__ __launch_bounds__(256) void attn_keyterm_kernel(const int8_t* __restrict__ k, int32_t* __restrict__ kterm, const float* __restrict__ prm,
@@ -1283,16 +1255,6 @@ __global__ __launch_bounds__(256) void attn_keyterm_kernel(const int8_t* __restr
     if (c < nchunks && (c % CPR) == 0) kterm[c / CPR] = QD_MAGICI + nzq * s;
 }
 
-template <int DT>
-int launch_dt(const AttnK& k, bool p16, bool asym, hipStream_t st) {
-    dim3 grid((unsigned)(k.gx * k.BH));
-    if (p16 && asym) hipLaunchKernelGGL((attn_kernel<DT, true, true>), grid, dim3(256), 0, st, k);
-    else if (p16) hipLaunchKernelGGL((attn_kernel<DT, true, false>), grid, dim3(256), 0, st, k);
-    else if (asym) hipLaunchKernelGGL((attn_kernel<DT, false, true>), grid, dim3(256), 0, st, k);
-    else hipLaunchKernelGGL((attn_kernel<DT, false, false>), grid, dim3(256), 0, st, k);
-    return 0;
-}
-
 }  // namespace
 
 // Run-time knobs of the attention launcher: read from the environment ONCE (first call), changed afterwards only through
@@ -1305,14 +1267,38 @@ static AttnKnobs& attn_knobs() {
     }();
     return k;
 }
-// the lean / LDS-staged kernels: a padding row of V^T for the code sums (d not a multiple of 32) and |scores| < 2^22
-// (d * 255 * 128 < 2^22 <=> d <= 128).  Default: d < 64 (SD's 4096-token level).  d = 80 (SD's 1024-token level, three
-// 32-byte K slabs per key) runs on the register-fed lean kernel only with QD_ATTN_LEAN=3: measured SLOWER than
-// attn_kernel<3> (127 vs 113 us per 1024-key self-attention call, profiles/r04_attn_keyterm.md) — without LDS staging the
-// three slabs per key come through the vector-memory path per wave, which costs more than the constant-operand MFMAs saved.
-static bool attn_lean_shape(int d) {
-    const int lean = attn_knobs().lean;
-    return lean != 0 && (d & 31) != 0 && (d < 64 || (d < 96 && lean == 3));
+
+// An instantiation by its compile-time tuple.  family: attn_kernel / attn_lean_kernel / attn_stats_kernel + two attn_pv_kernel
+// launches; dt = dpad / 32; term: KT of F_LEAN and F_LDS — 0 = symmetric q (no per-key term), 1 = constant-operand MFMAs, 2 =
+// key-term table —, ASYM of F_DENSE; p16: 16-bit probability codes.
+enum { F_DENSE = 0, F_LEAN = 1, F_LDS = 2 };
+struct FormId {
+    int family, dt, term;
+    bool p16;
+    constexpr bool operator==(const FormId& o) const { return family == o.family && dt == o.dt && term == o.term && p16 == o.p16; }
+};
+
+// THE kernel-choice rule (the table of DESIGN.md §4.4; tests/abi_emulator.py attn_i8_form states it a second time): pure, for the
+// exact pads ceil32.  pipe: 2 = LDS-staged kernel wherever it pays (default), 0 = attn_lean_kernel everywhere (A/B runs and
+// the equality test), 3 = LDS-staged kernel on every eligible shape.
+static FormId attn_policy(int d, int S, bool q_asym, bool have_kterm, const AttnKnobs& kn) {
+    const int dpad = (d + 31) / 32 * 32, Spad = (S + 31) / 32 * 32;
+    // the lean / LDS-staged kernels: a padding row of V^T for the code sums (d not a multiple of 32) and |scores| < 2^22
+    // (d * 255 * 128 < 2^22 <=> d <= 128).  Default: d < 64 (SD's 4096-token level).  d = 80 (SD's 1024-token level, three
+    // 32-byte K slabs per key) runs on the register-fed lean kernel only with QD_ATTN_LEAN=3: measured SLOWER than
+    // attn_kernel<3> (127 vs 113 us per 1024-key self-attention call, profiles/r04_attn_keyterm.md) — without LDS staging the
+    // three slabs per key come through the vector-memory path per wave, which costs more than the constant-operand MFMAs saved.
+    if (kn.lean == 0 || (d & 31) == 0 || !(d < 64 || (d < 96 && kn.lean == 3))) return {F_DENSE, dpad / 32, q_asym ? 1 : 0, false};
+    // the table pays where the LDS-staged kernel runs (thousands of keys); the register-fed kernel on short key axes (the 77
+    // context tokens: 3 tiles per sweep, 3 waves per SIMD) keeps the constant-operand MFMAs — it has no registers to spare
+    // for 16 seeds per tile and nothing to gain from them; pipe modes 0 / 3 (tests, A/B runs) take a table on every key axis
+    const bool table = q_asym && kn.ktab != 0 && (kn.pipe != 2 || S >= 512);
+    const int term = !q_asym ? 0 : (have_kterm && table) ? 2 : 1;
+    // the LDS-staged path: a key axis long enough for the ring start-up and the barriers to pay (pipe 2: S >= 512; pipe 3: any)
+    // that fits the constant row of ones, two K slabs at most; without a table for an asymmetric q (term 1: the constant-operand
+    // MFMAs, A/B runs with ktab = 0) the register-fed kernel runs instead
+    const bool lds = dpad <= 64 && Spad <= QD_ONES_ROW && (kn.pipe == 3 || (kn.pipe == 2 && S >= 512));
+    return {lds && term != 1 ? F_LDS : F_LEAN, dpad / 32, term, false};
 }
 
 extern "C" void qd_attn_config(int pipe_mode, int xcd, int ktab, int lean) {
@@ -1323,29 +1309,15 @@ extern "C" void qd_attn_config(int pipe_mode, int xcd, int ktab, int lean) {
     if (lean >= 0) k.lean = lean;
 }
 
-// shapes of the LDS-staged two-kernel path: a lean shape (d < 64, not a multiple of 32) whose key axis is long enough for
-// the ring start-up and the barriers to pay (pipe 2: S >= 512; pipe 3: any) and fits the constant row of ones
-static bool attn_lds_shape(int T, int S, int d, int Spad, int dpad) {
-    (void)T;
-    const AttnKnobs& kn = attn_knobs();
-    if (!attn_lean_shape(d) || dpad > 64 || Spad > QD_ONES_ROW) return false;
-    return kn.pipe == 3 || (kn.pipe == 2 && S >= 512);
-}
+// workspace of the LDS-staged path: [BH][Tpad] AttnStat + one int per block
+static int64_t attn_ws_need(int BH, int T, int Tpad) { return (int64_t)BH * Tpad * (int64_t)sizeof(AttnStat) + (int64_t)BH * ((T + 127) / 128) * 4; }
 
+// for the shape alone (an upper bound: an asymmetric q without a table runs the register-fed kernel and needs none)
 extern "C" int64_t qd_attn_ws_bytes(int BH, int T, int S, int d) {
-    if (BH <= 0 || T <= 0 || S <= 0 || d <= 0) return 0;
-    const int Tpad = (T + 31) / 32 * 32, Spad = (S + 31) / 32 * 32, dpad = (d + 31) / 32 * 32;
-    if (!attn_lds_shape(T, S, d, Spad, dpad)) return 0;
-    return (int64_t)BH * Tpad * (int64_t)sizeof(AttnStat) + (int64_t)BH * ((T + 127) / 128) * 4;
+    if (BH <= 0 || T <= 0 || S <= 0 || d <= 0 || attn_policy(d, S, false, false, attn_knobs()).family != F_LDS) return 0;
+    return attn_ws_need(BH, T, (T + 31) / 32 * 32);
 }
-
-// the table pays where the LDS-staged kernel runs (thousands of keys); the register-fed kernel on short key axes (the 77
-// context tokens: 3 tiles per sweep, 3 waves per SIMD) keeps the constant-operand MFMAs — it has no registers to spare
-// for 16 seeds per tile and nothing to gain from them; pipe modes 0 / 3 (tests, A/B runs) take a table on every key axis
-extern "C" int qd_attn_uses_keyterm(int d, int S, int q_asym) {
-    const AttnKnobs& k = attn_knobs();
-    return (q_asym != 0 && attn_lean_shape(d) && k.ktab != 0 && (k.pipe != 2 || S >= 512)) ? 1 : 0;
-}
+extern "C" int qd_attn_uses_keyterm(int d, int S, int q_asym) { return attn_policy(d, S, q_asym != 0, true, attn_knobs()).term == 2 ? 1 : 0; }
 
 extern "C" int qd_attn_keyterm(const int8_t* k, int BH, int Spad, int dpad, const float* prm, int32_t* kterm, void* stream) {
     QD_REQUIRE(k && prm && kterm, "qd_attn_keyterm: null pointer");
@@ -1362,11 +1334,37 @@ extern "C" int qd_attn_keyterm(const int8_t* k, int BH, int Spad, int dpad, cons
     return 0;
 }
 
-extern "C" int qd_attn_i8_qp(const int8_t* q, const int8_t* k, const int8_t* vt, const int32_t* qsum, const int32_t* kterm,
-                             const int32_t* vsum, int BH, int H, int T, int S, int d, int Tpad, int Spad, int dpad,
-                             const float* prm, int wbits, int wmin, int wmax, int q_asym, float* out, int64_t ldo,
-                             int8_t* out8, int64_t ldo8, const float* oq_params, int oq_min, int oq_max, int oq_off,
-                             void* ws, int64_t ws_bytes, void* stream, int q_heads) {
+template <int FAMILY, int DT, int TERM, bool P16>
+struct Form { static constexpr FormId id{FAMILY, DT, TERM, P16}; };
+// THE list of instantiations: f(Form<...>{}) for the one `id` names; false if the library has none such.
+//   attn_kernel DT 1 2 3 4 5 8 x ASYM; attn_lean_kernel DT 1 2 3 x KT 0 1 2; LDS-staged DT 1 2 x KT 0 2; each for 8- and 16-bit codes
+template <int FAMILY, class F, int... DT, int... TERM>
+bool visit_family(const FormId& id, F f, std::integer_sequence<int, DT...>, std::integer_sequence<int, TERM...>) {
+    auto one = [&](auto t) { return decltype(t)::id == id && (f(t), true); };
+    auto terms = [&](auto dt) { return ((one(Form<FAMILY, decltype(dt)::value, TERM, false>{}) || one(Form<FAMILY, decltype(dt)::value, TERM, true>{})) || ...); };
+    return (terms(std::integral_constant<int, DT>{}) || ...);
+}
+template <class F>
+bool visit_form(const FormId& id, F f) {
+    using std::integer_sequence;
+    return visit_family<F_DENSE>(id, f, integer_sequence<int, 1, 2, 3, 4, 5, 8>{}, integer_sequence<int, 0, 1>{}) ||
+           visit_family<F_LEAN>(id, f, integer_sequence<int, 1, 2, 3>{}, integer_sequence<int, 0, 1, 2>{}) ||
+           visit_family<F_LDS>(id, f, integer_sequence<int, 1, 2>{}, integer_sequence<int, 0, 2>{});
+}
+
+// One attention call as a plain value: plan() fills it without a HIP call, launch() issues it.
+struct AttnLaunch {
+    AttnK   k;
+    FormId  form;
+    void*   ws;            // F_LDS: the workspace and the bytes of it the three launches use; elsewhere unused, 0
+    int64_t ws_need;
+};
+
+static int plan(const int8_t* q, const int8_t* k, const int8_t* vt, const int32_t* qsum, const int32_t* kterm,
+                const int32_t* vsum, int BH, int H, int T, int S, int d, int Tpad, int Spad, int dpad,
+                const float* prm, int wbits, int wmin, int wmax, int q_asym, float* out, int64_t ldo,
+                int8_t* out8, int64_t ldo8, const float* oq_params, int oq_min, int oq_max, int oq_off,
+                void* ws, int64_t ws_bytes, int q_heads, AttnLaunch* L) {
     QD_REQUIRE(q && k && vt && vsum && prm && (out || out8), "qd_attn_i8: null pointer");
     QD_REQUIRE(!out8 || (oq_params && ldo8 >= (int64_t)H * d && oq_max - oq_off <= 127 && oq_min - oq_off >= -128),
                "qd_attn_i8: quantised output needs oq_params, ldo8 >= H*d and a grid that fits int8");
@@ -1382,43 +1380,70 @@ extern "C" int qd_attn_i8_qp(const int8_t* q, const int8_t* k, const int8_t* vt,
     QD_REQUIRE(wmax - wmin <= (wbits == 16 ? 65535 : 255), "qd_attn_i8: probability grid [%d,%d] wider than %d bits", wmin, wmax, wbits);
     QD_REQUIRE(qd_aligned(q, 16) && qd_aligned(k, 16) && qd_aligned(vt, 16) && qd_aligned(kterm, 16), "qd_attn_i8: operands must be 16-byte aligned");
     (void)qsum;                                  // per-query constants cancel in the softmax: never needed
-    const bool asym = q_asym != 0;
     const AttnKnobs& kn = attn_knobs();
-    AttnK a{q, k, vt, qsum, kterm, vsum, prm, out, (long)ldo, BH, H, T, S, d, Tpad, Spad, dpad, (float)wmin, (float)wmax, wmin,
-            q_heads, out8, (long)ldo8, oq_params, (float)oq_min, (float)oq_max, oq_off, kn.xcd != 0 ? 1 : 0, (T + 127) / 128};
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const bool p16 = wbits == 16;
-    // lean variant: needs a padding row of V^T (d not a multiple of 32) and |scores| < 2^22 (d < 64)
-    // pipe: 2 = LDS-staged kernel wherever it pays (default), 0 = attn_lean_kernel everywhere (A/B runs and the equality
-    // test), 3 = LDS-staged kernel on every eligible shape
-    if (attn_lean_shape(d)) {
-        const int kt = !asym ? 0 : (kterm && qd_attn_uses_keyterm(d, S, q_asym)) ? 2 : 1;     // per-key zero-point term: none / constant-operand MFMAs / table
-        // the LDS-staged two-kernel path (qd_attn_ws_bytes says which shapes): without a table for an asymmetric q (kt == 1: the
-        // constant-operand MFMAs, A/B runs with ktab = 0) the register-fed kernel runs instead
-        if (kt != 1 && attn_lds_shape(T, S, d, Spad, dpad)) {
-            const int64_t need = qd_attn_ws_bytes(BH, T, S, d);
-            QD_REQUIRE(ws && ws_bytes >= need && qd_aligned(ws, 16), "qd_attn_i8: this shape needs %ld bytes of 16-byte aligned workspace (qd_attn_ws_bytes), got %ld",
-                       (long)need, (long)ws_bytes);
-            if (dpad == 32) launch_lds<1>(a, p16, kt, ws, st);
-            else launch_lds<2>(a, p16, kt, ws, st);
-        } else if (dpad == 32) launch_lean<1>(a, p16, kt, st);
-        else if (dpad == 64) launch_lean<2>(a, p16, kt, st);
-        else launch_lean<3>(a, p16, kt, st);
-        QD_LAUNCH_CHECK("qd_attn_i8");
-        return 0;
-    }
-    switch (dpad / 32) {
-        case 1: launch_dt<1>(a, p16, asym, st); break;
-        case 2: launch_dt<2>(a, p16, asym, st); break;
-        case 3: launch_dt<3>(a, p16, asym, st); break;
-        case 4: launch_dt<4>(a, p16, asym, st); break;
-        case 5: launch_dt<5>(a, p16, asym, st); break;
-        case 8: launch_dt<8>(a, p16, asym, st); break;
-        default:
-            qd_set_error("qd_attn_i8: head dim pad %d unsupported (32,64,96,128,160,256)", dpad);
-            return 1;
-    }
+    L->k = AttnK{q, k, vt, qsum, kterm, vsum, prm, out, (long)ldo, BH, H, T, S, d, Tpad, Spad, dpad, (float)wmin, (float)wmax, wmin,
+                 q_heads, out8, (long)ldo8, oq_params, (float)oq_min, (float)oq_max, oq_off, kn.xcd != 0 ? 1 : 0, (T + 127) / 128};
+    FormId& f = L->form = attn_policy(d, S, q_asym != 0, kterm != nullptr, kn);
+    f.p16 = wbits == 16;
+    // (the rule speaks for exact pads: a caller's wider ones count, and keep the LDS-staged kernel off what its ring and its row of ones do not take)
+    f.dt = dpad / 32;
+    if (f.family == F_LDS && (dpad > 64 || Spad > QD_ONES_ROW)) f.family = F_LEAN;
+    L->ws = ws;
+    L->ws_need = f.family == F_LDS ? attn_ws_need(BH, T, Tpad) : 0;
+    QD_REQUIRE(f.family != F_LDS || (ws && ws_bytes >= L->ws_need && qd_aligned(ws, 16)),
+               "qd_attn_i8: this shape needs %ld bytes of 16-byte aligned workspace (qd_attn_ws_bytes), got %ld", (long)L->ws_need, (long)ws_bytes);
+    const bool built = visit_form(f, [](auto) {});
+    QD_REQUIRE(built || f.family != F_DENSE, "qd_attn_i8: head dim pad %d unsupported (32,64,96,128,160,256)", dpad);
+    QD_REQUIRE(built, "qd_attn_i8: head dim %d on pad %d has no lean kernel (pads 32, 64, 96)", d, dpad);
+    return 0;
+}
+
+// The only place that launches attn_kernel / attn_lean_kernel / attn_stats_kernel / attn_pv_kernel: the instantiation the plan names.
+// F_LDS: statistics, then the two P.V launches (every block runs in exactly one of them).
+static int launch(const AttnLaunch& L, hipStream_t st) {
+    const AttnK& k = L.k;
+    const dim3 grid((unsigned)(k.gx * k.BH)), block(256);
+    const bool done = visit_form(L.form, [&](auto t) {
+        constexpr FormId I = decltype(t)::id;
+        if constexpr (I.family == F_DENSE) hipLaunchKernelGGL((attn_kernel<I.dt, I.p16, I.term != 0>), grid, block, 0, st, k);
+        else if constexpr (I.family == F_LEAN) hipLaunchKernelGGL((attn_lean_kernel<I.dt, I.p16, I.term>), grid, block, 0, st, k);
+        else {
+            AttnStat* stat = reinterpret_cast<AttnStat*>(L.ws);
+            int* flag = reinterpret_cast<int*>(stat + (long)k.BH * k.Tpad);
+            hipLaunchKernelGGL((attn_stats_kernel<I.dt, I.term>), grid, block, 0, st, k, stat, flag, I.p16 ? 1 : 0);
+            hipLaunchKernelGGL((attn_pv_kernel<I.dt, I.p16, I.term, false>), grid, block, 0, st, k, (const AttnStat*)stat, (const int*)flag);
+            hipLaunchKernelGGL((attn_pv_kernel<I.dt, I.p16, I.term, true>), grid, block, 0, st, k, (const AttnStat*)stat, (const int*)flag);
+        }
+    });
+    QD_REQUIRE(done, "qd_attn_i8: the launch plan names no built kernel (family %d, DT %d, term %d, %d-bit codes)", L.form.family, L.form.dt, L.form.term, L.form.p16 ? 16 : 8);
+    return 0;
+}
+
+extern "C" int qd_attn_i8_qp(const int8_t* q, const int8_t* k, const int8_t* vt, const int32_t* qsum, const int32_t* kterm,
+                             const int32_t* vsum, int BH, int H, int T, int S, int d, int Tpad, int Spad, int dpad,
+                             const float* prm, int wbits, int wmin, int wmax, int q_asym, float* out, int64_t ldo,
+                             int8_t* out8, int64_t ldo8, const float* oq_params, int oq_min, int oq_max, int oq_off,
+                             void* ws, int64_t ws_bytes, void* stream, int q_heads) {
+    AttnLaunch L;
+    if (const int rc = plan(q, k, vt, qsum, kterm, vsum, BH, H, T, S, d, Tpad, Spad, dpad, prm, wbits, wmin, wmax, q_asym, out, ldo,
+                            out8, ldo8, oq_params, oq_min, oq_max, oq_off, ws, ws_bytes, q_heads, &L)) return rc;
+    if (const int rc = launch(L, reinterpret_cast<hipStream_t>(stream))) return rc;
     QD_LAUNCH_CHECK("qd_attn_i8");
+    return 0;
+}
+
+// The launch form qd_attn_i8_qp would take now (the same arguments, the stream aside): its plan.  form4 = {family 0 attn_kernel /
+// 1 lean / 2 LDS-staged, DT, term mode (ASYM for family 0), launches}.
+extern "C" int qd_attn_i8_form(const int8_t* q, const int8_t* k, const int8_t* vt, const int32_t* qsum, const int32_t* kterm,
+                               const int32_t* vsum, int BH, int H, int T, int S, int d, int Tpad, int Spad, int dpad,
+                               const float* prm, int wbits, int wmin, int wmax, int q_asym, float* out, int64_t ldo,
+                               int8_t* out8, int64_t ldo8, const float* oq_params, int oq_min, int oq_max, int oq_off,
+                               void* ws, int64_t ws_bytes, int32_t* form4, int q_heads) {
+    QD_REQUIRE(form4 != nullptr, "qd_attn_i8_form: null form4");
+    AttnLaunch L;
+    if (const int rc = plan(q, k, vt, qsum, kterm, vsum, BH, H, T, S, d, Tpad, Spad, dpad, prm, wbits, wmin, wmax, q_asym, out, ldo,
+                            out8, ldo8, oq_params, oq_min, oq_max, oq_off, ws, ws_bytes, q_heads, &L)) return rc;
+    form4[0] = L.form.family; form4[1] = L.form.dt; form4[2] = L.form.term; form4[3] = L.form.family == F_LDS ? 3 : 1;
     return 0;
 }
 

@@ -65,7 +65,7 @@ EXPORTS = ["qd_abi_version", "qd_last_error", "qd_device_ok", "qd_box_probe", "q
            "qd_pack_weights_t8",
            "qd_conv2d_i8", "qd_conv_config", "qd_conv2d_i8_group", "qd_conv2d_i8_splitk_ws_bytes", "qd_conv2d_i8_form",
            "qd_conv2d_i8_acc", "qd_groupnorm_ws_bytes", "qd_groupnorm_silu_quant", "qd_groupnorm_mod_silu_quant", "qd_layernorm_quant",
-           "qd_geglu_quant", "qd_quantize_heads", "qd_attn_i8", "qd_attn_i8_qp", "qd_attn_keyterm", "qd_attn_uses_keyterm", "qd_attn_config", "qd_attn_ws_bytes", "qd_bmm_qk_i8", "qd_bmm_pv_i8", "qd_temb_mlp", "qd_temb_mlp_wq_h16",
+           "qd_geglu_quant", "qd_quantize_heads", "qd_attn_i8", "qd_attn_i8_qp", "qd_attn_i8_form", "qd_attn_keyterm", "qd_attn_uses_keyterm", "qd_attn_config", "qd_attn_ws_bytes", "qd_bmm_qk_i8", "qd_bmm_pv_i8", "qd_temb_mlp", "qd_temb_mlp_wq_h16",
            "qd_fakequant_blocks", "qd_fakequant_fwd", "qd_fakequant_bwd",
            "qd_adaround_blocks", "qd_adaround_fwd", "qd_adaround_bwd",
            "qd_conv2d_bf16", "qd_pack_weights_bf16_bytes", "qd_pack_weights_bf16", "qd_groupnorm_silu_bf16",
@@ -117,6 +117,8 @@ def load():
                                i64, vp, i64, vp, i32, i32, i32, vp, i64, vp]
     if hasattr(lib, "qd_attn_i8_qp"):            # (an A/B library of an earlier revision, QDIFF_HIP_LIB, has none: calling it is an error there)
         lib.qd_attn_i8_qp.argtypes = lib.qd_attn_i8.argtypes + [i32]
+    if hasattr(lib, "qd_attn_i8_form"):          # (likewise; the stream's slot holds form4)
+        lib.qd_attn_i8_form.argtypes = lib.qd_attn_i8.argtypes + [i32]
     lib.qd_attn_keyterm.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     lib.qd_attn_uses_keyterm.argtypes = [i32, i32, i32]
     lib.qd_attn_config.argtypes = [i32, i32, i32, i32]
@@ -702,6 +704,25 @@ def attn_i8(q, k, vt, vsum, BH, H, T, S, d, Tpad, Spad, dpad, prm, wbits, wmin, 
         _check(load().qd_attn_i8(*args), "qd_attn_i8")
     else:
         _check(load().qd_attn_i8_qp(*args, int(q_heads)), "qd_attn_i8_qp")
+
+
+def attn_i8_form(q, k, vt, vsum, BH, H, T, S, d, Tpad, Spad, dpad, prm, wbits, wmin, wmax, q_asym, out, ldo,
+                 out8=None, oq_params=None, oq_grid=None, kterm=None, q_heads=None):
+    """(kernel family 0 attn_kernel / 1 lean / 2 LDS-staged, DT, per-key term mode — q_asym for family 0 —, launches) of the launch
+    attn_i8 would make for these arguments now (qd_attn_i8_form: the launcher's own checks and kernel choice with the launch
+    withheld; nothing runs on the device).  The table and the workspace attn_i8 would supply are stood in for by an aligned
+    address that is never followed."""
+    g = oq_grid
+    stand_in = 16
+    kt = _ptr(kterm) if kterm is not None else (stand_in if attn_uses_keyterm(d, S, q_asym) else None)
+    need = int(load().qd_attn_ws_bytes(int(BH), int(T), int(S), int(d)))
+    form = (ctypes.c_int32 * 4)()
+    _check(load().qd_attn_i8_form(_ptr(q), _ptr(k), _ptr(vt), None, kt, _ptr(vsum), BH, H, T, S, d, Tpad, Spad,
+                                  dpad, _ptr(prm), wbits, wmin, wmax, 1 if q_asym else 0, _ptr(out), ldo,
+                                  _ptr(out8), out8.stride(0) if out8 is not None else 0, _ptr(oq_params),
+                                  g.qmin if g else 0, g.qmax if g else 0, g.off if g else 0,
+                                  stand_in if need else None, need, form, BH if q_heads is None else int(q_heads)), "qd_attn_i8_form")
+    return tuple(form)
 
 
 def bmm_qk_i8(q8, k8, BH, T, S, d, Tpad, Spad, dpad, prm, out):

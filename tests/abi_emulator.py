@@ -289,8 +289,23 @@ def quantize_heads(x, B, T, H, d, strides, prescale, qparams, grid, transpose, o
             rsum.copy_(buf.sum(1).to(torch.int32))
 
 
+def attn_i8_form(d, S, q_asym, have_kterm, pipe=2, ktab=1, lean=1):
+    """qd_attn_i8_form, written down from the table of DESIGN.md 4.4 row by row: (family 0 attn_kernel / 1 lean / 2 LDS-staged,
+    DT, per-key term mode — q_asym for family 0 —, launches)."""
+    dpad, Spad = -(-d // 32) * 32, -(-S // 32) * 32
+    lean_dim = lean != 0 and d % 32 != 0 and (d < 64 or (d < 96 and lean == 3))
+    if not lean_dim:                                                                      # row 1
+        return (0, dpad // 32, 1 if q_asym else 0, 1)
+    table_wanted = bool(q_asym) and ktab != 0 and (pipe != 2 or S >= 512)
+    term = 0 if not q_asym else 2 if table_wanted and have_kterm else 1
+    lds_keys = (pipe == 3 or (pipe == 2 and S >= 512)) and dpad <= 64 and Spad <= 16384
+    if lds_keys and term != 1:                                                            # row 2
+        return (2, dpad // 32, term, 3)
+    return (1, dpad // 32, term, 1)                                                       # row 3
+
+
 def attn_uses_keyterm(d, S, q_asym):
-    return bool(q_asym) and d < 64 and d % 32 != 0 and S >= 512
+    return attn_i8_form(d, S, q_asym, True)[2] == 2
 
 
 def attn_keyterm(k, BH, Spad, dpad, prm, kterm=None):

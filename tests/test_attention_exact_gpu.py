@@ -46,19 +46,22 @@ def test_case_list_is_complete():
 
 
 def forms_of(d, asym):
-    """(family, pipe_mode, ktab, lean) of every launch form that takes head dim d."""
+    """(family, pipe_mode, ktab, lean, form4) of every launch form that takes head dim d; form4 = what qd_attn_i8_form must answer
+    under those knobs: (0 attn_kernel / 1 lean / 2 LDS-staged, DT, per-key term mode — q_asym for attn_kernel —, launches)."""
+    DT, kt = (d + 31) // 32, 2 if asym else 0
+    dense = (0, DT, 1 if asym else 0, 1)
     if d % 32 and d < 96:
         L = 3 if d >= 64 else 1
-        out = [("lean_kt2" if asym else "lean_kt0", 0, 1, L)]
+        out = [("lean_kt2" if asym else "lean_kt0", 0, 1, L, (1, DT, kt, 1))]
         if asym:
-            out.append(("lean_kt1", 0, 0, L))
+            out.append(("lean_kt1", 0, 0, L, (1, DT, 1, 1)))
         if d < 64:
-            out.append(("lds_kt2" if asym else "lds_kt0", 3, 1, L))
+            out.append(("lds_kt2" if asym else "lds_kt0", 3, 1, L, (2, DT, kt, 3)))
             if asym:
-                out.append(("lean_kt1_pipe3", 3, 0, L))             # no table: the LDS path hands over to the register-fed kernel
-        out.append(("attn_kernel", 2, 1, 0))
+                out.append(("lean_kt1_pipe3", 3, 0, L, (1, DT, 1, 1)))             # no table: the LDS path hands over to the register-fed kernel
+        out.append(("attn_kernel", 2, 1, 0, dense))
         return out
-    return [("attn_kernel", 2, 1, 1)]
+    return [("attn_kernel", 2, 1, 1, dense)]
 
 
 def _vt_pad_columns(S):
@@ -105,14 +108,18 @@ def test_attention_exact_rows(cuda, name, record_property):
         v8[:, d:, :] = rnd(B * H, dp - d, Sp)
         vsum[:, d:] = 123456789
     outs = {}
+    rows = torch.empty((B * T, C), dtype=torch.float32, device=cuda)        # the query's output argument: never written
     try:
-        for fam, pipe, ktab, lean in forms_of(d, ap.asym):
+        for fam, pipe, ktab, lean, form in forms_of(d, ap.asym):
             hip.attn_config(pipe_mode=pipe, ktab=ktab, lean=lean)
+            # the kernel this output will be labelled with is the kernel the launcher takes for the call below
+            assert hip.attn_i8_form(q8, k8, v8, vsum, B * H, H, T, S, d, Tp, Sp, dp, ap.prm, ap.wbits, ap.wmin, ap.wmax, ap.asym,
+                                    rows, rows.stride(0)) == form, (name, fam)
             o = engine.attention_codes(ap, q8, k8, v8, vsum, B, T, S, H, d)
             torch.cuda.synchronize()
             outs[fam] = o.clone()
         # the float entry (its own operand buffers, zero pads and producer calls) on the first form
-        fam, pipe, ktab, lean = forms_of(d, ap.asym)[0]
+        fam, pipe, ktab, lean, _ = forms_of(d, ap.asym)[0]
         hip.attn_config(pipe_mode=pipe, ktab=ktab, lean=lean)
         outs["float_entry"] = engine.attention(ap, c.q.to(cuda), c.k.to(cuda), c.v.to(cuda), B, T, S, H, d,
                                                (T * C, C, d, 1), (S * C, C, d, 1), (S * C, C, d, 1)).clone()

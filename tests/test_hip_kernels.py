@@ -813,7 +813,8 @@ def test_attention_lds_equals_lean(cuda, case):
     for which, (t, L, buf) in enumerate(((q, T, q8), (k, S, k8), (v, S, v8))):
         engine.heads_from_float(ap, which, t.to(cuda), B, L, H, d, (L * C, C, d, 1), buf, vsum)
     from qdiff import hip
-    outs = {}
+    outs, forms = {}, {}
+    rows = torch.empty((B * T, C), dtype=torch.float32, device=cuda)        # the form query's output argument: never written
     try:
         # pipe 0: attn_lean_kernel (register-fed, one kernel), 3: the LDS-staged path on every eligible shape — three launches
         # since round 6: statistics, lo-only P.V, hi + lo P.V (every block runs in exactly one of the two); ktab 1: per-key
@@ -822,11 +823,19 @@ def test_attention_lds_equals_lean(cuda, case):
         for mode in (0, 3):
             for ktab in (1, 0):
                 hip.attn_config(pipe_mode=mode, ktab=ktab, lean=3 if d >= 64 else 1)
+                forms[(mode, ktab)] = hip.attn_i8_form(q8, k8, v8, vsum, B * H, H, T, S, d, Tp, Sp, dp, ap.prm, ap.wbits, ap.wmin, ap.wmax,
+                                                       ap.asym, rows, rows.stride(0))
                 o = engine.attention_codes(ap, q8, k8, v8, vsum, B, T, S, H, d)
                 torch.cuda.synchronize()
                 outs[(mode, ktab)] = o.clone()
     finally:
         hip.attn_config(pipe_mode=2, ktab=1, lean=1)
+    # the settings are the kernels the comment above names, by the launcher's own answer (qd_attn_i8_form): both families where the
+    # shape is LDS-eligible, and the register-fed kernel with constant-operand MFMAs for an asymmetric q without a table
+    if d % 32 and d < 64 and Sp <= 16384:
+        assert len({f[0] for f in forms.values()}) >= 2, forms
+    if ap.asym:
+        assert forms[(3, 0)][0] == 1 and forms[(3, 0)][2] == 1, forms
     ref = outs[(0, 1)]
     assert torch.isfinite(ref).all() and ref.abs().max() > 0
     for key, o in outs.items():

@@ -140,16 +140,25 @@ def test_random_attention_shapes(cuda, draw):
     vsum = torch.zeros((B * H, dp), dtype=torch.int32, device=cuda)
     for which, (t, L, buf) in enumerate(((q, T, q8), (k, S, k8), (v, S, v8))):
         engine.heads_from_float(ap, which, t.to(cuda), B, L, H, d, (L * C, C, d, 1), buf, vsum)
-    outs = {}
+    outs, forms = {}, {}
+    rows = torch.empty((B * T, C), dtype=torch.float32, device=cuda)        # the form query's output argument: never written
     try:
         for mode in (0, 3):
             for ktab in (1, 0):
                 hip.attn_config(pipe_mode=mode, ktab=ktab, lean=3 if d >= 64 else 1)
+                forms[(mode, ktab)] = hip.attn_i8_form(q8, k8, v8, vsum, B * H, H, T, S, d, Tp, Sp, dp, ap.prm, ap.wbits, ap.wmin, ap.wmax,
+                                                       ap.asym, rows, rows.stride(0))
                 o = engine.attention_codes(ap, q8, k8, v8, vsum, B, T, S, H, d)
                 torch.cuda.synchronize()
                 outs[(mode, ktab)] = o.clone()
     finally:
         hip.attn_config(pipe_mode=2, ktab=1, lean=1)
+    # by the launcher's own answer (qd_attn_i8_form): the four settings are both kernel families where the shape is LDS-eligible,
+    # and the register-fed kernel with constant-operand MFMAs for an asymmetric q without a table
+    if d % 32 and d < 64 and Sp <= 16384:
+        assert len({f[0] for f in forms.values()}) >= 2, forms
+    if ap.asym:
+        assert forms[(3, 0)][0] == 1 and forms[(3, 0)][2] == 1, forms
     ref = outs[(0, 1)]
     assert torch.isfinite(ref).all() and ref.abs().max() > 0
     for key, o in outs.items():

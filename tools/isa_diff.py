@@ -46,15 +46,18 @@ def functions(asm):
                 cur = None
             continue
         cur.append(s)
+    # local labels are numbered per function: basic blocks, and the anchors of relaxed long branches (.Lpost_getpcN, a counter
+    # that runs over the whole file and so follows the order in which the kernels were instantiated)
+    local = r"\.LBB\w+|\.Lpost_getpc\d+"
     norm = {}
     for k, lines in fns.items():
         labels, out = {}, []
         for s in lines:
-            m = re.match(r"^(\.LBB\w+):$", s)
+            m = re.match(rf"^({local}):$", s)
             if m:
                 labels.setdefault(m.group(1), f"L{len(labels)}")
         for s in lines:
-            out.append(re.sub(r"\.LBB\w+", lambda mm: labels.get(mm.group(0), mm.group(0)), s))
+            out.append(re.sub(local, lambda mm: labels.get(mm.group(0), mm.group(0)), s))
         norm[k] = out
     return norm
 
