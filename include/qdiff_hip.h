@@ -454,6 +454,11 @@ int qd_attn_i8_form(const int8_t* q, const int8_t* k, const int8_t* vt,
  *                   u = clamp(rint(w/dw)+zpw, wmin, wmax) and contracted with v:
  *                   out[bh][c][t] = dw*dv * sum_s (u-zpw)(v'-zv')   ("bct": row stride ldo, head stride obstride);
  *                   vt / vsum = transpose=1 output of qd_quantize_heads; prm[3..6] = {dw, zpw, dw*dv, zv'}.
+ *                   wbits 8 or 16, wmax - wmin < 2^wbits.  Bounds on S (refused with a message, nothing is launched): the
+ *                   kernel sums a query's S codes and accumulates the lo / hi code bytes against v' in int32, so
+ *                   S * (wmax - wmin) < 2^31 (S <= 32768 for a full 16-bit grid) and S < 131072 (S products of at most
+ *                   128 * 128 = 2^14 per byte accumulator); everything after the accumulators is 64-bit.
+ *     Both refuse a head-dim pad outside {32, 64, 96, 128, 160, 256}.
  * ------------------------------------------------------------------------------------------ */
 int qd_bmm_qk_i8(const int8_t* q, const int8_t* k, int BH, int T, int S, int d, int Tpad, int Spad, int dpad,
                  const float* prm, float* out, int64_t ldo, int64_t bstride, void* stream);

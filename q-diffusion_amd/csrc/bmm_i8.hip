@@ -204,6 +204,10 @@ extern "C" int qd_bmm_pv_i8(const float* w, int64_t ldw, int64_t wbstride, const
     QD_REQUIRE(wbits == 8 || wbits == 16, "qd_bmm_pv_i8: probability bits must be 8 or 16 (got %d)", wbits);
     QD_REQUIRE(wmax - wmin <= (wbits == 16 ? 65535 : 255), "qd_bmm_pv_i8: probability grid [%d,%d] wider than %d bits", wmin, wmax, wbits);
     QD_REQUIRE(ldw >= S && ldo >= T, "qd_bmm_pv_i8: ldw >= S and ldo >= T required");
+    // int32 sums over the S keys of a query: the code sum (S terms of at most wmax - wmin) and the lo / hi byte accumulators of
+    // the MFMAs (S products of at most 128 * 128 = 2^14 in magnitude, so S < 2^31 / 2^14 = 131072)
+    QD_REQUIRE((int64_t)S * ((int64_t)wmax - wmin) < (1LL << 31), "qd_bmm_pv_i8: S=%d keys of probability codes spanning %lld overflow the int32 code sum (S * (wmax - wmin) must stay below 2^31)", S, (long long)wmax - wmin);
+    QD_REQUIRE(S < 131072, "qd_bmm_pv_i8: S=%d overflows the int32 byte accumulators (S * 2^14 must stay below 2^31: S < 131072)", S);
     PvK a{w, vt, vsum, prm, out, (long)ldw, (long)wbstride, (long)ldo, (long)obstride, T, S, d, Spad, dpad, (float)wmin, (float)wmax, wmin};
     dim3 grid((unsigned)((T + 127) / 128), (unsigned)BH);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

@@ -1300,6 +1300,25 @@ def attention_codes(ap, q8, k8, v8, vsum, B, T, S, H, d, out=None, out_plan=None
 # ------------------------------------------------------------------------------------------------
 # standalone attention matmuls (QuantQKMatMul / QuantSMVMatMul used on their own)
 # ------------------------------------------------------------------------------------------------
+BMM_HEAD_TILES = (1, 2, 3, 4, 5, 8)      # dpad / 32 of the bmm_qk_kernel / bmm_pv_kernel instantiations (csrc/bmm_i8.hip)
+
+
+def bmm_shape_ok(c, aq_w=None, S=None):
+    """The standalone matmul launchers take head dim c — and, for P.V, the softmax quantiser aq_w over S keys: what
+    qd_bmm_qk_i8 / qd_bmm_pv_i8 and _softmax_grid would otherwise refuse by raising (head-dim pad, 9..15-bit probabilities,
+    the int32 bounds on S of include/qdiff_hip.h).  The modules' gates keep the composition on a miss."""
+    if pad32(c) // 32 not in BMM_HEAD_TILES:
+        return False
+    if aq_w is None:
+        return True
+    if 8 < aq_w.n_bits != 16:
+        return False
+    if S is None:
+        return True
+    _, wmin, wmax = _softmax_grid(aq_w)
+    return S < 131072 and S * (wmax - wmin) < 2 ** 31
+
+
 def _softmax_grid(aq_w):
     if aq_w.n_bits not in (8, 16) and aq_w.n_bits > 8:
         raise hip.HipEngineError(f"softmax bit-width {aq_w.n_bits} unsupported (<=8 or 16)")

@@ -339,20 +339,37 @@ def attn_i8(q, k, vt, vsum, BH, H, T, S, d, Tpad, Spad, dpad, prm, wbits, wmin, 
         out[:, :H * d] = rows
 
 
+def _bmm_refuse(who, dpad, S=None, wbits=None, wmin=0, wmax=0):
+    """What qd_bmm_qk_i8 / qd_bmm_pv_i8 refuse beyond malformed arguments (include/qdiff_hip.h), with the library's error type."""
+    from qdiff import hip
+    if wbits is not None:
+        if wbits not in (8, 16):
+            raise hip.HipEngineError(f"{who}: probability bits must be 8 or 16 (got {wbits})")
+        if wmax - wmin > 2 ** wbits - 1:
+            raise hip.HipEngineError(f"{who}: probability grid [{wmin},{wmax}] wider than {wbits} bits")
+        if S * (wmax - wmin) >= 2 ** 31 or S >= 131072:
+            raise hip.HipEngineError(f"{who}: S={S} overflows the int32 sums over the keys")
+    if dpad // 32 not in (1, 2, 3, 4, 5, 8):
+        raise hip.HipEngineError(f"{who}: head dim pad {dpad} unsupported (32,64,96,128,160,256)")
+
+
 def bmm_qk_i8(q8, k8, BH, T, S, d, Tpad, Spad, dpad, prm, out):
+    _bmm_refuse("qd_bmm_qk_i8", dpad)
     cs, zq, zk = float(prm[0]), int(prm[1]), int(prm[2])
     qi = q8.to(torch.int64)[:, :T, :d] - zq
     ki = k8.to(torch.int64)[:, :S, :d] - zk
-    out.copy_(torch.einsum("bid,bjd->bij", qi.double(), ki.double()).float() * cs)
+    # + 0.0: the integer 0 converts to +0.0 (a sum of fp64 products -0.0 would keep its sign)
+    out.copy_((torch.einsum("bid,bjd->bij", qi.double(), ki.double()) + 0.0).float() * cs)
 
 
 def bmm_pv_i8(w, v8t, vsum, BH, T, S, d, Spad, dpad, prm, wbits, wmin, wmax, out):
+    _bmm_refuse("qd_bmm_pv_i8", dpad, S, wbits, wmin, wmax)
     dw, zpw, osc, zv = (float(prm[i]) for i in range(3, 7))
     inv = torch.empty(Spad, dtype=torch.long)
     inv[_perm_index(Spad)] = torch.arange(Spad)
     vi = v8t.to(torch.int64)[:, :, inv][:, :d, :S] - int(zv)                    # [BH, d, S]
     u = torch.clamp(torch.round(w.float() / dw) + zpw, wmin, wmax) - zpw
-    out.copy_(torch.einsum("bts,bcs->bct", u.double(), vi.double()).float() * osc)
+    out.copy_((torch.einsum("bts,bcs->bct", u.double(), vi.double()) + 0.0).float() * osc)
 
 
 def temb_mlp(x, silu, plans, offsets, out):
