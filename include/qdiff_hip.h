@@ -510,6 +510,41 @@ int qd_adaround_bwd(const float* gw, int64_t ldg, const float* w, int64_t rows, 
                     const float* greg, float* galpha, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Calibration: fused MSE range search that INITIALISES a quantiser.  Replaces the LAPQ-style loop over
+ *     80 shrink factors of UniformAffineQuantizer.init_quantization_scale with scale_method = 'mse' (reference
+ *     qdiff/quant_layer.py:138-140 channel-wise, :162-177 the search, :183-190 quantize()): per factor a quantise and an
+ *     L_2.4 score over the whole tensor, ~14 launches each.
+ *     Geometry: `rows` rows of `cols` consecutive floats, row r at x + r * ldx (ldx >= cols when rows > 1; 4-byte aligned:
+ *     a channel slice is read in place).  per_row = 1: one search per row, G = rows groups (channel-wise weights).
+ *     per_row = 0: ONE search over all rows together, G = 1 (an activation tensor; the x[:, :split] / x[:, split:] slices
+ *     of a split layer's input as B strided rows).  rows * cols < 2^31.  fp32 only.
+ *     factors: n_cand (1..80) shrink factors f_i; the host passes float32(1.0 - i * 0.01).  levels = 2^n_bits - 1 divides
+ *     the range, qmax = n_levels - 1 clamps the codes (they differ for a symmetric quantiser, as in the reference).
+ *     Per group and candidate i, operation by operation (no contraction, IEEE division), as ATen evaluates the
+ *     composition on the device — it divides a tensor by a host scalar as a product with the scalar's fp32 reciprocal:
+ *       hi = x_max * f_i;  lo = x_min * f_i;  d = (always_zero ? hi : hi - lo) * (1.0f / levels)
+ *       z  = always_zero ? 0 : rint(-lo / d)
+ *       per element:  c = clamp(rint(x / d) + z, 0, qmax);  xq = (c - z) * d;  term = |x - xq|^2.4     (fp32, powf)
+ *       score_i = mean of the terms: a lane adds at most 8 terms in fp32, everything after that in fp64 in a fixed order;
+ *                 the fp64 total is divided by the element count and rounded to fp32 once
+ *     Selection: best = 1e10f, ascending i, i taken only when score_i < best.  Nothing taken: index = -1 and
+ *     delta = zero_point = 0.  NaN as in ATen: x_min / x_max of a group holding a NaN are NaN, clamp keeps a NaN, a NaN
+ *     score is never better — so a constant row (d = 0, z = -inf) and a row of zeros (z = NaN) take nothing.
+ *     Outputs: delta, zero_point, x_min, x_max, index hold G values; scores (may be null) holds [G][n_cand].
+ *     ws: qd_mse_search_ws_bytes(rows, cols, per_row, n_cand) bytes, 16-byte aligned (0 bytes: may be null).
+ *     qd_mse_search_form: the launch form the library takes, the one rule —  per_row = 1: one launch, a block per row,
+ *     QD_MSE_FORM_WAVE (64 threads) when cols <= 512, else QD_MSE_FORM_BLOCK (256);  per_row = 0: QD_MSE_FORM_SPREAD, three
+ *     launches (min / max partials; [block][n_cand] fp64 partial sums; finalise).  -1 for an empty tensor.
+ *     No floating-point atomics: results are bit-identical from run to run.
+ * ------------------------------------------------------------------------------------------ */
+enum { QD_MSE_FORM_WAVE = 0, QD_MSE_FORM_BLOCK = 1, QD_MSE_FORM_SPREAD = 2 };
+int qd_mse_search_form(int64_t rows, int64_t cols, int per_row);
+int64_t qd_mse_search_ws_bytes(int64_t rows, int64_t cols, int per_row, int n_cand);
+int qd_mse_search(const float* x, int64_t rows, int64_t cols, int64_t ldx, int per_row, const float* factors, int n_cand,
+                  int levels, int qmax, int always_zero, float* delta, float* zero_point, float* x_min, float* x_max,
+                  int32_t* index, float* scores, void* ws, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * First-stage decoder: the convolutions of the KL-f8 / VQ-f4 `Decoder`
  *     (ldm/modules/diffusionmodules/model.py:465-572 `Decoder.forward`: conv_in, ResnetBlock :80-141, AttnBlock :144-196
  *     q/k/v/proj_out, Upsample :48-63 nearest-2x + conv, conv_out; called from ldm/models/autoencoder.py:330-333 `decode`

@@ -601,6 +601,26 @@ def adaround_device_ok(t):
     return t.is_cuda
 
 
+# Fused MSE range search: False (default) = a quantiser with scale_method 'mse' initialises through the torch
+# composition (80 shrink factors, ~14 launches each); True = UniformAffineQuantizer.init_quantization_scale hands an fp32
+# device tensor whose rows are consecutive in memory to qd_mse_search: one launch per channel-wise weight, three per
+# activation tensor.  QDIFF_FUSED_MSE_INIT=1, or engine.set_fused_mse_init().
+FUSED_MSE_INIT = _parse_flag(os.environ.get("QDIFF_FUSED_MSE_INIT"), "QDIFF_FUSED_MSE_INIT")
+
+# qd_mse_search calls (tests read it)
+MSE_INIT_SEARCHES = [0]
+
+
+def set_fused_mse_init(on):
+    """True / False (or the strings QDIFF_FUSED_MSE_INIT accepts)."""
+    _set_flag("FUSED_MSE_INIT", on, "fused MSE initialisation")
+
+
+def mse_init_device_ok(t):
+    """The fused range search runs on GPU tensors only; anything else keeps the composition."""
+    return t.is_cuda
+
+
 def wonly_device_ok(t):
     """The weights-only kernel runs on GPU tensors only; anything else keeps the library path."""
     return t.is_cuda

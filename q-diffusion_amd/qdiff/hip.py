@@ -68,6 +68,7 @@ EXPORTS = ["qd_abi_version", "qd_last_error", "qd_device_ok", "qd_box_probe", "q
            "qd_geglu_quant", "qd_quantize_heads", "qd_attn_i8", "qd_attn_i8_qp", "qd_attn_i8_form", "qd_attn_keyterm", "qd_attn_uses_keyterm", "qd_attn_config", "qd_attn_ws_bytes", "qd_bmm_qk_i8", "qd_bmm_pv_i8", "qd_temb_mlp", "qd_temb_mlp_wq_h16",
            "qd_fakequant_blocks", "qd_fakequant_fwd", "qd_fakequant_bwd",
            "qd_adaround_blocks", "qd_adaround_fwd", "qd_adaround_bwd",
+           "qd_mse_search_form", "qd_mse_search_ws_bytes", "qd_mse_search",
            "qd_conv2d_bf16", "qd_pack_weights_bf16_bytes", "qd_pack_weights_bf16", "qd_groupnorm_silu_bf16",
            "qd_pack_weights_h16", "qd_groupnorm_silu_h16", "qd_conv2d_wq_h16", "qd_rows_to_h16",
            "qd_conv2d_wq_h16_splitk_ws_bytes", "qd_wq_h16_config",
@@ -135,6 +136,10 @@ def load():
     lib.qd_adaround_blocks.argtypes = [i64, i64]
     lib.qd_adaround_fwd.argtypes = [vp, i64, i64, i64, vp, vp, vp, i32, f32, f32, f32, vp, vp, vp]
     lib.qd_adaround_bwd.argtypes = [vp, i64, vp, i64, i64, i64, vp, vp, vp, i32, f32, f32, f32, vp, vp, vp]
+    lib.qd_mse_search_form.argtypes = [i64, i64, i32]
+    lib.qd_mse_search_ws_bytes.restype = ctypes.c_int64
+    lib.qd_mse_search_ws_bytes.argtypes = [i64, i64, i32, i32]
+    lib.qd_mse_search.argtypes = [vp, i64, i64, i64, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.qd_conv2d_bf16.argtypes = [ctypes.POINTER(ConvDesc), vp]
     lib.qd_pack_weights_bf16_bytes.restype = ctypes.c_int64
     lib.qd_pack_weights_bf16_bytes.argtypes = [i32, i32, i32]
@@ -800,6 +805,49 @@ def adaround_bwd(gw, w, alpha, delta, zero_point, n_levels, gamma, zeta, reg_b=N
     from . import engine
     engine.ADAROUND_LAUNCHES[0] += 1
     return galpha
+
+
+MSE_FORM_WAVE, MSE_FORM_BLOCK, MSE_FORM_SPREAD = 0, 1, 2
+MSE_CANDIDATES = 80
+_MSE_FACTORS = {}
+
+
+def mse_search_form(rows, cols, per_row):
+    """The launch form qd_mse_search takes for this geometry (a pure host function of the library)."""
+    return int(load().qd_mse_search_form(int(rows), int(cols), 1 if per_row else 0))
+
+
+def mse_factors(device):
+    """The 80 shrink factors of the range search as the composition multiplies them in: float32(1.0 - i * 0.01)."""
+    device = torch.device(device)
+    if device not in _MSE_FACTORS:                       # one table per device: no host-to-device copy per search
+        _MSE_FACTORS[device] = torch.tensor([1.0 - (i * 0.01) for i in range(MSE_CANDIDATES)], dtype=torch.float64).to(torch.float32).to(device)
+    return _MSE_FACTORS[device]
+
+
+def mse_search(x, per_row, n_bits, n_levels, always_zero, want_scores=False):
+    """The 'mse' range search of UniformAffineQuantizer.init_quantization_scale over fp32 rows read in place (adaround_rows(x):
+    a dense tensor or a channel slice), per row or over all rows together.  Returns device tensors only and never synchronises:
+    (delta, zero_point, x_min, x_max, index, scores) with G = rows (per_row) or 1 values each, index = -1 where no candidate
+    was taken (delta = zero_point = 0 there), scores [G, 80] or None."""
+    rows, cols, ldx = adaround_rows(x)
+    if not per_row and ldx == cols:                      # dense rows searched together are one long row
+        rows, cols, ldx = 1, rows * cols, rows * cols
+    lib = load()
+    G = rows if per_row else 1
+    dev = x.device
+    out = torch.empty(4, G, dtype=torch.float32, device=dev)
+    index = torch.empty(G, dtype=torch.int32, device=dev)
+    scores = torch.empty(G, MSE_CANDIDATES, dtype=torch.float32, device=dev) if want_scores else None
+    factors = mse_factors(dev)
+    nbytes = int(lib.qd_mse_search_ws_bytes(rows, cols, 1 if per_row else 0, MSE_CANDIDATES))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev) if nbytes else None
+    _check(lib.qd_mse_search(_ptr(x, "x"), rows, cols, ldx, 1 if per_row else 0, _ptr(factors), MSE_CANDIDATES, 2 ** int(n_bits) - 1,
+                             int(n_levels) - 1, 1 if always_zero else 0, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3]),
+                             _ptr(index), _ptr(scores), _ptr(ws), _stream()), "qd_mse_search")
+    from . import engine
+    engine.MSE_INIT_SEARCHES[0] += 1
+    return out[0], out[1], out[2], out[3], index, scores
 
 
 def box_probe(device, kind, blocks, iters):

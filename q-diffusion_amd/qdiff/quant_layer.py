@@ -222,7 +222,32 @@ class UniformAffineQuantizer(nn.Module):
         shape = (-1,) + (1,) * (x.dim() - 1)
         return delta.view(shape), zero_point.view(shape)
 
-    def init_quantization_scale(self, x: torch.Tensor, channel_wise: bool = False):
+    def _init_mse_fused(self, x, channel_wise):
+        """The 'mse' range search as ONE qd_mse_search call (engine.FUSED_MSE_INIT; csrc/mse_search.hip): None
+        when the route does not apply — the knob, the method, fp32 on a device the kernel runs on, rows consecutive in memory
+        (a dense tensor, a weight[:, a:b] slice, an activation's channel slice as B rows), fewer than 2^31 elements — or when
+        the whole-tensor search took no candidate: the caller's composition then returns what it always returned."""
+        if not (engine.FUSED_MSE_INIT and self.scale_method == 'mse' and torch.is_tensor(x) and x.dtype == torch.float32
+                and engine.mse_init_device_ok(x)):
+            return None
+        xd = x.detach()
+        geo = hip.adaround_rows(xd)
+        if geo is None or geo[0] * geo[1] >= 2 ** 31:
+            return None
+        delta, zero_point, x_min, x_max, index, _ = hip.mse_search(xd, channel_wise, self.n_bits, self.n_levels, self.always_zero)
+        if channel_wise:                                   # a row where nothing was taken holds (0, 0), as the composition's
+            shape = (-1,) + (1,) * (x.dim() - 1)
+            return delta.view(shape), zero_point.view(shape)
+        if int(index) < 0:
+            return None
+        if self.leaf_param:
+            self.x_min, self.x_max = x_min.reshape(()), x_max.reshape(())
+        return delta.reshape(()), (0 if self.always_zero else zero_point.reshape(()))
+
+    def init_quantization_scale(self, x: torch.Tensor, channel_wise: bool = False, _fused: bool = True):
+        fused = self._init_mse_fused(x, channel_wise) if _fused else None
+        if fused is not None:
+            return fused
         if channel_wise:
             if 'max' in self.scale_method:
                 return self._init_max_channelwise(x)
@@ -231,8 +256,8 @@ class UniformAffineQuantizer(nn.Module):
             xc = x.clone().detach()
             delta = torch.zeros(xc.shape[0], dtype=x.dtype, device=x.device)
             zero_point = torch.zeros_like(delta)
-            for c in range(xc.shape[0]):
-                delta[c], zero_point[c] = self.init_quantization_scale(xc[c], channel_wise=False)
+            for c in range(xc.shape[0]):               # (a channel-wise tensor the fused search refused stays on the composition)
+                delta[c], zero_point[c] = self.init_quantization_scale(xc[c], channel_wise=False, _fused=False)
             shape = (-1,) + (1,) * (x.dim() - 1)
             return delta.view(shape), zero_point.view(shape)
 
