@@ -633,6 +633,15 @@ int qd_conv2d_wq_h16(const qd_conv_desc* d, int act_dtype, void* stream);
  * under the policy; 0 when the layer is launched unsplit.  Pure host function: shape fields, nseg, seg[].clen and epilogue only
  * are read, no pointer is followed, no GPU is needed. */
 int64_t qd_conv2d_wq_h16_splitk_ws_bytes(const qd_conv_desc* d);
+/* Launch-form query (additive in ABI 20; a pure host function): the launches qd_conv2d_wq_h16(d, act_dtype, stream) would make NOW,
+ * the state of qd_wq_h16_config included.  form4 = {K slices (1 = one pass), K-steps per slice (0 for one pass), epilogue form
+ * (0 fp32 rows, 1 fp16 rows, 2 GEGLU operand rows), 1 if the split-K finalise pass is the vectorised form (four columns per thread;
+ * 0 for one pass)}.  d->splitk_ws / splitk_ws_bytes decide as they do for the launch: a NULL or too small workspace gives the one
+ * pass, without an error.  The descriptor goes through the launcher's own checks and decisions with the launch withheld, so the
+ * answer cannot drift from the launcher; it returns non-zero with qd_last_error wherever qd_conv2d_wq_h16 would refuse the
+ * descriptor, with the same message.  Nothing is launched and no pointer of the descriptor is followed (null tests and alignment
+ * only).  For tests and tools; not on any launch path. */
+int qd_conv2d_wq_h16_form(const qd_conv_desc* d, int act_dtype, int32_t* form4);
 /* qd_wq_h16_config (additive in ABI 20): splitk -1 = the policy (default); 0 = never split; n >= 2 = force n slices (clamped to
  * the K-step count so that no slice is empty; QD_EPI_GEGLU_H16 still unsplit); 1 = one slice, the same as 0.  qd_conv2d_wq_h16_splitk_ws_bytes honours it.
  * For tests and measurements. */

@@ -13,8 +13,8 @@ LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(LIBDIR, "libqdiff_hip.so")
 ARCH = "gfx950"
-SOURCES = ["errors.cpp", "igemm_dma.hip", "quantize.hip", "norm_quant.hip", "attn_i8.hip", "attn_h16.hip", "bmm_i8.hip", "temb_mlp.hip", "fakequant.hip", "boxcal.hip", "adaround.hip", "mse_search.hip"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(HERE, "..", "include", "qdiff_hip.h")]
+SOURCES = ["errors.cpp", "igemm_dma.hip", "wq_h16.hip", "quantize.hip", "norm_quant.hip", "attn_i8.hip", "attn_h16.hip", "bmm_i8.hip", "temb_mlp.hip", "fakequant.hip", "boxcal.hip", "adaround.hip", "mse_search.hip"]
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "wq_codes.h"), os.path.join(HERE, "..", "include", "qdiff_hip.h")]
 # correctly-rounded fp32 division / sqrt are hipcc defaults; keep them explicit because the
 # quantisers must reproduce torch's `round(x / delta)` bit for bit.
 CFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fhip-fp32-correctly-rounded-divide-sqrt",

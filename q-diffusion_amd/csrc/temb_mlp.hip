@@ -14,6 +14,7 @@
 // order, so the results equal the generic path's bit for bit whenever the SiLU inputs do.
 // Bound: latency (the launch is ~10 us; 13 MB of weights would take 3 us at HBM speed).
 #include "common.h"
+#include "wq_codes.h"
 
 namespace {
 
@@ -146,9 +147,9 @@ __global__ __launch_bounds__(256) void temb_kernel(const float* __restrict__ x, 
 //     out[b][out_off + n] = delta[n] * sum_k r(silu?(x[b][k])) * (q[k][n] - z[n]) + bias[n]
 // r = the ONE rounding to fp16 / bf16 (nearest even, the packing functions of qd_rows_to_h16).
 // One wave = one 32-row x 32-channel tile of one layer on v_mfma_f32_32x32x16_{f16,bf16}, and it walks K exactly as
-// wq_h16_kernel (csrc/igemm_dma.hip) walks it for the same output element: 64-channel K-steps in order, in each the four MFMAs
-// (g, u) over k = g*32 + half*16 + u*8 + 0..7, the same A / B lane maps, the weight fragment q - z by the same 0x6400 | q
-// pattern and packed add, channels past K as zeros, then qd_wq_affine(acc, delta, 0, bias).  The same operand values in the same
+// wq_h16_kernel (csrc/wq_h16.hip) walks it for the same output element: 64-channel K-steps in order, in each the four MFMAs
+// (g, u) over k = g*32 + half*16 + u*8 + 0..7, the same A / B lane maps, the weight fragment q - z by the same functions
+// (wq_magic / wq_frag of wq_codes.h), channels past K as zeros, then qd_wq_affine(acc, delta, 0, bias).  The same operand values in the same
 // places of the same instructions give the same fp32 bits, so the results equal the unsplit generic path's bit for bit
 // whenever the SiLU values do — the property the int8 kernel above has towards qd_conv2d_i8 — and a model does not move when the
 // knob flips.  (An FMA or dot2 chain sums in another order: agreement to rounding only, and in a network of fp16 roundings a
@@ -164,36 +165,7 @@ struct TembWqLayer {
     int Cout, out_off;
 };
 
-typedef _Float16 tw_v2h __attribute__((ext_vector_type(2)));
 typedef float tw_v16f __attribute__((ext_vector_type(16)));
-
-// 8 codes of a unit -> the halves 1024 + q in K order (wq_magic_t4 / _t8 of csrc/igemm_dma.hip)
-template <int WB>
-__device__ __forceinline__ v4i temb_wq_magic(unsigned x, unsigned y) {
-    if constexpr (WB == 4) {                                  // one word: lo nibbles are codes 0..3, hi nibbles 4..7
-        const unsigned lo = x & 0x0F0F0F0Fu, hi = (x >> 4) & 0x0F0F0F0Fu;
-        return v4i{(int)__builtin_amdgcn_perm(0x64646464u, lo, 0x04010400u), (int)__builtin_amdgcn_perm(0x64646464u, lo, 0x04030402u),
-                   (int)__builtin_amdgcn_perm(0x64646464u, hi, 0x04010400u), (int)__builtin_amdgcn_perm(0x64646464u, hi, 0x04030402u)};
-    } else {                                                  // two words of stored bytes q - 128
-        x ^= 0x80808080u;
-        y ^= 0x80808080u;
-        return v4i{(int)__builtin_amdgcn_perm(0x64646464u, x, 0x04010400u), (int)__builtin_amdgcn_perm(0x64646464u, x, 0x04030402u),
-                   (int)__builtin_amdgcn_perm(0x64646464u, y, 0x04010400u), (int)__builtin_amdgcn_perm(0x64646464u, y, 0x04030402u)};
-    }
-}
-// halves 1024 + q -> the B fragment (q - z) in the operand type; nz = {-(1024 + z), -(1024 + z)}  (wq_frag)
-template <bool FH>
-__device__ __forceinline__ v4i temb_wq_frag(const v4i& mag, const tw_v2h nz) {
-    v4i r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int w = mag[e];                                 // (through a scalar, as wq_frag)
-        const tw_v2h d = __builtin_bit_cast(tw_v2h, w) + nz;  // v_pk_add_f16: exact integers
-        if constexpr (FH) r[e] = __builtin_bit_cast(int, d);
-        else r[e] = (int)qd_pack2bf((float)d[0], (float)d[1]);
-    }
-    return r;
-}
 
 template <int WB, bool FH>
 __global__ __launch_bounds__(128) void temb_wq_kernel(const float* __restrict__ x, long ldx, int B, int K, int silu,
@@ -214,7 +186,7 @@ __global__ __launch_bounds__(128) void temb_wq_kernel(const float* __restrict__ 
     const int ntiles = (L.Cout + 31) >> 5;
     const int z = nok ? L.z[n] : 0;
     const _Float16 hz = (_Float16)(float)(-(1024 + z));        // exact: |1024 + z| <= 2048
-    const tw_v2h nz = {hz, hz};
+    const v2h nz = {hz, hz};
     const float dl = nok ? L.delta[n] : 0.f, bias = (nok && L.bias) ? L.bias[n] : 0.f;
     tw_v16f acc;
 #pragma unroll
@@ -228,12 +200,12 @@ __global__ __launch_bounds__(128) void temb_wq_kernel(const float* __restrict__ 
             const uint8_t* bp = wsrc + ((g * 2 + fhalf) * 32 + frow) * UB;
             if constexpr (WB == 4) {
                 const uint2 raw = *reinterpret_cast<const uint2*>(bp);
-                mag[0] = temb_wq_magic<4>(raw.x, 0u);
-                mag[1] = temb_wq_magic<4>(raw.y, 0u);
+                mag[0] = wq_magic<4>(raw.x, 0u);
+                mag[1] = wq_magic<4>(raw.y, 0u);
             } else {
                 const v4i raw = *reinterpret_cast<const v4i*>(bp);
-                mag[0] = temb_wq_magic<8>((unsigned)raw.x, (unsigned)raw.y);
-                mag[1] = temb_wq_magic<8>((unsigned)raw.z, (unsigned)raw.w);
+                mag[0] = wq_magic<8>((unsigned)raw.x, (unsigned)raw.y);
+                mag[1] = wq_magic<8>((unsigned)raw.z, (unsigned)raw.w);
             }
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
@@ -249,7 +221,7 @@ __global__ __launch_bounds__(128) void temb_wq_kernel(const float* __restrict__ 
 #pragma unroll
                     for (int j = 0; j < 4; ++j) af[j] = (int)(FH ? qd_pack2h(e[2 * j], e[2 * j + 1]) : qd_pack2bf(e[2 * j], e[2 * j + 1]));
                 }
-                const v4i bf = temb_wq_frag<FH>(mag[u], nz);
+                const v4i bf = wq_frag<FH>(mag[u], nz);
                 if constexpr (FH)
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(v8h, af), __builtin_bit_cast(v8h, bf), acc, 0, 0, 0);
                 else
@@ -283,10 +255,13 @@ extern "C" int qd_temb_mlp_wq_h16(const float* x, int64_t ldx, int B, int K, int
     const auto* L = reinterpret_cast<const TembWqLayer*>(layers);
     const auto* bl = reinterpret_cast<const int2*>(blocks);
     const bool fh = act_dtype == QD_F16;
-#define QD_TEMB_WQ(WB, FH) hipLaunchKernelGGL((temb_wq_kernel<WB, FH>), dim3(n_blocks, groups), dim3(128), 0, st, x, (long)ldx, B, K, apply_silu, L, bl, out, (long)ldo)
-    if (wbits == 4) { if (fh) QD_TEMB_WQ(4, true); else QD_TEMB_WQ(4, false); }
-    else            { if (fh) QD_TEMB_WQ(8, true); else QD_TEMB_WQ(8, false); }
-#undef QD_TEMB_WQ
+    auto launch = [&](auto wb, auto fh16) {
+        hipLaunchKernelGGL((temb_wq_kernel<decltype(wb)::value, decltype(fh16)::value>), dim3(n_blocks, groups), dim3(128), 0, st, x, (long)ldx, B, K,
+                           apply_silu, L, bl, out, (long)ldo);
+    };
+    auto operands = [&](auto wb) { if (fh) launch(wb, std::true_type{}); else launch(wb, std::false_type{}); };
+    if (wbits == 4) operands(std::integral_constant<int, 4>{});
+    else operands(std::integral_constant<int, 8>{});
     QD_LAUNCH_CHECK("qd_temb_mlp_wq_h16");
     return 0;
 }

@@ -71,7 +71,7 @@ EXPORTS = ["qd_abi_version", "qd_last_error", "qd_device_ok", "qd_box_probe", "q
            "qd_mse_search_form", "qd_mse_search_ws_bytes", "qd_mse_search",
            "qd_conv2d_bf16", "qd_pack_weights_bf16_bytes", "qd_pack_weights_bf16", "qd_groupnorm_silu_bf16",
            "qd_pack_weights_h16", "qd_groupnorm_silu_h16", "qd_conv2d_wq_h16", "qd_rows_to_h16",
-           "qd_conv2d_wq_h16_splitk_ws_bytes", "qd_wq_h16_config",
+           "qd_conv2d_wq_h16_splitk_ws_bytes", "qd_wq_h16_config", "qd_conv2d_wq_h16_form",
            "qd_attn_h16", "qd_layernorm_h16", "qd_geglu_h16", "qd_groupnorm_h16", "qd_groupnorm_mod_h16", "qd_groupnorm_resample_h16"]
 
 _lib = None
@@ -153,6 +153,8 @@ def load():
     lib.qd_conv2d_wq_h16_splitk_ws_bytes.restype = ctypes.c_int64
     lib.qd_wq_h16_config.argtypes = [i32]
     lib.qd_wq_h16_config.restype = None
+    if hasattr(lib, "qd_conv2d_wq_h16_form"):    # (as qd_conv2d_i8_form above)
+        lib.qd_conv2d_wq_h16_form.argtypes = [ctypes.POINTER(ConvDesc), i32, vp]
     lib.qd_attn_h16.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32] + [i64] * 12 + [f32, i32, vp, i32, i64, vp]
     lib.qd_layernorm_h16.argtypes = [vp, i32, i64, i32, i64, f32, vp, vp, vp, i32, i64, vp]
     lib.qd_geglu_h16.argtypes = [vp, i32, i64, i32, i64, vp, i32, i64, vp]
@@ -439,8 +441,9 @@ def rows_to_h16(x, B, C, S, strides, out, ldo, c0, clen, clen_pad, oc0):
                                  _H16[out.dtype], ldo, oc0, _stream()), "qd_rows_to_h16")
 
 
-def conv2d_wq_h16(c, act_dtype):
-    """ConvCall whose x are fp16 / bf16 rows and whose segs carry scale = delta_w, zw = raw zero points (qd_conv2d_wq_h16)."""
+def _wq_launch_desc(c, act_dtype):
+    """(descriptor conv2d_wq_h16 hands to qd_conv2d_wq_h16 for ConvCall `c`, whether split-K scratch is attached): the wrapper's
+    own checks, then the scratch where the call asks for split-K and the library would use it."""
     if act_dtype not in (torch.float16, torch.bfloat16):
         raise HipEngineError("conv2d_wq_h16: activations must be float16 or bfloat16")
     if c.epilogue == EPI_GEGLU_H16:
@@ -465,10 +468,25 @@ def conv2d_wq_h16(c, act_dtype):
             ws = _splitk_scratch(c.x.device, need)
             d.splitk_ws, d.splitk_ws_bytes = ws.data_ptr(), ws.numel()
             split = True
+    return d, split
+
+
+def conv2d_wq_h16(c, act_dtype):
+    """ConvCall whose x are fp16 / bf16 rows and whose segs carry scale = delta_w, zw = raw zero points (qd_conv2d_wq_h16)."""
+    d, split = _wq_launch_desc(c, act_dtype)
     _check(load().qd_conv2d_wq_h16(ctypes.byref(d), _H16[act_dtype], _stream()), "qd_conv2d_wq_h16")
     if split:
         from . import engine
         engine.WONLY_SPLITK[0] += 1
+
+
+def conv2d_wq_h16_form(c, act_dtype):
+    """(K slices, K-steps per slice, epilogue form 0 fp32 / 1 fp16 / 2 GEGLU rows, vectorised finalise) of the launches
+    conv2d_wq_h16(c, act_dtype) would make now (qd_conv2d_wq_h16_form: the launcher's own checks and slicing decision with the
+    launch withheld; nothing runs on the device)."""
+    form = (ctypes.c_int32 * 4)()
+    _check(load().qd_conv2d_wq_h16_form(ctypes.byref(_wq_launch_desc(c, act_dtype)[0]), _H16[act_dtype], form), "qd_conv2d_wq_h16_form")
+    return tuple(form)
 
 
 def wq_h16_splitk_ws_bytes(c):

@@ -264,12 +264,37 @@ def test_resblock_with_scale_shift_norm_or_updown_keeps_todays_path(emu):
 # ---- 3. argument checks before any launch -------------------------------------------------------------------------------------
 def test_contraction_still_refuses_statistics_and_upsampling(emu):
     from qdiff import hip
-    src = open(os.path.join(ROOT, "q-diffusion_amd", "csrc", "igemm_dma.hip")).read()
-    body = src[src.index("int run_wq_h16("):]
+    src = open(os.path.join(ROOT, "q-diffusion_amd", "csrc", "wq_h16.hip")).read()
+    body = src[src.index("int plan_wq("):]
     assert "!d->gn_part && !d->upsample2x" in body and "!d->rowbias &&" not in body.split("WqD k{}")[0]
     c = hip.ConvCall(gn_part=torch.zeros(1), upsample2x=False, rowbias=None)
     with pytest.raises(hip.HipEngineError, match="linear epilogue only"):
         wonly_fused_emulator.conv2d_wq_h16(c, torch.float16)
+    # the same through the real library on fake pointers: the launcher and its form query refuse, with one message, before any
+    # launch; a row bias alone is no reason to refuse
+    import ctypes
+    from conv_form_util import FAKE
+    lib = hip.load()
+
+    def desc(**fields):
+        d = hip.ConvDesc()
+        d.x = d.w = d.out = d.rowbias = d.seg[0].scale = d.seg[0].zw = FAKE
+        d.ldx, d.ldo, d.ld_rowbias = 16, 24, 24
+        d.B, d.H, d.W, d.Ho, d.Wo, d.Cout = 2, 5, 5, 5, 5, 24
+        d.kh, d.kw, d.stride, d.pad_t, d.pad_l = 3, 3, 1, 1, 1
+        d.wbits, d.w_tiled, d.nseg, d.seg[0].clen = 4, 1, 1, 16
+        for k, v in fields.items():
+            setattr(d, k, v)
+        return d
+
+    form = (ctypes.c_int32 * 4)()
+    assert lib.qd_conv2d_wq_h16_form(ctypes.byref(desc()), hip.F16, form) == 0 and tuple(form) == (1, 0, 0, 0)
+    for bad in (dict(gn_part=FAKE), dict(upsample2x=1)):
+        d = desc(**bad)
+        assert lib.qd_conv2d_wq_h16_form(ctypes.byref(d), hip.F16, form) != 0
+        msg = lib.qd_last_error().decode()
+        assert "linear epilogue only (no GroupNorm statistics or up-sampling)" in msg
+        assert lib.qd_conv2d_wq_h16(ctypes.byref(d), hip.F16, None) != 0 and lib.qd_last_error().decode() == msg
 
 
 def test_forward_rows_rowbias_is_validated(emu):

@@ -98,7 +98,7 @@ def test_forced_count_never_leaves_an_empty_slice(lib):
 def test_abi_lists_carry_the_new_symbols(lib):
     from qdiff import hip
     header = open(os.path.join(ROOT, "include", "qdiff_hip.h")).read()
-    for name in ("qd_conv2d_wq_h16_splitk_ws_bytes", "qd_wq_h16_config"):
+    for name in ("qd_conv2d_wq_h16_splitk_ws_bytes", "qd_wq_h16_config", "qd_conv2d_wq_h16_form"):
         assert name in hip.EXPORTS and name + "(" in header and hasattr(lib, name)
     assert lib.qd_abi_version() == 20
     assert "split-K, oq_* / hd_* are ignored" not in header

@@ -337,9 +337,43 @@ def test_wrapper_validates_the_geglu_epilogue_before_any_launch(monkeypatch):
 
 
 def test_library_source_refuses_the_same_before_launching():
-    src = open(os.path.join(ROOT, "q-diffusion_amd", "csrc", "igemm_dma.hip")).read()
-    body = src[src.index("int run_wq_h16("):]
+    src = open(os.path.join(ROOT, "q-diffusion_amd", "csrc", "wq_h16.hip")).read()
+    body = src[src.index("int plan_wq("):]
     head = body.split("WqD k{}")[0]
     for needle in ("QD_EPI_GEGLU_H16", "d->out_dtype == act_dtype", "takes no residual and no rowbias", "d->Cout % 64 == 0",
                    "!d->gn_part && !d->upsample2x"):
         assert needle in head, needle
+    # the same through the real library on fake pointers: what the wrapper refuses above, the launcher and its form query refuse
+    # too, with one message, before any launch
+    import ctypes
+    from conv_form_util import FAKE
+    from qdiff import hip
+    lib = hip.load()
+
+    def desc(**fields):
+        d = hip.ConvDesc()
+        d.x = d.w = d.out = d.seg[0].scale = d.seg[0].zw = FAKE
+        d.ldx, d.ldo = 64, 64
+        d.B, d.H, d.W, d.Ho, d.Wo, d.Cout = 1, 1, 4, 1, 4, 128
+        d.kh, d.kw, d.stride = 1, 1, 1
+        d.wbits, d.w_tiled, d.nseg, d.seg[0].clen = 4, 1, 1, 64
+        d.epilogue, d.out_dtype = hip.EPI_GEGLU_H16, hip.F16
+        for k, v in fields.items():
+            setattr(d, k, v)
+        return d
+
+    form = (ctypes.c_int32 * 4)()
+    assert lib.qd_conv2d_wq_h16_form(ctypes.byref(desc()), hip.F16, form) == 0 and tuple(form) == (1, 0, 2, 0)
+    for bad, needle in ((dict(out_dtype=hip.F32), "out_dtype must be act_dtype (operand rows)"),
+                        (dict(out_dtype=hip.BF16), "out_dtype must be act_dtype (operand rows)"),
+                        (dict(ldo=56), "ldo >= F"), (dict(ldo=68), "ldo % 8 == 0"),
+                        (dict(residual=FAKE, ldr=64), "takes no residual and no rowbias"),
+                        (dict(rowbias=FAKE, ld_rowbias=128), "takes no residual and no rowbias"),
+                        (dict(Cout=80), "Cout = 2 F with F % 32 == 0 (Cout=80)"),
+                        (dict(epilogue=hip.EPI_GEGLU_I8), "linear epilogue only"),
+                        (dict(gn_part=FAKE), "linear epilogue only"), (dict(upsample2x=1), "linear epilogue only")):
+        d = desc(**bad)
+        assert lib.qd_conv2d_wq_h16_form(ctypes.byref(d), hip.F16, form) != 0, bad
+        msg = lib.qd_last_error().decode()
+        assert needle in msg, (bad, msg)
+        assert lib.qd_conv2d_wq_h16(ctypes.byref(d), hip.F16, None) != 0 and lib.qd_last_error().decode() == msg, bad

@@ -5,7 +5,9 @@
 
 Compiles csrc/<file> of <rev> and of the working tree for gfx950 with the flags of q-diffusion_amd/build.py
 (`--save-temps`-free: `-S --cuda-device-only`), splits the device assembly into functions and compares the instruction
-streams symbol by symbol (labels renumbered, comments and debug directives dropped).  Used at the end of a round whose
+streams symbol by symbol (labels renumbered, comments and debug directives dropped).  The symbols of all files given are
+pooled on each side, so a kernel that moved from one file to another is compared (name both files); a file absent from <rev>
+contributes nothing to the old side.  Used at the end of a round whose
 last commits could not be run on a GPU: a default-path kernel whose instruction stream is IDENTICAL to the last
 GPU-verified revision needs no new verification; only the listed ones do.
 Objects go to q-diffusion_amd/build/isa_diff/ (git-ignored)."""
@@ -73,29 +75,55 @@ def main():
     for rel, dst in (("q-diffusion_amd/csrc/common.h", os.path.join(old_root, "csrc", "common.h")),
                      ("include/qdiff_hip.h", os.path.join(OUT, "include", "qdiff_hip.h"))):
         open(dst, "w").write(subprocess.run(["git", "show", f"{rev}:{rel}"], cwd=ROOT, capture_output=True, text=True, check=True).stdout)
-    changed_total = 0
+    # every header of the old csrc/ beside common.h (a header absent from <rev> is simply not there for the old sources)
+    for h in os.listdir(B.CSRC):
+        if h.endswith(".h") and h != "common.h":
+            r = subprocess.run(["git", "show", f"{rev}:q-diffusion_amd/csrc/{h}"], cwd=ROOT, capture_output=True, text=True)
+            dst = os.path.join(old_root, "csrc", h)
+            if r.returncode == 0:
+                open(dst, "w").write(r.stdout)
+            elif os.path.exists(dst):                    # (left by a run against another revision)
+                os.remove(dst)
+    # symbols are pooled over all files, on each side: a kernel that moved between files is compared, not "removed" and "new"
+    a, b, home, old_home = {}, {}, {}, {}
     for f in files:
+        new_src = os.path.join(B.CSRC, f)
+        if os.path.exists(new_src):
+            fb = functions(device_asm(new_src, [B.CSRC], os.path.join(OUT, f + ".new.s")))
+            b.update(fb)
+            for k in fb:
+                home.setdefault(k, f)
+        else:
+            print(f"{f}: not in the working tree (removed file)")
         r = subprocess.run(["git", "show", f"{rev}:q-diffusion_amd/csrc/{f}"], cwd=ROOT, capture_output=True, text=True)
         if r.returncode != 0:
             print(f"{f}: not in {rev} (new file)")
             continue
         old_src = os.path.join(old_root, "csrc", f)
         open(old_src, "w").write(r.stdout)
-        a = functions(device_asm(old_src, [os.path.join(old_root, "csrc")], os.path.join(OUT, f + ".old.s")))
-        b = functions(device_asm(os.path.join(B.CSRC, f), [B.CSRC], os.path.join(OUT, f + ".new.s")))
-        same = [k for k in a if k in b and a[k] == b[k]]
-        diff = [k for k in a if k in b and a[k] != b[k]]
-        gone, new = [k for k in a if k not in b], [k for k in b if k not in a]
-        print(f"{f}: {len(same)} kernels identical, {len(diff)} changed, {len(new)} new, {len(gone)} removed")
-        for k in diff:
+        fa = functions(device_asm(old_src, [os.path.join(old_root, "csrc")], os.path.join(OUT, f + ".old.s")))
+        a.update(fa)
+        old_home.update({k: f for k in fa if k not in old_home})
+    home.update({k: f for k, f in old_home.items() if k not in home})
+    # (__hip_cuid_<hash>: the per-compilation-unit id symbol, another name for every source text)
+    a, b = ({k: v for k, v in side.items() if not k.startswith("__hip_cuid_")} for side in (a, b))
+    diff = [k for k in a if k in b and a[k] != b[k]]
+    gone, new = [k for k in a if k not in b], [k for k in b if k not in a]
+    # a symbol counts under the first file given that holds it now (a removed one: that held it); the metadata headers every
+    # file has (amdhsa.kernels, amdhsa.version) are pooled like any symbol, so they count once
+    for f in files:
+        def here(ks):
+            return [k for k in ks if home[k] == f]
+        same = here(k for k in a if k in b and a[k] == b[k])
+        print(f"{f}: {len(same)} kernels identical, {len(here(diff))} changed, {len(here(new))} new, {len(here(gone))} removed")
+        for k in here(diff):
             n = sum(1 for x, y in zip(a[k], b[k]) if x != y) + abs(len(a[k]) - len(b[k]))
             print(f"   CHANGED {k}  ({len(a[k])} -> {len(b[k])} lines, ~{n} differ)")
-        for k in new:
+        for k in here(new):
             print(f"   new     {k}")
-        for k in gone:
+        for k in here(gone):
             print(f"   removed {k}")
-        changed_total += len(diff)
-    return 1 if changed_total else 0
+    return 1 if diff else 0
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """VGPR / AGPR / spill / scratch / SGPR / LDS of every kernel of one csrc file, as hipcc compiles it for gfx950.
 
-    python tools/kernel_resources.py igemm_dma.hip [substring ...]
+    python tools/kernel_resources.py igemm_dma.hip [substring ...]      (wq_h16.hip: the weights-only contraction)
 
 Compiles the working tree's csrc/<file> to device assembly with the flags of q-diffusion_amd/build.py and reads the
 amdhsa metadata (what rocprofv3's kernel trace reports per dispatch, without a GPU).  Used to catch a template instantiation
