@@ -86,37 +86,52 @@ def _nibble_values(by):
     return ch
 
 
-def pack_weights_t4(w, alpha, delta, zp, Cout, Cin_total, taps, c0, clen, n_levels, wt, kstep0, ntiles, wsum):
-    """qd_pack_weights_t4: wt[kstep][ntile][ksub*2+half][n%32][8 B]."""
+def _tiled_codes(w, alpha, delta, zp, Cout, Cin_total, taps, c0, clen, n_levels):
+    """int64 codes [Cout, clen, taps] of the slice: floor + (alpha >= 0) or round-half-even, + zero point, clamp to the grid."""
     wv = w.reshape(Cout, Cin_total, taps)[:, c0:c0 + clen].float()
     d, z = delta.view(-1, 1, 1), zp.view(-1, 1, 1)
     q = (torch.floor(wv / d) + (alpha.reshape(Cout, clen, taps) >= 0).float()) if alpha is not None else torch.round(wv / d)
-    code = torch.clamp(q + z, 0, n_levels - 1).to(torch.int64)                 # [Cout, clen, taps]
-    pad = (clen + 15) // 16 * 16
-    nst = (pad + 63) // 64
+    return torch.clamp(q + z, 0, n_levels - 1).to(torch.int64)
+
+
+def _tiled_canvas(stored, zp, Cout, clen, taps, ntiles, nst):
+    """stored values [Cout, clen, taps] -> [ntiles * 32, taps, nst * 64] with zero pad rows and pad channels (the pads are 0
+    whatever zp is: test_pack_exact_host.py swaps in a canvas that is not)."""
     full = torch.zeros(ntiles * 32, taps, nst * 64, dtype=torch.int64)
-    full[:Cout, :, :clen] = code.permute(0, 2, 1)
-    units = full.view(ntiles, 32, taps, nst, 4, 16)                             # [jt, nn, t, cs, kh4, 16]
-    by = _nibble_bytes(units).permute(2, 3, 0, 4, 1, 5).contiguous()          # [t, cs, jt, kh4, nn, 8]
+    full[:Cout, :, :clen] = stored.permute(0, 2, 1)
+    return full
+
+
+def _tile_order(units):
+    """[jt, nn, t, cs, kh4, e] -> [t, cs, jt, kh4, nn, e]: the order of a K-step's tiles in memory."""
+    return units.permute(2, 3, 0, 4, 1, 5).contiguous()
+
+
+def _wsum_add(wsum, s):
+    if wsum is not None:                                     # NULL: no sums wanted
+        wsum += s.to(torch.int32)
+
+
+def pack_weights_t4(w, alpha, delta, zp, Cout, Cin_total, taps, c0, clen, n_levels, wt, kstep0, ntiles, wsum):
+    """qd_pack_weights_t4: wt[kstep][ntile][ksub*2+half][n%32][8 B]."""
+    code = _tiled_codes(w, alpha, delta, zp, Cout, Cin_total, taps, c0, clen, n_levels)   # [Cout, clen, taps]
+    nst = ((clen + 15) // 16 * 16 + 63) // 64
+    full = _tiled_canvas(code, zp, Cout, clen, taps, ntiles, nst)
+    by = _tile_order(_nibble_bytes(full.view(ntiles, 32, taps, nst, 4, 16) & 15))   # [t, cs, jt, kh4, nn, 8]
     view = wt.view(-1, ntiles, 4, 32, 8)
     view[kstep0:kstep0 + taps * nst] = by.view(taps * nst, ntiles, 4, 32, 8).to(torch.uint8)
-    wsum += code.sum(dim=(1, 2)).to(torch.int32)          # raw nibble sums; zero point restored via zw in the epilogue
+    _wsum_add(wsum, code.sum(dim=(1, 2)))                 # raw nibble sums; zero point restored via zw in the epilogue
 
 
 def pack_weights_t8(w, alpha, delta, zp, Cout, Cin_total, taps, c0, clen, n_levels, wt, kstep0, ntiles, wsum):
     """qd_pack_weights_t8: wt[kstep][ntile][ksub*2+half][n%32][16 B], stored byte = W - 128."""
-    wv = w.reshape(Cout, Cin_total, taps)[:, c0:c0 + clen].float()
-    d, z = delta.view(-1, 1, 1), zp.view(-1, 1, 1)
-    q = (torch.floor(wv / d) + (alpha.reshape(Cout, clen, taps) >= 0).float()) if alpha is not None else torch.round(wv / d)
-    stored = torch.clamp(q + z, 0, n_levels - 1).to(torch.int64) - 128                  # [Cout, clen, taps]
-    pad = (clen + 15) // 16 * 16
-    nst = (pad + 63) // 64
-    full = torch.zeros(ntiles * 32, taps, nst * 64, dtype=torch.int64)
-    full[:Cout, :, :clen] = stored.permute(0, 2, 1)
-    units = full.view(ntiles, 32, taps, nst, 4, 16).permute(2, 3, 0, 4, 1, 5).contiguous()   # [t, cs, jt, kh4, nn, 16]
+    stored = _tiled_codes(w, alpha, delta, zp, Cout, Cin_total, taps, c0, clen, n_levels) - 128   # [Cout, clen, taps]
+    nst = ((clen + 15) // 16 * 16 + 63) // 64
+    full = _tiled_canvas(stored, zp, Cout, clen, taps, ntiles, nst)
+    units = _tile_order(full.view(ntiles, 32, taps, nst, 4, 16))                    # [t, cs, jt, kh4, nn, 16]
     view = wt.view(torch.int8).view(-1, ntiles, 4, 32, 16)
     view[kstep0:kstep0 + taps * nst] = units.view(taps * nst, ntiles, 4, 32, 16).to(torch.int8)
-    wsum += stored.sum(dim=(1, 2)).to(torch.int32)
+    _wsum_add(wsum, stored.sum(dim=(1, 2)))
 
 
 def _unpack_rows(c, seg):

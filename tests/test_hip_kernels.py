@@ -132,9 +132,7 @@ def test_pack_weights_codes_bit_exact(cuda, n_bits, adaround):
     taps = kh * kh
     ldk = 64
     for mode in ([8, 0] if n_bits > 4 else [4, 8]):
-        if mode == 0:
-            continue  # direct mode needs zp in [0,128]; covered through engine.pack_module_weights
-        wq = torch.zeros(Cout * taps * ldk // (2 if mode == 4 else 1), dtype=torch.uint8, device=cuda)
+        wq =torch.zeros(Cout * taps * ldk // (2 if mode == 4 else 1), dtype=torch.uint8, device=cuda)
         wsum = torch.zeros(Cout, dtype=torch.int32, device=cuda)
         codes = torch.zeros((Cout, Cin, taps), dtype=torch.int32, device=cuda)
         hip.pack_weights(w.to(cuda), q.alpha.to(cuda) if adaround else None, q.delta.reshape(-1).to(cuda),
@@ -148,6 +146,16 @@ def test_pack_weights_codes_bit_exact(cuda, n_bits, adaround):
             assert torch.equal(got, want - 128)
             assert (rows[:, :, Cin:48] == 0).all()
             assert torch.equal(wsum.cpu().long(), (want - 128).sum(dim=(1, 2, 3)))
+        elif mode == 0:
+            # direct mode: the stored byte is the low byte of W - zw (an s8 wherever W - zw fits one: every zero point of the
+            # 6-bit grid here, zw = 128 alone on the full 8-bit grid); the sum is that of W - zw itself
+            direct = want - zp.view(-1, 1, 1, 1)
+            rows = wq.cpu().view(Cout, taps, ldk).long()
+            got = rows[:, :, :Cin].permute(0, 2, 1).reshape(Cout, Cin, kh, kh)
+            assert torch.equal(got, direct & 0xff)
+            assert n_bits == 8 or torch.equal(wq.cpu().view(torch.int8).view(Cout, taps, ldk).long()[:, :, :Cin].permute(0, 2, 1).reshape(want.shape), direct)
+            assert (rows[:, :, Cin:48] == 0).all()
+            assert torch.equal(wsum.cpu().long(), direct.sum(dim=(1, 2, 3)))
         else:
             raw = wq.cpu().view(Cout, taps, ldk // 2).long()
             lo, hi = raw & 15, raw >> 4
