@@ -193,7 +193,11 @@ int qd_conv2d_i8(const qd_conv_desc* d, void* stream);
 /* qd_conv_config (ABI v20): kgroups 1 (default; initial value QD_KGROUPS) = a launch with at most one output tile per CU and at least
  * eight K-steps runs 512-thread blocks whose two groups of four waves contract alternate K-steps and add their int32
  * accumulators in LDS before the (unchanged) epilogue — two waves per SIMD where the four-wave block leaves one; 0 = always the
- * four-wave block; -1 = leave unchanged.  The integers, and therefore the bytes written, are the same either way. */
+ * four-wave block; -1 = leave unchanged.  The integers, and therefore the bytes written, are the same either way.
+ * The argument is a bit field: bit 0 is the K-group choice above; bit 1 (value 2, so 2 or 3; for tests) sends every block of the
+ * linear epilogues (fp32 / fp16 / bf16 rows, int32 accumulators, split-K partials) through the generic body that otherwise only
+ * blocks with a ragged edge take, instead of the full-tile body — again the same bytes.  Every call with a non-negative argument
+ * sets both bits, so qd_conv_config(0) and qd_conv_config(1) also restore the default epilogue choice. */
 void qd_conv_config(int kgroups);
 
 /* Grouped launch (ABI v20): n = 1..3 descriptors of ONE problem shape with head-layout epilogues (QD_EPI_HEADS_I8 / _T_I8) — the

@@ -78,6 +78,7 @@ struct ConvD {
     int    res_f16;           // O_HROWS: the fp residual is fp16 (else fp32)
     int    res_period;        // O_F32 / O_F16 rows, > 0: output row m adds residual row m % res_period (0: row m)
     int    ups;               // x is the HALF-resolution map [B][H/2][W/2][ldx]; the convolution runs on its nearest-2x up-sampling
+    int    full_ok;           // linear epilogues: blocks without an edge may take the full-tile body (its 32-bit byte offsets fit; not switched off)
 };
 
 // O_PART: split-K partial.  The block contracts K-steps [y*it_per, (y+1)*it_per) only and stores
@@ -134,6 +135,11 @@ __device__ __forceinline__ constexpr int crow(int r) { return (r & 3) + 8 * (r >
 // [k-half][lane-half][n % 32][16 B] order), so the DMA loader, the im2col gather, the ring and the barriers are untouched;
 // accumulators are fp32, there is no zero-point algebra (no row sums, no per-channel integer constants) and out-of-image
 // taps read zeros.  All sizes the loader sees (ldx, c0, clen) are BYTES.
+// Compile-time choices of the full-tile body of the linear epilogues: LD = the one row operand added in phase 2 (0: none, 1: row
+// bias, 2: residual), GN = GroupNorm partials wanted, [JB, JE) = the column tiles of this wave's K-group.
+template <int LD_, bool GN_, int JB_, int JE_>
+struct FullTag { static constexpr int LD = LD_, JB = JB_, JE = JE_; static constexpr bool GN = GN_; };
+
 #ifndef QD_MT1_OCC
 #define QD_MT1_OCC 2      // waves per SIMD the 128-row tiles are compiled for (3 fits without spills; A/B knob of build.py)
 #endif
@@ -1210,9 +1216,170 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
         }
         }
     };
+    // The full-tile body of single(): chosen ONCE per block (wave-uniform) where every row of the block exists, every column of it
+    // lies inside Cout, `vec` holds and the launcher found every lane offset below to fit 32 bits (p.full_ok).  What single() asks per
+    // element is a compile-time tag here — LD: no row operand / the row bias / the residual (periodic or not: the lane's rows are
+    // worked out once per block); GN: statistics wanted — so the body is straight-line code without exec masking: per 32 x 32 tile
+    // four 16-byte loads of the row operand, sixteen ds_write_b32, four ds_read_b128, four 16-byte stores.  Addresses are a uniform
+    // 64-bit base plus a 32-bit lane offset that does not depend on the column tile.  The row operand of tile t + 1 is requested
+    // before tile t's row-major pass, so its round trip hides behind a tile of work instead of standing in front of every tile.
+    // Tiles run in single()'s order (column tile outer, row tile inner) and every float operation is single()'s: same bytes,
+    // same statistics.  A descriptor with BOTH a row bias and a residual (no layer of the three UNets has one) takes single().
     bool lines16 = false;
     if constexpr (H16_OUT && !BF) lines16 = p.vec == 2;
-    if (lines16) {
+    auto full = [&](auto tg) __attribute__((always_inline)) {
+        using TG = decltype(tg);
+        constexpr int LD = TG::LD, JB = TG::JB, JE = TG::JE;
+        constexpr bool GN = TG::GN;
+        constexpr int NTL = (JE - JB) * MT;
+        constexpr bool RAW16 = LD == 1 || OUT == O_F32;            // the row operand is fp32 (16 bytes per lane), else 16-bit (8 bytes)
+        using Raw = std::conditional_t<RAW16, v4f, uint2>;
+        constexpr unsigned OSZ = (INT_OUT || OUT == O_F32) ? 4 : 2, LSZ = RAW16 ? 4 : 2;      // bytes per element: output, row operand
+        // all offsets in BYTES: a uniform 64-bit base, and 32-bit parts (uniform tile step + lane) the launcher has bounded
+        const unsigned ldo_u = INT_OUT ? (unsigned)p.Cout : (unsigned)p.ldo;
+        char* const ob = (INT_OUT ? reinterpret_cast<char*>(oi) : reinterpret_cast<char*>(p.out)) + ((long)(m0 + wrow0) * ldo_u + wcol0) * OSZ;
+        const unsigned olane = ((unsigned)rr0 * ldo_u + c4) * OSZ, ostep = 8u * ldo_u * OSZ;     // row stride multiplied once
+        // lane offsets of the row operand per (row tile, pass), from column wcol0 of the operand's first row; they do not depend on
+        // the column tile, so the periodic residual's row and the row bias's sample are looked up once per block
+        unsigned lofs[LD ? MT : 1][4];
+        const char* lbase = nullptr;
+        if constexpr (LD == 1) {
+            lbase = reinterpret_cast<const char*>(p.rowbias + wcol0);
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int ps = 0; ps < 4; ++ps) lofs[i][ps] = ((unsigned)sRowB[wrow0 + i * 32 + ps * 8 + rr0] * (unsigned)p.ldrb + c4) * LSZ;
+        } else if constexpr (LD == 2) {
+            lbase = reinterpret_cast<const char*>(p.residual) + (long)wcol0 * LSZ;
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int ps = 0; ps < 4; ++ps) lofs[i][ps] = ((unsigned)res_row((long)m0 + wrow0 + i * 32 + ps * 8 + rr0) * (unsigned)p.ldr + c4) * LSZ;
+        }
+        auto request = [&](const int t, Raw (&b)[4]) __attribute__((always_inline)) {
+            const int j = JB + t / MT, i = t % MT;
+#pragma unroll
+            for (int ps = 0; ps < 4; ++ps) b[ps] = *reinterpret_cast<const Raw*>(lbase + (lofs[i][ps] + (unsigned)j * (32u * LSZ)));   // (one 32-bit sum: a scalar base + a lane offset)
+        };
+        Raw buf[2][4];
+        float gs[4], gq[4];
+#pragma unroll
+        for (int t = 0; t < NTL; ++t) {
+            const int j = JB + t / MT, i = t % MT;
+            const int cl = wn * WCOLS + j * 32 + frow;
+            const float sc = sScale[cl];
+            const int zw_n = sZw[cl];
+            const int zc2 = sZc[cl] - zw_n * kz;
+            const float bias_n = sBias[cl];
+            const int rbase = wrow0 + i * 32;
+            int as[16];
+            if constexpr (!BF) row_terms(rbase, as);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {             // phase 1: single()'s, element for element
+                const int rl = crow(r) + 4 * fhalf;
+                if constexpr (INT_OUT) {
+                    const int v = OUT == O_PART ? (int)acc[i][j][r] - __mul24(zw_n, as[r])
+                                                : (int)acc[i][j][r] - zc2 - __mul24(zw_n, as[r]);
+                    tb[rl * 32 + frow] = (unsigned)v;
+                } else if constexpr (BF) {
+                    tb[rl * 32 + frow] = __float_as_uint((float)acc[i][j][r] + bias_n);
+                } else {
+                    const int I = acc[i][j][r] - zc2 - __mul24(zw_n, as[r]);
+                    float v;
+                    if (SPLIT) v = __builtin_fmaf((float)I, sc, facc[SPLIT ? i : 0][SPLIT ? j : 0][r]) + bias_n;
+                    else v = __builtin_fmaf((float)I, sc, bias_n);
+                    tb[rl * 32 + frow] = __float_as_uint(v);
+                }
+            }
+            if (GN && i == 0) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { gs[e] = 0.f; gq[e] = 0.f; }
+            }
+            // The next tile's row operand is requested here: its round trip runs behind this tile's row-major pass and the next
+            // tile's phase 1, and its 16 registers are those of the accumulator tile that phase 1 has just parked.  Tile 0 waits
+            // for its own request, and tile 1's goes out after tile 0's pass (below): with one tile parked there is one buffer
+            // (two at once put the 128 x 128 tile above 128 VGPRs: three waves per SIMD where it has four).
+            if constexpr (LD != 0) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (t == 0) request(0, buf[0]);
+                if (t > 0 && t + 1 < NTL) request(t + 1, buf[(t + 1) & 1]);
+                __builtin_amdgcn_sched_barrier(0);     // the requests stay ahead of the row-major pass
+            }
+#pragma unroll
+            for (int ps = 0; ps < 4; ++ps) {           // phase 2: row-major, 16 bytes (8 of a 16-bit stream) per lane, every lane stores
+                const int rl = ps * 8 + rr0;
+                char* const ot = ob;
+                const unsigned oo = (unsigned)(i * 4 + ps) * ostep + (olane + (unsigned)j * (32u * OSZ));
+                if constexpr (INT_OUT) {
+                    *reinterpret_cast<v4i*>(ot + oo) = *reinterpret_cast<const v4i*>(tb + rl * 32 + c4);
+                } else {
+                    v4f v = *reinterpret_cast<const v4f*>(tb + rl * 32 + c4);
+                    if constexpr (LD != 0) {
+                        const Raw w = buf[t & 1][ps];
+                        if constexpr (RAW16) v += w;
+                        else if constexpr (B16_OUT) v += qd_ld4bf(&w);
+                        else v += qd_ld4h(reinterpret_cast<const __half*>(&w));
+                    }
+                    if constexpr (OUT == O_F32) *reinterpret_cast<v4f*>(ot + oo) = v;
+                    else if constexpr (B16_OUT) qd_st4bf(ot + oo, v);
+                    else qd_st4h(reinterpret_cast<__half*>(ot + oo), v);
+                    if constexpr (GN) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) { gs[e] += v[e]; gq[e] = __builtin_fmaf(v[e], v[e], gq[e]); }
+                    }
+                }
+            }
+            if constexpr (LD != 0) {
+                if (t == 0 && NTL > 1) request(1, buf[1]);     // (one parked tile = one buffer: tile 1 is requested once tile 0's is consumed)
+            }
+            if (GN && i == MT - 1) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+#pragma unroll
+                    for (int sh = 8; sh < 64; sh <<= 1) {
+                        gs[e] += __shfl_xor(gs[e], sh);
+                        gq[e] += __shfl_xor(gq[e], sh);
+                    }
+                }
+                if (lane < 8) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        sGn[(wave * WCOLS + j * 32 + c4 + e) * 2] = gs[e];
+                        sGn[(wave * WCOLS + j * 32 + c4 + e) * 2 + 1] = gq[e];
+                    }
+                }
+            }
+        }
+    };
+    // (not built for fp16 rows on the 256-row tiles — that stream leaves through pair() there, and a second body costs those
+    //  instantiations registers they do not have: more spills — nor for two segments on the 128 x 128 tile, which a second body
+    //  takes from 256 to 260 VGPRs: one wave per SIMD where it has two)
+    constexpr bool FULL_BUILT = !(H16_OUT && !BF && MT == 2) && !(SPLIT && NT == 4);
+    const bool full_tile = FULL_BUILT && vec && !lines16 && p.full_ok && m0 + BM <= p.M && n0 + BN <= p.Cout && !(has_rb && has_res);
+    if (full_tile) {
+        if constexpr (FULL_BUILT) {
+        auto columns = [&](auto jb, auto je) __attribute__((always_inline)) {
+            constexpr int JB = decltype(jb)::value, JE = decltype(je)::value;
+            if constexpr (INT_OUT) {
+                full(FullTag<0, false, JB, JE>{});
+            } else if (gn) {
+                if (has_rb) full(FullTag<1, true, JB, JE>{});
+                else if (has_res) full(FullTag<2, true, JB, JE>{});
+                else full(FullTag<0, true, JB, JE>{});
+            } else {
+                if (has_rb) full(FullTag<1, false, JB, JE>{});
+                else if (has_res) full(FullTag<2, false, JB, JE>{});
+                else full(FullTag<0, false, JB, JE>{});
+            }
+        };
+        if constexpr (KS > 1) {
+            if (kg == 0) columns(std::integral_constant<int, 0>{}, std::integral_constant<int, J0>{});
+            else columns(std::integral_constant<int, J0>{}, std::integral_constant<int, NT>{});
+        } else {
+            columns(std::integral_constant<int, 0>{}, std::integral_constant<int, NT>{});
+        }
+        }
+    } else if (lines16) {
         // Pairs start at tile 0 whatever the alignment.  Where the wave's first column is an odd multiple of 32 (every other
         // block of the 160-wide tiles, wave column 1 of the 128 x 320 tile) a pair straddles two lines — two half-line
         // requests, what the 4-halves form issues everywhere.  The variant that peels tile 0 on those waves (every pair one
@@ -1422,6 +1589,11 @@ static int& kgroups_knob() {
     static int v = (getenv("QD_KGROUPS") && atoi(getenv("QD_KGROUPS")) == 0) ? 0 : 1;
     return v;
 }
+// the linear epilogues' full-tile body off: every block takes the generic (edge) body — the equality tests' second side
+static int& generic_epilogue_knob() {
+    static int v = 0;
+    return v;
+}
 
 // K loops of fewer than eight 64-byte steps stay on the four-wave block (nothing to split).  Measured with the epilogue divided
 // between the groups (profiles/r06_c7_kgroups_igemm_ab.txt, one box, us per launch at batch 16): 3 x 3 1280 -> 1280 at 16 x 16
@@ -1509,6 +1681,11 @@ int plan_block(Launch* L, TileId tile) {
     ConvD& k = L->k;
     k.nblk_m = (k.M + tile.bm() - 1) / tile.bm();
     k.nblk_n = (k.Cout + tile.bn() - 1) / tile.bn();
+    // the full-tile body addresses with 32-bit byte offsets: inside a block of the output (at most 256 rows), over the whole
+    // residual (any row of a period) and the whole row-bias table
+    const long ldo = L->out == O_PART || L->out == O_I32 ? k.Cout : k.ldo;
+    k.full_ok = !generic_epilogue_knob() && ldo > 0 && ldo < (1L << 20) && (!k.residual || (k.ldr > 0 && (long)k.M * k.ldr < (1L << 28))) &&
+                (!k.rowbias || (k.ldrb > 0 && (long)k.B * k.ldrb < (1L << 28)));
     const int ksteps = L->out == O_PART ? k.it_per : k.taps * k.seg[0].nsteps_tap;
     const bool k2 = kgroups_knob() && !L->split && k.nseg == 1 && (long)k.nblk_m * k.nblk_n * L->nsplit <= 256 && ksteps >= kgroups_min_steps();
     bool ok = false;
@@ -1878,7 +2055,7 @@ extern "C" int qd_conv2d_i8_form(const qd_conv_desc* d, int32_t* form4) {
 }
 
 extern "C" void qd_conv_config(int kgroups) {
-    if (kgroups >= 0) kgroups_knob() = kgroups ? 1 : 0;
+    if (kgroups >= 0) { kgroups_knob() = kgroups & 1; generic_epilogue_knob() = (kgroups >> 1) & 1; }
 }
 extern "C" int qd_conv2d_i8_group(const qd_conv_desc* const* descs, int n, void* stream) { return run_group(descs, n, stream); }
 extern "C" int qd_conv2d_i8(const qd_conv_desc* d, void* stream) { return run(d, nullptr, stream); }

@@ -328,8 +328,12 @@ def conv2d_i8_form(c):
     return tuple(form)
 
 
-def conv_config(kgroups=-1):
-    load().qd_conv_config(int(kgroups))
+def conv_config(kgroups=-1, generic_epilogue=False):
+    """kgroups: 1 / 0 = two K-groups where the launcher wants them / never; -1 = leave the state as it is.
+    generic_epilogue (tests; needs kgroups 0 or 1): every block of the linear epilogues takes the edge body (same bytes)."""
+    if generic_epilogue and int(kgroups) < 0:
+        raise ValueError("conv_config: generic_epilogue is set together with kgroups (0 or 1)")
+    load().qd_conv_config(int(kgroups) if int(kgroups) < 0 else (int(bool(kgroups)) | (2 if generic_epilogue else 0)))
 
 
 def conv2d_i8_group(calls):
