@@ -128,6 +128,89 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) {
 
 __device__ __forceinline__ constexpr int crow(int r) { return (r & 3) + 8 * (r >> 2); }   // C-layout row of register r (+ 4*half)
 
+// ---- fragments every epilogue body of igemm_body composes (a value two bodies must compute alike is computed here, once) ----
+// Epilogue constants of one output channel: kz * zw[n] is folded into the channel constant (zc2 = zc - zw * kz).
+struct Chan { float sc; int zw, zc2; float bias; };
+struct OutQ { QP qp; QB qb; };                    // the output quantiser of the int8 epilogues
+struct HeadCol { int h, dd; };                    // column n of a head layout: head, column inside the head
+// (functions of the descriptor, not lambdas of the body: captured by reference and called from the nested tile lambdas, head_of
+//  kept the whole descriptor in scratch memory on the 160- and 224-column head kernels, profiles/igemm_epilogue_isa.txt)
+__device__ __forceinline__ OutQ out_quant(const ConvD& p) {
+    const QP q = qd_load_qp(p.oq);
+    return OutQ{q, qd_bytes_setup(q, p.oqmin, p.oqmax, p.oqoff)};
+}
+__device__ __forceinline__ HeadCol head_of(const ConvD& p, int nn) {         // nn / hdd (exact: nn < 2^16)
+    const int h = (int)__umulhi((unsigned)nn, p.hdrcp);
+    return HeadCol{h, nn - h * p.hdd};
+}
+
+// [32 rows][64 dwords] transposition tile of TWO MFMA tiles (one 128-byte line of halves per row).  A ds_read_b128 group of 16
+// lanes covers rows (0, 1, 2, 3) x 4 chunks, so the 16-byte chunk index is XOR-ed with (row & 1): conflict-free reads, and the
+// ds_write_b32 side stays a permutation of 32 consecutive banks.  Phase 2: lane -> (row = pass*8 + lane/8, 8 columns from k8*8).
+struct Tile64 {
+    unsigned* tb;
+    int frow, fhalf, k8, rd_lo, rd_hi;
+    __device__ __forceinline__ Tile64(unsigned* t, int lane) : tb(t), frow(lane & 31), fhalf(lane >> 5), k8(lane & 7) {
+        const int sw = (lane >> 3) & 1;
+        rd_lo = ((2 * k8) ^ sw) * 4;
+        rd_hi = ((2 * k8 + 1) ^ sw) * 4;
+    }
+    __device__ __forceinline__ void put(int r, float v0, float v1) const {      // register r of the lane's column in either tile
+        const int rl = crow(r) + 4 * fhalf;
+        const int pc = frow ^ ((r & 1) << 2);     // (row & 1) == (r & 1) in the C layout
+        tb[rl * 64 + pc] = __float_as_uint(v0);
+        tb[rl * 64 + 32 + pc] = __float_as_uint(v1);
+    }
+    __device__ __forceinline__ void get(int rl, v4f& lo, v4f& hi) const {
+        lo = *reinterpret_cast<const v4f*>(tb + rl * 64 + rd_lo);
+        hi = *reinterpret_cast<const v4f*>(tb + rl * 64 + rd_hi);
+    }
+};
+
+// Four elements of a row of fp32 (O_F32) / bf16 (O_BF16) / fp16 (any other OUT) values as floats: one vector access where the row
+// is aligned and all four columns exist (vecok), else column by column inside Cout.
+template <int OUT>
+using row_elem_t = std::conditional_t<OUT == O_F32, float, std::conditional_t<OUT == O_BF16, unsigned short, __half>>;
+template <int OUT>
+__device__ __forceinline__ v4f ld4(const row_elem_t<OUT>* src, int n4, int cout, bool vecok) {
+    if (vecok) {
+        if constexpr (OUT == O_F32) return *reinterpret_cast<const v4f*>(src);
+        else if constexpr (OUT == O_BF16) return qd_ld4bf(src);
+        else return qd_ld4h(src);
+    }
+    v4f v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if constexpr (OUT == O_F32) v[e] = n4 + e < cout ? src[e] : 0.f;
+        else if constexpr (OUT == O_BF16) v[e] = n4 + e < cout ? qd_bf2f(src[e]) : 0.f;
+        else v[e] = n4 + e < cout ? __half2float(src[e]) : 0.f;
+    }
+    return v;
+}
+template <int OUT>
+__device__ __forceinline__ void st4(row_elem_t<OUT>* dst, const v4f& v, int n4, int cout, bool vecok) {
+    if (vecok) {
+        if constexpr (OUT == O_F32) *reinterpret_cast<v4f*>(dst) = v;
+        else if constexpr (OUT == O_BF16) qd_st4bf(dst, v);
+        else qd_st4h(dst, v);
+        return;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (n4 + e < cout) {
+            if constexpr (OUT == O_F32) dst[e] = v[e];
+            else if constexpr (OUT == O_BF16) dst[e] = (unsigned short)(qd_pack2bf(v[e], 0.f) & 0xffffu);
+            else dst[e] = __float2half(v[e]);
+        }
+}
+
+// GroupNorm partials of four columns: sum and sum of squares.  (explicit fma: the 4- and the 8-column forms must round alike — left
+// to the optimiser, one is packed into v_pk_mul + v_pk_add and the other contracted)
+__device__ __forceinline__ void gn_add(const v4f& v, float* gs, float* gq) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { gs[e] += v[e]; gq[e] = __builtin_fmaf(v[e], v[e], gq[e]); }
+}
+
 // WB = weight bits of the tile-ordered operand: 4 (raw nibbles, 1 KB per K-step x 32 channels) or 8 (s8 bytes W-128,
 // 2 KB); everything but the B tile size and the fragment read is shared.
 // WB = 16: the same kernel as a bf16 x bf16 -> fp32 convolution (v_mfma_f32_32x32x16_bf16).  A 64-byte K-step is 32 bf16
@@ -666,6 +749,33 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
             for (int e = 0; e < 4; ++e) as[4 * g4 + e] = t[e];
         }
     };
+    constexpr bool INT_OUT = OUT == O_PART || OUT == O_I32;
+    constexpr bool H16_OUT = OUT == O_F16, B16_OUT = OUT == O_BF16;
+    auto chan = [&](int cl) __attribute__((always_inline)) {          // cl: tile-local channel
+        const int zw = sZw[cl];
+        return Chan{sScale[cl], zw, sZc[cl] - zw * kz, sBias[cl]};
+    };
+    // the exact integer of one element; a split-K partial keeps zc for the finalise pass
+    auto restore = [](int a, const Chan& ch, int as_r) __attribute__((always_inline)) {
+        return OUT == O_PART ? a - __mul24(ch.zw, as_r) : a - ch.zc2 - __mul24(ch.zw, as_r);
+    };
+    auto seg0 = [&](int i, int j, int r) __attribute__((always_inline)) { return SPLIT ? facc[SPLIT ? i : 0][SPLIT ? j : 0][r] : 0.f; };
+    // one fma(I, scale, bias) — written out: the O_F16 pair form and the split-K finalise
+    // must produce this value bit for bit and may not depend on where the optimiser contracts
+    auto to_row = [](int I, const Chan& ch, float facc_r) __attribute__((always_inline)) {
+        return SPLIT ? __builtin_fmaf((float)I, ch.sc, facc_r) + ch.bias : __builtin_fmaf((float)I, ch.sc, ch.bias);
+    };
+    // phase 1 of a 32-column tile: dequantise in the C layout, park the tile in LDS
+    auto park = [&](int i, int j, const Chan& ch, const int (&as)[16]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int rl = crow(r) + 4 * fhalf;
+            if constexpr (INT_OUT) tb[rl * 32 + frow] = (unsigned)restore((int)acc[i][j][r], ch, as[r]);
+            else if constexpr (BF) tb[rl * 32 + frow] = __float_as_uint((float)acc[i][j][r] + ch.bias);
+            else tb[rl * 32 + frow] = __float_as_uint(to_row(restore(acc[i][j][r], ch, as[r]), ch, seg0(i, j, r)));
+        }
+    };
+    const Tile64 t64(tb, lane);
 
     if constexpr (OUT == O_GEGLU) {
         // weight rows were packed (value tile, gate tile) interleaved: tiles 2jp / 2jp+1 of this lane hold the value
@@ -675,8 +785,7 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
         constexpr int ROWB = 16 * NT;                  // output bytes per row of this wave
         constexpr int LPR = ROWB / 16;                 // lanes per row in phase 2
         constexpr int RPP = 64 / LPR;                  // rows per pass
-        const QP oqp = qd_load_qp(p.oq);
-        const QB oqb = qd_bytes_setup(oqp, p.oqmin, p.oqmax, p.oqoff);
+        const OutQ oq = out_quant(p);
         int8_t* tb8 = reinterpret_cast<int8_t*>(tb);   // [32 rows][ROWB]  (<= 4 KB for NT <= 8)
         const int Fout = p.Cout >> 1;
         const int f0 = (wcol0 >> 1);                   // first output feature of this wave
@@ -691,20 +800,16 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
 #pragma unroll
             for (int jp = 0; jp < NT / 2; ++jp) {
                 const int lv = wn * WCOLS + (2 * jp) * 32 + frow, lg = lv + 32;     // tile-local channel of value / gate
-                const float sv = sScale[lv], sgt = sScale[lg];
-                const int zwv = sZw[lv], zwg = sZw[lg];
-                const int zcv = sZc[lv] - zwv * kz, zcg = sZc[lg] - zwg * kz;       // kz folded into the channel constant (row_terms)
-                const float bv = sBias[lv], bg = sBias[lg];
+                const Chan cv = chan(lv), cg = chan(lg);
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {      // two rows per step: the float math runs packed (v_pk_*_f32)
                     const int rl0 = crow(r) + 4 * fhalf, rl1 = crow(r + 1) + 4 * fhalf;
-                    const int as0 = as[r], as1 = as[r + 1];
-                    const v2f vi = {(float)(acc[i][2 * jp][r] - zcv - __mul24(zwv, as0)), (float)(acc[i][2 * jp][r + 1] - zcv - __mul24(zwv, as1))};
-                    const v2f gi = {(float)(acc[i][2 * jp + 1][r] - zcg - __mul24(zwg, as0)), (float)(acc[i][2 * jp + 1][r + 1] - zcg - __mul24(zwg, as1))};
-                    const v2f val = qd_fma2(vi, qd_splat2(sv), qd_splat2(bv)), gate = qd_fma2(gi, qd_splat2(sgt), qd_splat2(bg));
+                    const v2f vi = {(float)restore(acc[i][2 * jp][r], cv, as[r]), (float)restore(acc[i][2 * jp][r + 1], cv, as[r + 1])};
+                    const v2f gi = {(float)restore(acc[i][2 * jp + 1][r], cg, as[r]), (float)restore(acc[i][2 * jp + 1][r + 1], cg, as[r + 1])};
+                    const v2f val = qd_fma2(vi, qd_splat2(cv.sc), qd_splat2(cv.bias)), gate = qd_fma2(gi, qd_splat2(cg.sc), qd_splat2(cg.bias));
                     const v2f y = val * (qd_splat2(0.5f) * gate * (qd_splat2(1.0f) + qd_erff2(gate * qd_splat2(0.70710678118654752440f))));
                     int b0, b1;
-                    qd_bytes2_t<FAST>(y, oqp, oqb, b0, b1);
+                    qd_bytes2_t<FAST>(y, oq.qp, oq.qb, b0, b1);
                     tb8[rl0 * ROWB + jp * 32 + frow] = (int8_t)b0;
                     tb8[rl1 * ROWB + jp * 32 + frow] = (int8_t)b1;
                 }
@@ -718,7 +823,7 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
             }
         }
         };
-        QD_FAST_DISPATCH(oqp.fast, epi);
+        QD_FAST_DISPATCH(oq.qp.fast, epi);
         return;
     }
     if constexpr (OUT == O_HROWS) {
@@ -727,8 +832,7 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
         // zero-initialised once and reused.  Phase 1 writes the fp32 projection, phase 2 adds the optional fp32 residual
         // (H = 1, d = Cout turns this epilogue into "Linear + residual -> the next Linear's int8 rows": the FF output of
         // a transformer block feeding SpatialTransformer.proj_out), quantises and stores 4 codes per lane.
-        const QP oqp = qd_load_qp(p.oq);
-        const QB oqb = qd_bytes_setup(oqp, p.oqmin, p.oqmax, p.oqoff);
+        const OutQ oq = out_quant(p);
         int8_t* o8 = reinterpret_cast<int8_t*>(p.out);
         const int bidx = m0 / p.hdT, t0 = m0 - bidx * p.hdT;
         const bool hres = p.residual != nullptr;
@@ -738,27 +842,18 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
         auto epi = [&](auto ft) __attribute__((always_inline)) {
         constexpr bool FAST = decltype(ft)::value;
         auto tile1 = [&](const int j) __attribute__((always_inline)) {
-            const int cl = wn * WCOLS + j * 32 + frow;
-            const float sc = sScale[cl];
-            const int zw_n = sZw[cl];
-            const int zc2 = sZc[cl] - zw_n * kz;
-            const float bias_n = sBias[cl];
+            const Chan ch = chan(wn * WCOLS + j * 32 + frow);
             const int n4 = wcol0 + j * 32 + c4;        // first of this lane's 4 columns in phase 2
             const bool nok = n4 < p.Cout;
             const int nn = nok ? n4 : 0;
-            const int h = (int)__umulhi((unsigned)nn, p.hdrcp), dd = nn - h * p.hdd;     // nn / hdd (exact: nn < 2^16)
-            int8_t* ob = o8 + (((long)bidx * p.hdH + h) * p.hdTpad + t0) * p.hddpad + dd;
+            const HeadCol hc = head_of(p, nn);
+            int8_t* ob = o8 + (((long)bidx * p.hdH + hc.h) * p.hdTpad + t0) * p.hddpad + hc.dd;
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 const int rbase = wrow0 + i * 32;
                 int as[16];
                 row_terms(rbase, as);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int rl = crow(r) + 4 * fhalf;
-                    const int I = acc[i][j][r] - zc2 - __mul24(zw_n, as[r]);
-                    tb[rl * 32 + frow] = __float_as_uint(__builtin_fmaf((float)I, sc, bias_n));
-                }
+                park(i, j, ch, as);
                 v4f rs[4];
                 if (hres) {
 #pragma unroll
@@ -773,7 +868,7 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
                     const int rl = ps * 8 + rr0;
                     v4f v = *reinterpret_cast<const v4f*>(tb + rl * 32 + c4);
                     if (hres) v += rs[ps];
-                    const unsigned w = qd_pack4_t<FAST>(v[0] * p.oqpre, v[1] * p.oqpre, v[2] * p.oqpre, v[3] * p.oqpre, oqp, oqb);
+                    const unsigned w = qd_pack4_t<FAST>(v[0] * p.oqpre, v[1] * p.oqpre, v[2] * p.oqpre, v[3] * p.oqpre, oq.qp, oq.qb);
                     if (nok) *reinterpret_cast<unsigned*>(ob + (long)(rbase + rl) * p.hddpad) = w;
                 }
             }
@@ -783,32 +878,21 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
         // the phase-2 instructions per code; these launches are instruction-bound (a K = 320 q projection that writes 21 MB of
         // codes took longer than the same GEMM writing 84 MB of fp32).  Same values, same codes.
         auto tile2 = [&](const int j) __attribute__((always_inline)) {
-            const int cl0 = wn * WCOLS + j * 32 + frow, cl1 = cl0 + 32;
-            const float sc0 = sScale[cl0], sc1 = sScale[cl1];
-            const int zw0 = sZw[cl0], zw1 = sZw[cl1];
-            const int zc0 = sZc[cl0] - zw0 * kz, zc1 = sZc[cl1] - zw1 * kz;
-            const float bias0 = sBias[cl0], bias1 = sBias[cl1];
-            const int k8 = lane & 7, sw = (lane >> 3) & 1;
-            const int n8 = wcol0 + j * 32 + k8 * 8;
+            const int cl0 = wn * WCOLS + j * 32 + frow;
+            const Chan ch0 = chan(cl0), ch1 = chan(cl0 + 32);
+            const int n8 = wcol0 + j * 32 + t64.k8 * 8;
             const bool nok = n8 < p.Cout;              // Cout % 8 == 0 (host)
             const int nn = nok ? n8 : 0;
-            const int h = (int)__umulhi((unsigned)nn, p.hdrcp), dd = nn - h * p.hdd;     // 8 columns never straddle a head (hdd % 8 == 0)
-            int8_t* ob = o8 + (((long)bidx * p.hdH + h) * p.hdTpad + t0) * p.hddpad + dd;
-            const int rd_lo = ((2 * k8) ^ sw) * 4, rd_hi = ((2 * k8 + 1) ^ sw) * 4;
+            const HeadCol hc = head_of(p, nn);            // 8 columns never straddle a head (hdd % 8 == 0)
+            int8_t* ob = o8 + (((long)bidx * p.hdH + hc.h) * p.hdTpad + t0) * p.hddpad + hc.dd;
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
                 const int rbase = wrow0 + i * 32;
                 int as[16];
                 row_terms(rbase, as);
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int rl = crow(r) + 4 * fhalf;
-                    const int I0 = acc[i][j][r] - zc0 - __mul24(zw0, as[r]);
-                    const int I1 = acc[i][j + 1][r] - zc1 - __mul24(zw1, as[r]);
-                    const int pc = frow ^ ((r & 1) << 2);
-                    tb[rl * 64 + pc] = __float_as_uint(__builtin_fmaf((float)I0, sc0, bias0));
-                    tb[rl * 64 + 32 + pc] = __float_as_uint(__builtin_fmaf((float)I1, sc1, bias1));
-                }
+                for (int r = 0; r < 16; ++r)
+                    t64.put(r, to_row(restore(acc[i][j][r], ch0, as[r]), ch0, seg0(i, j, r)), to_row(restore(acc[i][j + 1][r], ch1, as[r]), ch1, seg0(i, j + 1, r)));
 #pragma unroll
                 for (int pb = 0; pb < 4; pb += 2) {
                     v4f ra[2], rb2[2];
@@ -823,11 +907,11 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
 #pragma unroll
                     for (int u = 0; u < 2; ++u) {
                         const int rl = (pb + u) * 8 + rr0;
-                        v4f lo = *reinterpret_cast<const v4f*>(tb + rl * 64 + rd_lo);
-                        v4f hi = *reinterpret_cast<const v4f*>(tb + rl * 64 + rd_hi);
+                        v4f lo, hi;
+                        t64.get(rl, lo, hi);
                         if (hres) { lo += ra[u]; hi += rb2[u]; }
-                        const unsigned w0 = qd_pack4_t<FAST>(lo[0] * p.oqpre, lo[1] * p.oqpre, lo[2] * p.oqpre, lo[3] * p.oqpre, oqp, oqb);
-                        const unsigned w1 = qd_pack4_t<FAST>(hi[0] * p.oqpre, hi[1] * p.oqpre, hi[2] * p.oqpre, hi[3] * p.oqpre, oqp, oqb);
+                        const unsigned w0 = qd_pack4_t<FAST>(lo[0] * p.oqpre, lo[1] * p.oqpre, lo[2] * p.oqpre, lo[3] * p.oqpre, oq.qp, oq.qb);
+                        const unsigned w1 = qd_pack4_t<FAST>(hi[0] * p.oqpre, hi[1] * p.oqpre, hi[2] * p.oqpre, hi[3] * p.oqpre, oq.qp, oq.qb);
                         if (nok) *reinterpret_cast<uint2*>(ob + (long)(rbase + rl) * p.hddpad) = make_uint2(w0, w1);
                     }
                 }
@@ -846,12 +930,11 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
                 if (owner(j) == kg) tile1(j);
         }
         };
-        QD_FAST_DISPATCH(oqp.fast, epi);
+        QD_FAST_DISPATCH(oq.qp.fast, epi);
         return;
     }
     if constexpr (OUT == O_HTR) {
-        const QP oqp = qd_load_qp(p.oq);
-        const QB oqb = qd_bytes_setup(oqp, p.oqmin, p.oqmax, p.oqoff);
+        const OutQ oq = out_quant(p);
         int8_t* o8 = reinterpret_cast<int8_t*>(p.out);
         const int bidx = m0 / p.hdT, t0 = m0 - bidx * p.hdT;
         int* sPart = reinterpret_cast<int*>(smem);            // [4][WCOLS] column-sum partials (the ring is dead by now)
@@ -863,12 +946,9 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
             const int cl = wn * WCOLS + j * 32 + frow;
             const bool nok = n0 + cl < p.Cout;
             const int nn = nok ? n0 + cl : 0;
-            const int h = (int)__umulhi((unsigned)nn, p.hdrcp), dd = nn - h * p.hdd;     // nn / hdd (exact: nn < 2^16)
-            const float sc = sScale[cl];
-            const int zw_n = sZw[cl];
-            const int zc2 = sZc[cl] - zw_n * kz;       // kz folded into the channel constant (row_terms)
-            const float bias_n = sBias[cl];
-            int8_t* ob = o8 + (((long)bidx * p.hdH + h) * p.hddpad + dd) * p.hdTpad + t0 + fhalf * 16;
+            const HeadCol hc = head_of(p, nn);
+            const Chan ch = chan(cl);
+            int8_t* ob = o8 + (((long)bidx * p.hdH + hc.h) * p.hddpad + hc.dd) * p.hdTpad + t0 + fhalf * 16;
             int csum = 0;
 #pragma unroll
             for (int i = 0; i < MT; ++i) {
@@ -884,13 +964,12 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
 #pragma unroll
                     for (int e = 0; e < 4; e += 2) {
                         const int r = 4 * g + e;
-                        const int I0 = acc[i][j][r] - zc2 - __mul24(zw_n, as[r]);
-                        const int I1 = acc[i][j][r + 1] - zc2 - __mul24(zw_n, as[r + 1]);
-                        const v2f v = qd_fma2(v2f{(float)I0, (float)I1}, qd_splat2(sc), qd_splat2(bias_n)) * qd_splat2(p.oqpre);
+                        const v2f I = {(float)restore(acc[i][j][r], ch, as[r]), (float)restore(acc[i][j][r + 1], ch, as[r + 1])};
+                        const v2f v = qd_fma2(I, qd_splat2(ch.sc), qd_splat2(ch.bias)) * qd_splat2(p.oqpre);
                         if (e == 0) v01 = v;
                         else v23 = v;
                     }
-                    const unsigned w = qd_pack4_t<FAST>(v01.x, v01.y, v23.x, v23.y, oqp, oqb);
+                    const unsigned w = qd_pack4_t<FAST>(v01.x, v01.y, v23.x, v23.y, oq.qp, oq.qb);
                     csum = __builtin_amdgcn_sdot4((int)w, 0x01010101, csum, false);     // the same integer sum of the signed stored codes
                     pk[g] = (int)w;
                 }
@@ -902,7 +981,7 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
             if (fhalf == 0) sPart[wave * WCOLS + j * 32 + frow] = nok ? csum : 0;
         }
         };
-        QD_FAST_DISPATCH(oqp.fast, epi);
+        QD_FAST_DISPATCH(oq.qp.fast, epi);
         __syncthreads();
         const int c = threadIdx.x;
         if (c < BN && n0 + c < p.Cout) {
@@ -917,8 +996,6 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
     }
 
     // ---- linear epilogues: fp32 / fp16 rows, raw int32 (test hook), split-K partials ----------------------------------------
-    constexpr bool INT_OUT = OUT == O_PART || OUT == O_I32;
-    constexpr bool H16_OUT = OUT == O_F16, B16_OUT = OUT == O_BF16;
     const bool has_rb = p.rowbias != nullptr, has_res = p.residual != nullptr;
     const bool vec = p.vec != 0;
     // residual row of output row m: per ROW, a tile may straddle the period (the residual exists for the first res_period rows
@@ -933,51 +1010,46 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
         while (r >= rper) r -= rper;
         return (long)r;
     };
-    float*  const of = reinterpret_cast<float*>(p.out);
-    __half* const oh = reinterpret_cast<__half*>(p.out);
-    const float*  const rf = reinterpret_cast<const float*>(p.residual);
-    const __half* const rh = reinterpret_cast<const __half*>(p.residual);
+    using RowT = row_elem_t<OUT>;                  // element of the output rows, and of the residual rows with them
+    RowT* const orow = reinterpret_cast<RowT*>(p.out);
+    const RowT* const rrow = reinterpret_cast<const RowT*>(p.residual);
     int32_t* const oi = p.iout + (OUT == O_PART ? (long)blockIdx.y * p.M * p.Cout : 0L);
     // optional GroupNorm statistics of the tensor being written (consumed by qd_groupnorm_silu_quant instead of its own
     // pass over HBM): per-column partials of the lane's rows -> butterfly over the 8 lanes that share the columns ->
     // fixed-order LDS reduction over the waves of each 128-row chunk -> one {sum, sumsq} pair per (chunk, channel).
     const bool gn = (OUT == O_F32 || OUT == O_F16 || OUT == O_BF16) && p.gnpart != nullptr;   // statistics of the fp32 values (before a 16-bit store)
     float* sGn = reinterpret_cast<float*>(smem + 4 * KS * TBW);   // [4 waves][WCOLS][2], behind the transposition tiles (K-groups own disjoint columns)
+    // the lane's partials of the 4 (8: the full-line form) columns from col0 of this wave: butterfly over the lanes that share them
+    auto gn_put = [&](int col0, auto& gs, auto& gq) __attribute__((always_inline)) {
+        constexpr int N = sizeof(gs) / sizeof(float);
+#pragma unroll
+        for (int e = 0; e < N; ++e) {
+#pragma unroll
+            for (int sh = 8; sh < 64; sh <<= 1) {
+                gs[e] += __shfl_xor(gs[e], sh);
+                gq[e] += __shfl_xor(gq[e], sh);
+            }
+        }
+        if (lane < 8) {
+#pragma unroll
+            for (int e = 0; e < N; ++e) {
+                sGn[(wave * WCOLS + col0 + e) * 2] = gs[e];
+                sGn[(wave * WCOLS + col0 + e) * 2 + 1] = gq[e];
+            }
+        }
+    };
     auto single = [&](const int j) __attribute__((always_inline)) {
-        const int cl = wn * WCOLS + j * 32 + frow;
-        const float sc = sScale[cl];
-        const int zw_n = sZw[cl];
-        const int zc2 = sZc[cl] - zw_n * kz;
-        const float bias_n = sBias[cl];
+        const Chan ch = chan(wn * WCOLS + j * 32 + frow);
         const int n4 = wcol0 + j * 32 + c4;            // this lane's 4 columns in phase 2
-        const bool nok4 = n4 + 3 < p.Cout;             // all four exist (the vector path); else per element
+        const bool vecok = vec && n4 + 3 < p.Cout;     // all four exist (the vector path); else per element
         const int n4c = n4 < p.Cout ? n4 : 0;
         float gs[4] = {0.f, 0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
             const int rbase = wrow0 + i * 32;
-            // phase 1: dequantise in the C layout, park the tile in LDS
             int as[16];
             if constexpr (!BF) row_terms(rbase, as);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int rl = crow(r) + 4 * fhalf;
-                if constexpr (INT_OUT) {
-                    const int v = OUT == O_PART ? (int)acc[i][j][r] - __mul24(zw_n, as[r])
-                                                : (int)acc[i][j][r] - zc2 - __mul24(zw_n, as[r]);
-                    tb[rl * 32 + frow] = (unsigned)v;
-                } else if constexpr (BF) {
-                    tb[rl * 32 + frow] = __float_as_uint((float)acc[i][j][r] + bias_n);
-                } else {
-                    const int I = acc[i][j][r] - zc2 - __mul24(zw_n, as[r]);
-                    // one fma(I, scale, bias) — written out: the O_F16 pair form and the split-K finalise
-                    // must produce this value bit for bit and may not depend on where the optimiser contracts
-                    float v;
-                    if (SPLIT) v = __builtin_fmaf((float)I, sc, facc[SPLIT ? i : 0][SPLIT ? j : 0][r]) + bias_n;
-                    else v = __builtin_fmaf((float)I, sc, bias_n);
-                    tb[rl * 32 + frow] = __float_as_uint(v);
-                }
-            }
+            park(i, j, ch, as);
             // phase 2: row-major, 4 columns per lane
             if constexpr (INT_OUT) {
 #pragma unroll
@@ -987,7 +1059,7 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
                     const v4i v = *reinterpret_cast<const v4i*>(tb + rl * 32 + c4);
                     if (m < p.M) {
                         int32_t* dst = oi + m * p.Cout + n4;
-                        if (vec && nok4) *reinterpret_cast<v4i*>(dst) = v;
+                        if (vecok) *reinterpret_cast<v4i*>(dst) = v;
                         else {
 #pragma unroll
                             for (int e = 0; e < 4; ++e) if (n4 + e < p.Cout) dst[e] = v[e];
@@ -1002,38 +1074,8 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
                     const int rl = ps * 8 + rr0;
                     const long m = m0 + rbase + rl;
                     mrow[ps] = m < p.M ? m : m0;       // row m0 always exists: loads are clamped, only stores predicated
-                    if (has_rb) {
-                        const float* src = p.rowbias + (long)sRowB[rbase + rl] * p.ldrb + n4c;
-                        if (vec && nok4) rb[ps] = *reinterpret_cast<const v4f*>(src);
-                        else {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) rb[ps][e] = n4 + e < p.Cout ? src[e] : 0.f;
-                        }
-                    }
-                    if (has_res) {
-                        if (OUT == O_F32) {
-                            const float* src = rf + res_row(mrow[ps]) * p.ldr + n4c;
-                            if (vec && nok4) rs[ps] = *reinterpret_cast<const v4f*>(src);
-                            else {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) rs[ps][e] = n4 + e < p.Cout ? src[e] : 0.f;
-                            }
-                        } else if (B16_OUT) {
-                            const unsigned short* src = reinterpret_cast<const unsigned short*>(p.residual) + mrow[ps] * p.ldr + n4c;
-                            if (vec && nok4) rs[ps] = qd_ld4bf(src);
-                            else {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) rs[ps][e] = n4 + e < p.Cout ? qd_bf2f(src[e]) : 0.f;
-                            }
-                        } else {
-                            const __half* src = rh + res_row(mrow[ps]) * p.ldr + n4c;
-                            if (vec && nok4) rs[ps] = qd_ld4h(src);
-                            else {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) rs[ps][e] = n4 + e < p.Cout ? __half2float(src[e]) : 0.f;
-                            }
-                        }
-                    }
+                    if (has_rb) rb[ps] = ld4<O_F32>(p.rowbias + (long)sRowB[rbase + rl] * p.ldrb + n4c, n4, p.Cout, vecok);
+                    if (has_res) rs[ps] = ld4<OUT>(rrow + res_row(mrow[ps]) * p.ldr + n4c, n4, p.Cout, vecok);   // (16-bit float mode: no period, row m)
                 }
 #pragma unroll
                 for (int ps = 0; ps < 4; ++ps) {
@@ -1043,77 +1085,27 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
                     if (has_rb) v += rb[ps];
                     if (has_res) v += rs[ps];
                     if (mok) {
-                        if (OUT == O_F32) {
-                            float* dst = of + mrow[ps] * p.ldo + n4;
-                            if (vec && nok4) *reinterpret_cast<v4f*>(dst) = v;
-                            else {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) if (n4 + e < p.Cout) dst[e] = v[e];
-                            }
-                        } else if (B16_OUT) {
-                            unsigned short* dst = reinterpret_cast<unsigned short*>(p.out) + mrow[ps] * p.ldo + n4;
-                            if (vec && nok4) qd_st4bf(dst, v);
-                            else {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e)
-                                    if (n4 + e < p.Cout) dst[e] = (unsigned short)(qd_pack2bf(v[e], 0.f) & 0xffffu);
-                            }
-                        } else {
-                            __half* dst = oh + mrow[ps] * p.ldo + n4;
-                            if (vec && nok4) qd_st4h(dst, v);
-                            else {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) if (n4 + e < p.Cout) dst[e] = __float2half(v[e]);
-                            }
-                        }
-                        if (gn) {
-#pragma unroll
-                            // (explicit fma: the 4- and the 8-column forms must round alike — left to the optimiser, one is
-                            //  packed into v_pk_mul + v_pk_add and the other contracted)
-                            for (int e = 0; e < 4; ++e) { gs[e] += v[e]; gq[e] = __builtin_fmaf(v[e], v[e], gq[e]); }
-                        }
+                        st4<OUT>(orow + mrow[ps] * p.ldo + n4, v, n4, p.Cout, vecok);
+                        if (gn) gn_add(v, gs, gq);
                     }
                 }
             }
         }
-        if (gn) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                for (int sh = 8; sh < 64; sh <<= 1) {
-                    gs[e] += __shfl_xor(gs[e], sh);
-                    gq[e] += __shfl_xor(gq[e], sh);
-                }
-            }
-            if (lane < 8) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    sGn[(wave * WCOLS + j * 32 + c4 + e) * 2] = gs[e];
-                    sGn[(wave * WCOLS + j * 32 + c4 + e) * 2 + 1] = gq[e];
-                }
-            }
-        }
+        if (gn) gn_put(j * 32 + c4, gs, gq);
     };
     // fp16 stream with 8-element-aligned rows (p.vec == 2): TWO MFMA tiles per transposition, i.e. 64 columns = one 128-byte
     // line of halves per row, and 16 bytes (8 halves) per lane in phase 2 — a store instruction writes eight FULL lines
     // (1 KB) where the 4-halves-per-lane form writes eight half lines: the store path is paced per request, not per byte
     // (profiles/r03_igemm_phase_ablation.md), so the half-line form moved half the bytes of the fp32 stream at the fp32
-    // stream's speed.  LDS tile: [32 rows][64 dwords]; a ds_read_b128 group of 16 lanes covers rows (0, 1, 2, 3) x 4 chunks,
-    // so the 16-byte chunk index is XOR-ed with (row & 1): conflict-free reads, and the ds_write_b32 side stays a
-    // permutation of 32 consecutive banks.  Lane -> (row, columns) is the 4-wide form's (row = pass*8 + lane/8), so every
+    // stream's speed.  LDS tile: Tile64.  Lane -> (row, columns) is the 4-wide form's (row = pass*8 + lane/8), so every
     // column's GroupNorm partial sum runs over the same rows in the same order: the statistics are bit-identical.
     auto pair = [&](const int j) __attribute__((always_inline)) {
         if constexpr (H16_OUT && !BF) {
-        const int cl0 = wn * WCOLS + j * 32 + frow, cl1 = cl0 + 32;
-        const float sc0 = sScale[cl0], sc1 = sScale[cl1];
-        const int zw0 = sZw[cl0], zw1 = sZw[cl1];
-        const int zc0 = sZc[cl0] - zw0 * kz, zc1 = sZc[cl1] - zw1 * kz;
-        const float bias0 = sBias[cl0], bias1 = sBias[cl1];
-        const int k8 = lane & 7, sw = (lane >> 3) & 1;
-        const int n8 = wcol0 + j * 32 + k8 * 8;        // this lane's 8 columns in phase 2
+        const int cl0 = wn * WCOLS + j * 32 + frow;
+        const Chan ch0 = chan(cl0), ch1 = chan(cl0 + 32);
+        const int n8 = wcol0 + j * 32 + t64.k8 * 8;    // this lane's 8 columns in phase 2
         const bool nok8 = n8 < p.Cout;                 // Cout % 8 == 0 (host): all eight exist or none
         const int n8c = nok8 ? n8 : 0;
-        const int rd_lo = ((2 * k8) ^ sw) * 4, rd_hi = ((2 * k8 + 1) ^ sw) * 4;
         // the row bias (one row per SAMPLE: the timestep-embedding projection) joins in phase 1 when a 32-row tile cannot
         // straddle two samples: one scalar per lane per tile instead of eight floats per lane per pass; same float order
         // ((I*scale + bias) + rowbias, then + residual) as the per-row form
@@ -1139,21 +1131,10 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
             row_terms(rbase, as);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int rl = crow(r) + 4 * fhalf;
-                const int I0 = acc[i][j][r] - zc0 - __mul24(zw0, as[r]);
-                const int I1 = acc[i][j + 1][r] - zc1 - __mul24(zw1, as[r]);
-                float v0, v1;
-                if (SPLIT) {
-                    v0 = __builtin_fmaf((float)I0, sc0, facc[SPLIT ? i : 0][SPLIT ? j : 0][r]) + bias0;
-                    v1 = __builtin_fmaf((float)I1, sc1, facc[SPLIT ? i : 0][SPLIT ? j + 1 : 0][r]) + bias1;
-                } else {
-                    v0 = __builtin_fmaf((float)I0, sc0, bias0);
-                    v1 = __builtin_fmaf((float)I1, sc1, bias1);
-                }
+                float v0 = to_row(restore(acc[i][j][r], ch0, as[r]), ch0, seg0(i, j, r));
+                float v1 = to_row(restore(acc[i][j + 1][r], ch1, as[r]), ch1, seg0(i, j + 1, r));
                 if (rb_tile) { v0 += rbv0; v1 += rbv1; }
-                const int pc = frow ^ ((r & 1) << 2);  // (row & 1) == (r & 1) in the C layout
-                tb[rl * 64 + pc] = __float_as_uint(v0);
-                tb[rl * 64 + 32 + pc] = __float_as_uint(v1);
+                t64.put(r, v0, v1);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -1164,14 +1145,14 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
             for (int u = 0; u < 2; ++u) {
                 const long m = m0 + rbase + (pb + u) * 8 + rr0;
                 mrow[u] = m < p.M ? m : m0;
-                if (has_res) rs[u] = *reinterpret_cast<const v4i*>(rh + res_row(mrow[u]) * p.ldr + n8c);
+                if (has_res) rs[u] = *reinterpret_cast<const v4i*>(rrow + res_row(mrow[u]) * p.ldr + n8c);
             }
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int rl = (pb + u) * 8 + rr0;
                 const bool mok = m0 + rbase + rl < p.M;
-                v4f lo = *reinterpret_cast<const v4f*>(tb + rl * 64 + rd_lo);
-                v4f hi = *reinterpret_cast<const v4f*>(tb + rl * 64 + rd_hi);
+                v4f lo, hi;
+                t64.get(rl, lo, hi);
                 if (has_rb && !rb_tile) {
                     const float* src = p.rowbias + (long)sRowB[rbase + rl] * p.ldrb + n8c;
                     lo += *reinterpret_cast<const v4f*>(src);
@@ -1185,35 +1166,13 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
                 if (mok && nok8) {
                     const v4i pk = {(int)qd_pack2h(lo[0], lo[1]), (int)qd_pack2h(lo[2], lo[3]),
                                     (int)qd_pack2h(hi[0], hi[1]), (int)qd_pack2h(hi[2], hi[3])};
-                    *reinterpret_cast<v4i*>(oh + mrow[u] * p.ldo + n8) = pk;
-                    if (gn) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            gs[e] += lo[e]; gq[e] = __builtin_fmaf(lo[e], lo[e], gq[e]);
-                            gs[4 + e] += hi[e]; gq[4 + e] = __builtin_fmaf(hi[e], hi[e], gq[4 + e]);
-                        }
-                    }
+                    *reinterpret_cast<v4i*>(orow + mrow[u] * p.ldo + n8) = pk;
+                    if (gn) { gn_add(lo, gs, gq); gn_add(hi, gs + 4, gq + 4); }
                 }
             }
             }
         }
-        if (gn) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-#pragma unroll
-                for (int sh = 8; sh < 64; sh <<= 1) {
-                    gs[e] += __shfl_xor(gs[e], sh);
-                    gq[e] += __shfl_xor(gq[e], sh);
-                }
-            }
-            if (lane < 8) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    sGn[(wave * WCOLS + j * 32 + k8 * 8 + e) * 2] = gs[e];
-                    sGn[(wave * WCOLS + j * 32 + k8 * 8 + e) * 2 + 1] = gq[e];
-                }
-            }
-        }
+        if (gn) gn_put(j * 32 + t64.k8 * 8, gs, gq);
         }
     };
     // The full-tile body of single(): chosen ONCE per block (wave-uniform) where every row of the block exists, every column of it
@@ -1266,31 +1225,9 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
 #pragma unroll
         for (int t = 0; t < NTL; ++t) {
             const int j = JB + t / MT, i = t % MT;
-            const int cl = wn * WCOLS + j * 32 + frow;
-            const float sc = sScale[cl];
-            const int zw_n = sZw[cl];
-            const int zc2 = sZc[cl] - zw_n * kz;
-            const float bias_n = sBias[cl];
-            const int rbase = wrow0 + i * 32;
             int as[16];
-            if constexpr (!BF) row_terms(rbase, as);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {             // phase 1: single()'s, element for element
-                const int rl = crow(r) + 4 * fhalf;
-                if constexpr (INT_OUT) {
-                    const int v = OUT == O_PART ? (int)acc[i][j][r] - __mul24(zw_n, as[r])
-                                                : (int)acc[i][j][r] - zc2 - __mul24(zw_n, as[r]);
-                    tb[rl * 32 + frow] = (unsigned)v;
-                } else if constexpr (BF) {
-                    tb[rl * 32 + frow] = __float_as_uint((float)acc[i][j][r] + bias_n);
-                } else {
-                    const int I = acc[i][j][r] - zc2 - __mul24(zw_n, as[r]);
-                    float v;
-                    if (SPLIT) v = __builtin_fmaf((float)I, sc, facc[SPLIT ? i : 0][SPLIT ? j : 0][r]) + bias_n;
-                    else v = __builtin_fmaf((float)I, sc, bias_n);
-                    tb[rl * 32 + frow] = __float_as_uint(v);
-                }
-            }
+            if constexpr (!BF) row_terms(wrow0 + i * 32, as);
+            park(i, j, chan(wn * WCOLS + j * 32 + frow), as);
             if (GN && i == 0) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { gs[e] = 0.f; gq[e] = 0.f; }
@@ -1323,32 +1260,13 @@ __device__ __forceinline__ void igemm_body(const ConvD& p, unsigned char* smem) 
                     if constexpr (OUT == O_F32) *reinterpret_cast<v4f*>(ot + oo) = v;
                     else if constexpr (B16_OUT) qd_st4bf(ot + oo, v);
                     else qd_st4h(reinterpret_cast<__half*>(ot + oo), v);
-                    if constexpr (GN) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) { gs[e] += v[e]; gq[e] = __builtin_fmaf(v[e], v[e], gq[e]); }
-                    }
+                    if constexpr (GN) gn_add(v, gs, gq);
                 }
             }
             if constexpr (LD != 0) {
                 if (t == 0 && NTL > 1) request(1, buf[1]);     // (one parked tile = one buffer: tile 1 is requested once tile 0's is consumed)
             }
-            if (GN && i == MT - 1) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-#pragma unroll
-                    for (int sh = 8; sh < 64; sh <<= 1) {
-                        gs[e] += __shfl_xor(gs[e], sh);
-                        gq[e] += __shfl_xor(gq[e], sh);
-                    }
-                }
-                if (lane < 8) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        sGn[(wave * WCOLS + j * 32 + c4 + e) * 2] = gs[e];
-                        sGn[(wave * WCOLS + j * 32 + c4 + e) * 2 + 1] = gq[e];
-                    }
-                }
-            }
+            if (GN && i == MT - 1) gn_put(j * 32 + c4, gs, gq);
         }
     };
     // (not built for fp16 rows on the 256-row tiles — that stream leaves through pair() there, and a second body costs those
@@ -1760,6 +1678,27 @@ void fill_geometry(ConvD& k, const qd_conv_desc* d) {
     k.pointwise = k.taps == 1 && d->stride == 1 && d->pad_t == 0 && d->pad_l == 0 && d->H == d->Ho && d->W == d->Wo;
 }
 
+// What every mode requires of the shape; `who` names the entry point in the message.
+int check_shape(const qd_conv_desc* d, const char* who) {
+    QD_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0 && d->Cout > 0, "%s: bad shape", who);
+    QD_REQUIRE(d->kh > 0 && d->kw > 0 && d->stride > 0 && d->kh * d->kw <= 32, "%s: bad kernel/stride (at most 32 taps)", who);
+    QD_REQUIRE((long)d->B * d->Ho * d->Wo < (1L << 31), "%s: M overflows int32", who);
+    QD_REQUIRE(!d->upsample2x || (d->stride == 1 && d->kh * d->kw > 1 && d->H % 2 == 0 && d->W % 2 == 0 && d->pad_t < 8 && d->pad_l < 8),
+               "%s: upsample2x needs stride 1, more than one tap, even H and W", who);
+    return 0;
+}
+
+// GroupNorm partials from the epilogue (gn_part set): 128-row chunks that stay inside one sample
+int plan_gn(ConvD& k, const qd_conv_desc* d, const char* who) {
+    QD_REQUIRE((d->Ho * d->Wo) % 128 == 0, "%s: gn_part needs Ho*Wo %% 128 == 0%s", who,
+               d->wbits < 16 ? " (a 128-row chunk stays inside one sample)" : "");
+    k.gnpart = d->gn_part;
+    k.gn_nchunk = d->Ho * d->Wo / 128;
+    QD_REQUIRE(d->gn_ld == 0 || d->gn_ld >= d->Cout, "%s: gn_ld must be 0 or >= Cout", who);
+    k.gn_ld = d->gn_ld ? (long)d->gn_ld : (long)d->Cout;
+    return 0;
+}
+
 // Everything qd_conv2d_i8 / _acc decides about a launch — every check, the kernel descriptor, split-K or one pass, the tile, the
 // K-groups — without a HIP call.  group_member: the plan of a member of a grouped launch (128-row tiles).
 int plan(const qd_conv_desc* d, int32_t* iout, bool group_member, Launch* L) {
@@ -1767,13 +1706,9 @@ int plan(const qd_conv_desc* d, int32_t* iout, bool group_member, Launch* L) {
     QD_REQUIRE(d->x && d->w && (d->out || iout), "qd_conv2d_i8: null tensor pointer");
     QD_REQUIRE(d->w_tiled, "qd_conv2d_i8: weights must be in the tile order of qd_pack_weights_t4 / _t8 (w_tiled = 1)");
     QD_REQUIRE(d->wbits == 4 || d->wbits == 8, "qd_conv2d_i8: wbits must be 4 or 8 (got %d)", d->wbits);
-    QD_REQUIRE(!d->upsample2x || (d->stride == 1 && d->kh * d->kw > 1 && d->H % 2 == 0 && d->W % 2 == 0 && d->pad_t < 8 && d->pad_l < 8),
-               "qd_conv2d_i8: upsample2x needs stride 1, more than one tap, even H and W");
     QD_REQUIRE(d->out_dtype == QD_F32 || d->out_dtype == QD_F16, "qd_conv2d_i8: out_dtype must be f32/f16");
     QD_REQUIRE(d->nseg == 1 || d->nseg == 2, "qd_conv2d_i8: nseg must be 1 or 2");
-    QD_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0 && d->Cout > 0, "qd_conv2d_i8: bad shape");
-    QD_REQUIRE(d->kh > 0 && d->kw > 0 && d->stride > 0 && d->kh * d->kw <= 32, "qd_conv2d_i8: bad kernel/stride (at most 32 taps)");
-    QD_REQUIRE((long)d->B * d->Ho * d->Wo < (1L << 31), "qd_conv2d_i8: M overflows int32");
+    if (const int rc = check_shape(d, "qd_conv2d_i8")) return rc;
     const bool w8 = d->wbits == 8;
     QD_REQUIRE(!w8 || d->epilogue == QD_EPI_LINEAR || ((d->epilogue == QD_EPI_HEADS_I8 || d->epilogue == QD_EPI_HEADS_T_I8) && d->Cout > 64),
                "qd_conv2d_i8: int8 weights take the linear epilogue, or the head-layout epilogues on more than 64 output channels");
@@ -1840,11 +1775,7 @@ int plan(const qd_conv_desc* d, int32_t* iout, bool group_member, Launch* L) {
     }
     if (d->gn_part) {
         QD_REQUIRE(!iout && !heads && !geglu, "qd_conv2d_i8: gn_part needs the plain fp32 / fp16 epilogue");
-        QD_REQUIRE((d->Ho * d->Wo) % 128 == 0, "qd_conv2d_i8: gn_part needs Ho*Wo %% 128 == 0 (a 128-row chunk stays inside one sample)");
-        k.gnpart = d->gn_part;
-        k.gn_nchunk = d->Ho * d->Wo / 128;
-        QD_REQUIRE(d->gn_ld == 0 || d->gn_ld >= d->Cout, "qd_conv2d_i8: gn_ld must be 0 or >= Cout");
-        k.gn_ld = d->gn_ld ? (long)d->gn_ld : (long)d->Cout;
+        if (const int rc = plan_gn(k, d, "qd_conv2d_i8")) return rc;
     }
     const bool mt2_ok = !heads || d->hd_T % 256 == 0;            // a block must stay inside one sample
     if (geglu) {
@@ -1904,15 +1835,11 @@ int run_bf16(const qd_conv_desc* d, void* stream) {
     QD_REQUIRE(d != nullptr, "qd_conv2d_bf16: null descriptor");
     QD_REQUIRE(d->x && d->w && d->out, "qd_conv2d_bf16: null tensor pointer");
     QD_REQUIRE(d->w_tiled && (d->wbits == 16 || d->wbits == 17), "qd_conv2d_bf16: weights must come from qd_pack_weights_bf16 / _h16 (w_tiled = 1, wbits = 16: bf16, 17: fp16)");
-    QD_REQUIRE(!d->upsample2x || (d->stride == 1 && d->kh * d->kw > 1 && d->H % 2 == 0 && d->W % 2 == 0 && d->pad_t < 8 && d->pad_l < 8),
-               "qd_conv2d_bf16: upsample2x needs stride 1, more than one tap, even H and W");
     const bool fh = d->wbits == 17;                  // operands are IEEE halves
     QD_REQUIRE(d->out_dtype == QD_F32 || d->out_dtype == (fh ? QD_F16 : QD_BF16), "qd_conv2d_bf16: out_dtype must be f32 or the operand type");
     QD_REQUIRE(d->nseg == 1 && d->epilogue == QD_EPI_LINEAR && !d->rowbias, "qd_conv2d_bf16: one segment, linear epilogue, no row bias");
     QD_REQUIRE(d->res_period == 0, "qd_conv2d_bf16: res_period is not supported (qd_conv2d_i8 with the linear epilogue only)");
-    QD_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Ho > 0 && d->Wo > 0 && d->Cout > 0, "qd_conv2d_bf16: bad shape");
-    QD_REQUIRE(d->kh > 0 && d->kw > 0 && d->stride > 0 && d->kh * d->kw <= 32, "qd_conv2d_bf16: bad kernel/stride (at most 32 taps)");
-    QD_REQUIRE((long)d->B * d->Ho * d->Wo < (1L << 31), "qd_conv2d_bf16: M overflows int32");
+    if (const int rc = check_shape(d, "qd_conv2d_bf16")) return rc;
     QD_REQUIRE((long)d->B * d->H * d->W * d->ldx * 2 < (1L << 32), "qd_conv2d_bf16: activation exceeds the 4-GiB offset range");
     QD_REQUIRE(d->ldx % 8 == 0 && qd_aligned(d->x, 16) && qd_aligned(d->w, 16), "qd_conv2d_bf16: x/w must be 16-byte aligned, ldx %% 8 == 0");
     const qd_conv_seg& g = d->seg[0];
@@ -1928,11 +1855,7 @@ int run_bf16(const qd_conv_desc* d, void* stream) {
     k.vec = d->Cout % 4 == 0 && d->ldo % 4 == 0 && qd_aligned(d->out, 4 * esz) &&
             (!d->residual || (d->ldr % 4 == 0 && qd_aligned(d->residual, 4 * esz)));
     if (d->gn_part) {
-        QD_REQUIRE((d->Ho * d->Wo) % 128 == 0, "qd_conv2d_bf16: gn_part needs Ho*Wo %% 128 == 0");
-        k.gnpart = d->gn_part;
-        k.gn_nchunk = d->Ho * d->Wo / 128;
-        QD_REQUIRE(d->gn_ld == 0 || d->gn_ld >= d->Cout, "qd_conv2d_bf16: gn_ld must be 0 or >= Cout");
-        k.gn_ld = d->gn_ld ? (long)d->gn_ld : (long)d->Cout;
+        if (const int rc = plan_gn(k, d, "qd_conv2d_bf16")) return rc;
     }
     L.out = d->out_dtype == QD_BF16 ? O_BF16 : d->out_dtype == QD_F16 ? O_F16 : O_F32;
     L.split = false; L.nsplit = 1;

@@ -956,13 +956,17 @@ def _next_plan(cuda, Fd, delta, zp, g):
 
 
 def _fused_geglu_bytes(fused, xq, M, nxt):
-    """engine.conv_forward_geglu under both K-group settings: asserted equal, returned once."""
+    """engine.conv_forward_geglu under both K-group settings: asserted equal, returned once.  Each is one launch on the only
+    form the GEGLU epilogue is built on: 128 x 128 blocks of four waves."""
+    from conv_tall_tile_cases import launch_forms, one_form
     from qdiff import engine, hip
     outs = []
     try:
         for kg in (1, 0):
             hip.conv_config(kg)
-            outs.append(engine.conv_forward_geglu(fused, xq, M, nxt).clone())
+            with launch_forms() as forms:
+                outs.append(engine.conv_forward_geglu(fused, xq, M, nxt).clone())
+            one_form(forms, 128, 128, 256)
     finally:
         hip.conv_config(1)
     torch.cuda.synchronize()
