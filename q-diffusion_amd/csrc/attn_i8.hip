@@ -157,8 +157,121 @@ __device__ __forceinline__ void attn_write_rows(const AttnK& p, const v16i (&ol)
     else pick(std::false_type{}, std::false_type{});
 }
 
+// ---- fragments of the kernel bodies ------------------------------------------------------------------------------------------
+// attn_kernel (dense), attn_lean_body (register-fed) and attn_stats_kernel + attn_pv_kernel (LDS-staged) run the same mathematics
+// on the same wave layout.  What they share is stated once: here, and in attn_rowref / attn_finish_stats / AttnRing /
+// attn_write_rows.  A fragment is used only where it left the instruction stream of every kernel what the written-out body gave
+// (hipcc's schedule follows the shape of the source, and these bodies are tuned on it); profiles/attn_fragments_isa.txt records
+// every cut that did not, and the sites that therefore stay written out say which other copies they must be changed with.
+// Fragments with float arithmetic switch FP contraction off for themselves, as the lean / LDS-staged bodies do; attn_kernel
+// compiles under hipcc's default (-ffp-contract=fast), so an expression the default may fuse there is not shared with it.
+constexpr float QD_MAGIC  = 12582912.f;                        // 1.5 * 2^23: float add == round-half-even to integer
+constexpr int   QD_MAGICI = 0x4B400000;                        // its bit pattern
+
+// Constant operands of the per-key zero-point term -zq' * sum_d k'[key][d]: every byte is -zq', in [-127, 128], as one or two
+// int8 constants (128 does not fit a signed byte: c2 != 0 only then).
+struct AttnZq {
+    int c2;
+    v4i c1v, c2v;
+    __device__ __forceinline__ explicit AttnZq(int nzq) {
+        const int c1 = nzq > 127 ? 64 : nzq;
+        c2 = nzq - c1;
+        const int c1w = (c1 & 0xff) * 0x01010101, c2w = (c2 & 0xff) * 0x01010101;
+        c1v = v4i{c1w, c1w, c1w, c1w};
+        c2v = v4i{c2w, c2w, c2w, c2w};
+    }
+};
+// The score chain of one 32-key tile on top of the caller's seeds: acc[4g+e] += k'[key] . q'[query], key = jt*32 + e + 8g +
+// 4*half, per-query constants dropped.  TERM (attn_kernel ASYM, attn_lean_body KT == 1): one more MFMA per K fragment against
+// the constant operand; the other bodies have the term in their seeds, or none (attn_qk).
+template <int DT, bool TERM>
+__device__ __forceinline__ void attn_scores(const v4i (&kf)[DT], const v4i (&qf)[DT], const AttnZq& z, v16i& acc) {
+#pragma unroll
+    for (int kk = 0; kk < DT; ++kk) {
+        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(kf[kk], qf[kk], acc, 0, 0, 0);
+        if (TERM) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(kf[kk], z.c1v, acc, 0, 0, 0);
+    }
+    if (TERM && z.c2 != 0) {                                  // wave-uniform, only when zq' == -128
+#pragma unroll
+        for (int kk = 0; kk < DT; ++kk) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(kf[kk], z.c2v, acc, 0, 0, 0);
+    }
+}
+
+// Does the key of accumulator register r of tile jt exist?  (Only the last tile of a ragged key axis has keys that do not.)
+__device__ __forceinline__ bool attn_key_ok(int S, int jt, int r, int half) { return jt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half < S; }
+
+// One tile of sweep 1 of the lean / LDS-staged bodies: a2 += exp2(fma(F, cs2, nc)) over the lane's 16 raw accumulators (packed
+// fp32 around the scalar exp2: two scores per instruction), mxa = their maximum (v_max3_i32).  TAIL: the caller has set the
+// accumulators of keys that do not exist to 0, "masked" (a raw accumulator is > 0 by its seed); the ragged tile is a
+// compile-time flag because with a run-time one the compiler kept the masking selects in the hot loop.
+template <bool TAIL>
+__device__ __forceinline__ void attn_s1_sum(const v16i& acc, const v2f& cs2v, const v2f& ncv, int& mxa, v2f& a2) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+        mxa = max(max(mxa, acc[r]), acc[r + 1]);
+        const v2f F = {__int_as_float(acc[r]), __int_as_float(acc[r + 1])};
+        const v2f x = __builtin_elementwise_fma(F, cs2v, ncv);
+        v2f e = {__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
+        if (TAIL) {
+            if (acc[r] == 0) e.x = 0.f;
+            if (acc[r + 1] == 0) e.y = 0.f;
+        }
+        a2 += e;
+    }
+}
+
+// Sweep 2, what a WAVE decides from {inv, emax} of its rows (attn_finish_stats; attn_pv_kernel reads them back from the
+// workspace): if attn_stats_kernel and attn_pv_kernel disagreed here, a block would run in the wrong launch.
+__device__ __forceinline__ float attn_top_code(float emax, float inv, float ubias) {
+#pragma clang fp contract(off)
+    return emax * inv * 1.0001f + ubias + 0.5f;               // above the largest code of the row (uu, before rounding)
+}
+// the upper clamp is needed — or ubias is odd: exact ties of e*inv would go to the even SUM, so the two-step rounding stays
+__device__ __forceinline__ bool attn_need_clamp(float emax, float inv, float ubias, float urange) {
+    return __any(!(attn_top_code(emax, inv, ubias) <= urange)) || (((int)ubias) & 1);
+}
+// some 16-bit code of the wave may reach 256: otherwise every hi operand byte is the constant 0x80 and the hi MFMAs are skipped
+__device__ __forceinline__ bool attn_hi_live(bool need_clamp, float emax, float inv, float ubias) {
+    return need_clamp || __any(!(attn_top_code(emax, inv, ubias) < 256.f));
+}
+
+// The code bits of four keys (float bits of uu + 1.5*2^23: bytes 0 / 1 are the lo / hi byte of the code) -> word g of the
+// operand of lo bytes and, HI, of the one of hi bytes: v_perm_b32 scatters them.  ^0x80: operand byte = code byte - 128;
+// BIAS128: the 128 is in the bits already (attn_pv_kernel, lo bytes only).
+template <bool HI, bool BIAS128>
+__device__ __forceinline__ void attn_pack4(const unsigned (&ub)[16], int g, v4i& plo, v4i& phi) {
+    const unsigned a01 = __builtin_amdgcn_perm(ub[4 * g + 1], ub[4 * g], 0x05010400u);      // lo0 lo1 hi0 hi1
+    const unsigned a23 = __builtin_amdgcn_perm(ub[4 * g + 3], ub[4 * g + 2], 0x05010400u);  // lo2 lo3 hi2 hi3
+    const unsigned lo = __builtin_amdgcn_perm(a23, a01, 0x05040100u);
+    plo[g] = BIAS128 ? (int)lo : (int)(lo ^ 0x80808080u);
+    if (HI) phi[g] = (int)(__builtin_amdgcn_perm(a23, a01, 0x07060302u) ^ 0x80808080u);
+}
+
+// K fragments of the register-fed bodies (dense, lean): tile jt of the lane's key row, DT 16-byte words
+template <int DT>
+__device__ __forceinline__ void attn_load_k(const AttnK& p, const int8_t* const& kbase, int jt, v4i (&kf)[DT]) {
+    const int8_t* kp = kbase + (long)jt * 32 * p.dpad;
+#pragma unroll
+    for (int kk = 0; kk < DT; ++kk) kf[kk] = *reinterpret_cast<const v4i*>(kp + kk * 32);
+}
+
 // prm layout (device floats): 0 cs = dq*dk*scale | 1 zq' | 2 zk' | 3 dw | 4 zpw | 5 dw*dv | 6 zv'
-//
+// ... and what every body derives from it and from the probability grid
+struct AttnConsts {
+    float cs2;                                                // scores -> log2 domain
+    float dw, zpw, oscale, urange, ubias;                     // codes are handled as uu = u - wmin in [0, urange]; ubias = zpw - wmin
+    int nzq, zv;
+    __device__ __forceinline__ explicit AttnConsts(const AttnK& p) {
+        cs2 = p.prm[0] * 1.4426950408889634f;
+        nzq = -(int)p.prm[1];
+        dw = p.prm[3], zpw = p.prm[4], oscale = p.prm[5];
+        zv = (int)p.prm[6];
+        urange = p.wmax - p.wmin;
+        ubias = zpw - p.wmin;
+    }
+};
+
 // VALU budget.  The kernel is VALU-bound (every score costs an int->float convert, an exp2 at quarter
 // rate and, in the second sweep, the quantisation of P), so the score path is kept to the minimum:
 //   * per-QUERY terms of the zero-point restoration (-zk*qsum_i + d*zq*zk) are dropped: a constant added
@@ -176,6 +289,7 @@ __device__ __forceinline__ void attn_write_rows(const AttnK& p, const v16i (&ol)
 template <int DT, bool P16, bool ASYM>
 // (3 blocks per CU was tried for DT=2/P16: 168 VGPRs + 100 B of scratch, 16% slower end to end.)
 __global__ __launch_bounds__(256, (DT * (P16 ? 2 : 1) <= 6) ? 2 : 1) void attn_kernel(const AttnK p) {
+    // (lane coordinates, block -> head / queries, query fragments: written out in all four bodies — change them together)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int frow = lane & 31, half = lane >> 5;
     const int lblk = p.xcd ? qd_xcd_remap(blockIdx.x, p.gx * p.BH) : (int)blockIdx.x;
@@ -183,14 +297,10 @@ __global__ __launch_bounds__(256, (DT * (P16 ? 2 : 1) <= 6) ? 2 : 1) void attn_k
     const int q0 = ((lblk - bh * p.gx) * 4 + wave) * 32;
     if (q0 >= p.T) return;
 
-    const float cs2 = p.prm[0] * 1.4426950408889634f;            // scores -> log2 domain
-    const int nzq = -(int)p.prm[1];
-    const float dw = p.prm[3], zpw = p.prm[4], oscale = p.prm[5];
-    const int zv = (int)p.prm[6];
-    const int izpw = (int)zpw;
-    const float urange = p.wmax - p.wmin;                         // codes are handled as uu = u - wmin in [0, urange]
-    const float ubias = zpw - p.wmin;
-    constexpr float MAGIC = 12582912.f;                           // 1.5 * 2^23: float add == round-half-even to integer
+    const AttnConsts c(p);
+    const float cs2 = c.cs2, dw = c.dw, zpw = c.zpw, oscale = c.oscale, urange = c.urange, ubias = c.ubias;
+    const int nzq = c.nzq, zv = c.zv;
+    constexpr float MAGIC = QD_MAGIC;
     constexpr int   MASKED = -(1 << 30);
 
     v4i qf[DT];
@@ -199,37 +309,23 @@ __global__ __launch_bounds__(256, (DT * (P16 ? 2 : 1) <= 6) ? 2 : 1) void attn_k
     for (int kk = 0; kk < DT; ++kk) qf[kk] = *reinterpret_cast<const v4i*>(qrow + kk * 32);
 
     const int8_t* kbase = p.k + (long)bh * p.Spad * p.dpad + (long)frow * p.dpad + half * 16;
-    // -zq' in [-127, 128] as one or two int8 constants (128 does not fit a signed byte)
-    const int c1 = nzq > 127 ? 64 : nzq, c2 = nzq - c1;
-    const int c1w = (c1 & 0xff) * 0x01010101, c2w = (c2 & 0xff) * 0x01010101;
-    const v4i c1v = {c1w, c1w, c1w, c1w}, c2v = {c2w, c2w, c2w, c2w};
+    const AttnZq zq(nzq);
     const int ntile = p.Spad >> 5;
     const int tail_tile = (p.S & 31) ? ntile - 1 : ntile;         // index of the ragged tile (or none)
 
     // K-tile registers (double-buffered by hand: `kf/ks` = current tile, loaded one iteration ahead)
-    auto load_k = [&](int jt, v4i (&kf)[DT]) __attribute__((always_inline)) {
-        const int8_t* kp = kbase + (long)jt * 32 * p.dpad;
-#pragma unroll
-        for (int kk = 0; kk < DT; ++kk) kf[kk] = *reinterpret_cast<const v4i*>(kp + kk * 32);
-    };
+    auto load_k = [&](int jt, v4i (&kf)[DT]) __attribute__((always_inline)) { attn_load_k<DT>(p, kbase, jt, kf); };
     // d[4g+e] = (score of key jt*32 + e + 8g + 4*half) - base, per-query constants dropped
     auto scores = [&](const v4i (&kf)[DT], int base, int (&d)[16]) __attribute__((always_inline)) {
         v16i acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = -base;
-#pragma unroll
-        for (int kk = 0; kk < DT; ++kk) {
-            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(kf[kk], qf[kk], acc, 0, 0, 0);
-            if (ASYM) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(kf[kk], c1v, acc, 0, 0, 0);
-        }
-        if (ASYM && c2 != 0) {                                    // wave-uniform, only when zq' == -128
-#pragma unroll
-            for (int kk = 0; kk < DT; ++kk) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(kf[kk], c2v, acc, 0, 0, 0);
-        }
+        attn_scores<DT, ASYM>(kf, qf, zq, acc);
 #pragma unroll
         for (int r = 0; r < 16; ++r) d[r] = acc[r];
     };
-    auto key_ok = [&](int jt, int r) __attribute__((always_inline)) { return jt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half < p.S; };
+    // (through a lambda: direct calls moved the accumulator zeroing of the DT 4 / 5 / 8 instances)
+    auto key_ok = [&](int jt, int r) __attribute__((always_inline)) { return attn_key_ok(p.S, jt, r, half); };
 
     // ---- sweep 1: row max (integer) and normaliser (online) ---------------------------------------
     int mi;                                                       // running integer row max (shifted scores)
@@ -298,7 +394,7 @@ __global__ __launch_bounds__(256, (DT * (P16 ? 2 : 1) <= 6) ? 2 : 1) void attn_k
     const float inv = 1.0f / (l * dw);                            // p/dw = e * inv
 
     // ---- sweep 2: quantise P, accumulate P.V ------------------------------------------------------
-    v16i ol[DT], oh[P16 ? DT : 1];
+    v16i ol[DT], oh[P16 ? DT : 1];                                // (zeroed alike in attn_kernel, attn_lean_body, attn_pv_kernel)
 #pragma unroll
     for (int t = 0; t < DT; ++t)
 #pragma unroll
@@ -348,7 +444,7 @@ __global__ __launch_bounds__(256, (DT * (P16 ? 2 : 1) <= 6) ? 2 : 1) void attn_k
             v4i plo, phi;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                // bytes 0/1 of each word are the lo/hi byte of the code
+                // attn_pack4, written out with the v_dot4 in between (the call moved instructions in attn_kernel<1, true, *>)
                 const unsigned a01 = __builtin_amdgcn_perm(ub[4 * g + 1], ub[4 * g], 0x05010400u);      // lo0 lo1 hi0 hi1
                 const unsigned a23 = __builtin_amdgcn_perm(ub[4 * g + 3], ub[4 * g + 2], 0x05010400u);  // lo2 lo3 hi2 hi3
                 plo[g] = (int)(__builtin_amdgcn_perm(a23, a01, 0x05040100u) ^ 0x80808080u);
@@ -420,9 +516,6 @@ __global__ __launch_bounds__(256, (DT * (P16 ? 2 : 1) <= 6) ? 2 : 1) void attn_k
 //     of the output tile is sum_j code_j — no v_dot4 in the loop.
 __device__ __attribute__((aligned(16))) int qd_ones16[4] = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
 
-constexpr float QD_MAGIC  = 12582912.f;                        // 1.5 * 2^23
-constexpr int   QD_MAGICI = 0x4B400000;                        // its bit pattern
-
 struct AttnRowRef { float nc, eps; };                          // x = fma(F, cs2, nc);  eps = (1.5*2^23 + m)*cs2 + nc, exactly
 __device__ __forceinline__ AttnRowRef attn_rowref(int m, float cs2) {
 #pragma clang fp contract(off)
@@ -432,7 +525,8 @@ __device__ __forceinline__ AttnRowRef attn_rowref(int m, float cs2) {
     r.eps = __builtin_fmaf(fm, cs2, r.nc);                     // the rounding error of a product is a float
     return r;
 }
-// End of sweep 1 (shared by the lean and the LDS-staged kernel so that both evaluate the SAME float expressions): `l` = this
+// End of sweep 1 (shared by the lean and the LDS-staged kernel, like attn_s1_sum, so that both evaluate the SAME float
+// expressions): `l` = this
 // half-wave's sum of exp2(cs2*(s - m0) + eps0), `mxn` = how far this half's maximum lies above m0 (may be negative: m0 is the
 // maximum of tile 0 over BOTH halves).  Returns the row maximum mi, the reference of sweep 2, and 1 / (normaliser * dw) such
 // that e2 * inv = p / dw for e2 = exp2(fma(F, cs2, ref2.nc)).
@@ -456,6 +550,7 @@ __device__ __forceinline__ void attn_lean_body(const AttnK& p) {
     // a*b+c written as such stays unfused: hipcc's default -ffp-contract=fast lets the optimiser fuse (or not) depending on the
     // surrounding code, and the lean and the LDS-staged bodies must produce the same normaliser bit for bit
 #pragma clang fp contract(off)
+    // (lane coordinates, block -> head / queries, query fragments: written out in all four bodies — change them together)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int frow = lane & 31, half = lane >> 5;
     const int lblk = p.xcd ? qd_xcd_remap(blockIdx.x, p.gx * p.BH) : (int)blockIdx.x;
@@ -463,13 +558,9 @@ __device__ __forceinline__ void attn_lean_body(const AttnK& p) {
     const int q0 = ((lblk - bh * p.gx) * 4 + wave) * 32;
     if (q0 >= p.T) return;
 
-    const float cs2 = p.prm[0] * 1.4426950408889634f;
-    const int nzq = -(int)p.prm[1];
-    const float dw = p.prm[3], zpw = p.prm[4], oscale = p.prm[5];
-    const int zv = (int)p.prm[6];
-    const int izpw = (int)zpw;
-    const float urange = p.wmax - p.wmin;
-    const float ubias = zpw - p.wmin;
+    const AttnConsts c(p);
+    const float cs2 = c.cs2, dw = c.dw, zpw = c.zpw, oscale = c.oscale, urange = c.urange, ubias = c.ubias;
+    const int nzq = c.nzq, zv = c.zv;
     constexpr float MAGIC = QD_MAGIC;
     constexpr int   MAGICI = QD_MAGICI;
 
@@ -479,17 +570,11 @@ __device__ __forceinline__ void attn_lean_body(const AttnK& p) {
     for (int kk = 0; kk < DT; ++kk) qf[kk] = *reinterpret_cast<const v4i*>(qrow + kk * 32);
     const int8_t* kbase = p.k + (long)bh * p.Spad * p.dpad + (long)frow * p.dpad + half * 16;
     const int32_t* tbase = KT == 2 ? p.kterm + (long)bh * p.Spad + half * 4 : nullptr;
-    const int c1 = nzq > 127 ? 64 : nzq, c2 = nzq - c1;           // KT == 1: -zq' in [-127, 128] as one or two int8 constants
-    const int c1w = (c1 & 0xff) * 0x01010101, c2w = (c2 & 0xff) * 0x01010101;
-    const v4i c1v = {c1w, c1w, c1w, c1w}, c2v = {c2w, c2w, c2w, c2w};
+    const AttnZq zq(nzq);                                         // KT == 1
     const int ntile = p.Spad >> 5;
     const int tail_tile = (p.S & 31) ? ntile - 1 : ntile;
 
-    auto load_k = [&](int jt, v4i (&kf)[DT]) __attribute__((always_inline)) {
-        const int8_t* kp = kbase + (long)jt * 32 * p.dpad;
-#pragma unroll
-        for (int kk = 0; kk < DT; ++kk) kf[kk] = *reinterpret_cast<const v4i*>(kp + kk * 32);
-    };
+    auto load_k = [&](int jt, v4i (&kf)[DT]) __attribute__((always_inline)) { attn_load_k<DT>(p, kbase, jt, kf); };
     // seeds of the 16 accumulator registers of this lane for tile jt: register 4g+e <-> key jt*32 + e + 8g + 4*half
     auto load_t = [&](int jt, v16i& ti) __attribute__((always_inline)) {
         if (KT == 2) {
@@ -507,17 +592,8 @@ __device__ __forceinline__ void attn_lean_body(const AttnK& p) {
     // acc[4g+e] = 0x4B400000 + (score of key jt*32 + e + 8g + 4*half), per-query constants dropped
     auto scores = [&](const v4i (&kf)[DT], const v16i& ti, v16i& acc) __attribute__((always_inline)) {
         acc = ti;
-#pragma unroll
-        for (int kk = 0; kk < DT; ++kk) {
-            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(kf[kk], qf[kk], acc, 0, 0, 0);
-            if (KT == 1) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(kf[kk], c1v, acc, 0, 0, 0);
-        }
-        if (KT == 1 && c2 != 0) {                                  // wave-uniform, only when zq' == -128
-#pragma unroll
-            for (int kk = 0; kk < DT; ++kk) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(kf[kk], c2v, acc, 0, 0, 0);
-        }
+        attn_scores<DT, KT == 1>(kf, qf, zq, acc);
     };
-    auto key_ok = [&](int jt, int r) __attribute__((always_inline)) { return jt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half < p.S; };
     const v2f cs2v = {cs2, cs2};
 
     // ---- sweep 1 ----------------------------------------------------------------------------------------------------
@@ -531,9 +607,9 @@ __device__ __forceinline__ void attn_lean_body(const AttnK& p) {
         {
             v16i acc;
             scores(kf, ti, acc);
-            m0 = 0;                                               // raw accumulators are > 0; 0 = masked
+            m0 = 0;                                               // raw accumulators are > 0; 0 = masked (attn_stats_kernel: the same seed)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) m0 = max(m0, (tail_tile == 0 && !key_ok(0, r)) ? 0 : acc[r]);
+            for (int r = 0; r < 16; ++r) m0 = max(m0, (tail_tile == 0 && !attn_key_ok(p.S, 0, r, half)) ? 0 : acc[r]);
             m0 -= MAGICI;
             m0 = max(m0, __shfl_xor(m0, 32));                     // one reference for both halves of the query row
         }
@@ -553,20 +629,9 @@ __device__ __forceinline__ void attn_lean_body(const AttnK& p) {
                 if (KT == 2 && jt + 1 < ntile) load_t(jt + 1, ti);
                 if (tail) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) if (!key_ok(jt, r)) acc[r] = 0;
+                    for (int r = 0; r < 16; ++r) if (!attn_key_ok(p.S, jt, r, half)) acc[r] = 0;
                 }
-#pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    mxa = max(max(mxa, acc[r]), acc[r + 1]);              // v_max3_i32
-                    const v2f F = {__int_as_float(acc[r]), __int_as_float(acc[r + 1])};
-                    const v2f x = __builtin_elementwise_fma(F, cs2v, ncv);
-                    v2f e = {__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
-                    if (tail) {
-                        if (acc[r] == 0) e.x = 0.f;
-                        if (acc[r + 1] == 0) e.y = 0.f;
-                    }
-                    a2 += e;
-                }
+                attn_s1_sum<tail>(acc, cs2v, ncv, mxa, a2);
                 if (jt + 1 < ntile) {
 #pragma unroll
                     for (int kk = 0; kk < DT; ++kk) kf[kk] = kfn[kk];
@@ -589,7 +654,7 @@ __device__ __forceinline__ void attn_lean_body(const AttnK& p) {
     (void)mi;
 
     // ---- sweep 2 ----------------------------------------------------------------------------------------------------
-    v16i ol[DT], oh[P16 ? DT : 1];
+    v16i ol[DT], oh[P16 ? DT : 1];                                // (zeroed alike in attn_kernel, attn_lean_body, attn_pv_kernel)
 #pragma unroll
     for (int t = 0; t < DT; ++t)
 #pragma unroll
@@ -597,7 +662,7 @@ __device__ __forceinline__ void attn_lean_body(const AttnK& p) {
             ol[t][r] = 0;
             if (P16) oh[P16 ? t : 0][r] = 0;
         }
-    const int t1 = p.d >> 5, frow1 = p.d & 31;                     // where the row of ones sits
+    const int t1 = p.d >> 5, frow1 = p.d & 31;                     // where the row of ones sits (attn_pv_kernel: AttnRing's vsrc)
     const int8_t* vp[DT];
     int vstep[DT];
 #pragma unroll
@@ -622,7 +687,7 @@ __device__ __forceinline__ void attn_lean_body(const AttnK& p) {
             v16i acc;
             scores(kf, ti, acc);
             if (KT == 2 && jt + 1 < ntile) load_t(jt + 1, ti);
-            unsigned ub[16];
+            unsigned ub[16];                                      // (accumulator -> code bits: attn_pv_kernel's `chain`, together)
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {
                 const v2f F = {__int_as_float(acc[r]), __int_as_float(acc[r + 1])};
@@ -642,15 +707,13 @@ __device__ __forceinline__ void attn_lean_body(const AttnK& p) {
             }
             if (tail) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) if (!key_ok(jt, r)) ub[r] = 0x8080u;
+                for (int r = 0; r < 16; ++r) if (!attn_key_ok(p.S, jt, r, half)) ub[r] = 0x8080u;
             }
             v4i plo, phi;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const unsigned a01 = __builtin_amdgcn_perm(ub[4 * g + 1], ub[4 * g], 0x05010400u);
-                const unsigned a23 = __builtin_amdgcn_perm(ub[4 * g + 3], ub[4 * g + 2], 0x05010400u);
-                plo[g] = (int)(__builtin_amdgcn_perm(a23, a01, 0x05040100u) ^ 0x80808080u);
-                phi[g] = P16 ? (int)(__builtin_amdgcn_perm(a23, a01, 0x07060302u) ^ 0x80808080u) : 0;
+                phi[g] = 0;
+                attn_pack4<P16, false>(ub, g, plo, phi);
             }
 #pragma unroll
             for (int t = 0; t < DT; ++t) {
@@ -663,7 +726,8 @@ __device__ __forceinline__ void attn_lean_body(const AttnK& p) {
             }
         };
         // (an odd ubias would send exact ties of e*inv to the even SUM: keep the two-step rounding of the clamp path then)
-        if (__any(!(emax * inv * 1.0001f + ubias + 0.5f <= urange)) || (((int)ubias) & 1)) {
+        // attn_need_clamp, spelt out on attn_top_code (the call itself changed the stream of every lean instance)
+        if (__any(!(attn_top_code(emax, inv, ubias) <= urange)) || (((int)ubias) & 1)) {
             for (int jt = 0; jt < tail_tile; ++jt) s2_tile(jt, std::false_type{}, std::true_type{});
         } else {
             for (int jt = 0; jt < tail_tile; ++jt) s2_tile(jt, std::false_type{}, std::false_type{});
@@ -672,7 +736,8 @@ __device__ __forceinline__ void attn_lean_body(const AttnK& p) {
     }
 
     // ---- epilogue ---------------------------------------------------------------------------------------------------
-    // code sums of query il(r, half): column d of the output tile, i.e. register r of lane frow1 + 32*half
+    // code sums of query il(r, half): column d of the output tile, i.e. register r of lane frow1 + 32*half (attn_pv_kernel's
+    // epilogue is this loop with hi_live for P16: change them together)
     int us[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -718,7 +783,8 @@ __device__ __attribute__((aligned(16))) OnesRow qd_ones_row_obj = OnesRow();   /
 // 255.5 for all lanes — the common case with thousands of keys and unpeaked rows), every hi operand byte is the constant
 // 0x80: the hi MFMAs and their v_perm / v_xor are skipped and the epilogue uses the 8-bit zero-point constants.
 // Arithmetic, operand order and summation order are those of attn_lean_kernel: bit-identical results
-// (tests/test_hip_kernels.py::test_attention_lds_equals_lean).
+// (tests/test_hip_kernels.py::test_attention_lds_equals_lean; tests/test_attention_exact_gpu.py holds every lean /
+// LDS-staged form to equal bytes).
 // What it buys, honestly: 64x64 self-attention of SD (T = S = 4096, d = 40, 128 heads) 1170 -> 1047 us on unpeaked rows
 // (-10 %, most of it the skipped hi MFMAs), 1180 -> 1143 us on peaked rows; short key axes (77-token cross-attention) are
 // SLOWER (ring start-up, barriers) and stay on attn_lean_kernel.  What did NOT help, all measured on the same shape: a
@@ -756,7 +822,8 @@ __device__ __forceinline__ void attn_wait_lgkm0() { asm volatile("s_waitcnt lgkm
 //     returns after reading its flag).
 // The latency of a wave's MFMA -> v_exp -> pack -> MFMA chain is covered by the OTHER waves of the SIMD instead of by a second
 // accumulator set of the same wave.  Arithmetic, operand order and summation order are attn_lean_kernel's: bit-identical
-// (tests/test_hip_kernels.py::test_attention_lds_equals_lean).
+// (tests/test_hip_kernels.py::test_attention_lds_equals_lean; tests/test_attention_exact_gpu.py holds every lean /
+// LDS-staged form to equal bytes).
 struct AttnStat { float nc, inv, emax; int pad; };            // 16 bytes per query: [BH][Tpad]
 
 template <int DT, int KT, bool WITH_V>
@@ -903,6 +970,7 @@ __global__ __launch_bounds__(256, QD_ATTN_STATS_OCC) void attn_stats_kernel(cons
     using Ring = AttnRing<DT, KT, false>;
     __shared__ __attribute__((aligned(16))) unsigned char smem[Ring::NST * Ring::STAGE];
     __shared__ int s_flag[2];
+    // (lane coordinates, block -> head / queries, query fragments: written out in all four bodies — change them together)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int frow = lane & 31, half = lane >> 5;
@@ -911,10 +979,8 @@ __global__ __launch_bounds__(256, QD_ATTN_STATS_OCC) void attn_stats_kernel(cons
     const int q0r = ((lblk - bh * p.gx) * 4 + wave) * 32;
     const bool live = q0r < p.T;                              // a wave past the last query still serves the DMA ring and the barriers
     const int q0 = live ? q0r : 0;
-    const float cs2 = p.prm[0] * 1.4426950408889634f;
-    const float dw = p.prm[3], zpw = p.prm[4];
-    const float urange = p.wmax - p.wmin;
-    const float ubias = zpw - p.wmin;
+    const AttnConsts c(p);
+    const float cs2 = c.cs2, dw = c.dw, urange = c.urange, ubias = c.ubias;
     constexpr int MAGICI = QD_MAGICI;
 
     v4i qf[DT];
@@ -924,7 +990,6 @@ __global__ __launch_bounds__(256, QD_ATTN_STATS_OCC) void attn_stats_kernel(cons
     const int ntile = p.Spad >> 5;
     const int nfull = (p.S & 31) ? ntile - 1 : ntile;
     const Ring ring(p, smem, bh, wave, lane);
-    auto key_ok = [&](int jt, int r) __attribute__((always_inline)) { return jt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half < p.S; };
     const v2f cs2v = {cs2, cs2};
 
     v4i kf[DT];
@@ -934,9 +999,9 @@ __global__ __launch_bounds__(256, QD_ATTN_STATS_OCC) void attn_stats_kernel(cons
     ring.read_k(0, kf);
     ring.read_t(0, acc);
     attn_qk<DT, KT>(kf, qf, acc);
-    int m0 = 0;                                               // raw accumulators are > 0; 0 = masked
+    int m0 = 0;                                               // raw accumulators are > 0; 0 = masked (attn_lean_body: the same seed)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) m0 = max(m0, (nfull == 0 && !key_ok(0, r)) ? 0 : acc[r]);
+    for (int r = 0; r < 16; ++r) m0 = max(m0, (nfull == 0 && !attn_key_ok(p.S, 0, r, half)) ? 0 : acc[r]);
     m0 -= MAGICI;
     m0 = max(m0, __shfl_xor(m0, 32));                         // one reference for both halves of the query row
     float l = 0.f;
@@ -957,20 +1022,9 @@ __global__ __launch_bounds__(256, QD_ATTN_STATS_OCC) void attn_stats_kernel(cons
             attn_qk<DT, KT>(kf, qf, acc);
             if (tail) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) if (!key_ok(jt, r)) acc[r] = 0;
+                for (int r = 0; r < 16; ++r) if (!attn_key_ok(p.S, jt, r, half)) acc[r] = 0;
             }
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                mxa = max(max(mxa, acc[r]), acc[r + 1]);
-                const v2f F = {__int_as_float(acc[r]), __int_as_float(acc[r + 1])};
-                const v2f x = __builtin_elementwise_fma(F, cs2v, ncv);
-                v2f e = {__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
-                if (tail) {
-                    if (acc[r] == 0) e.x = 0.f;
-                    if (acc[r + 1] == 0) e.y = 0.f;
-                }
-                a2 += e;
-            }
+            attn_s1_sum<tail>(acc, cs2v, ncv, mxa, a2);
         };
         int jt = 0;
         for (; jt + 4 <= nfull; jt += 4) {                    // four tiles = one turn of the ring: stage offsets are immediates
@@ -1006,9 +1060,9 @@ __global__ __launch_bounds__(256, QD_ATTN_STATS_OCC) void attn_stats_kernel(cons
     }
     attn_wait_vmcnt<0>();                                     // the ring's run-ahead copies: nothing may land in LDS after the block retires
     const AttnNorm nrm = attn_finish_stats(l, mxn, m0, ref0, cs2, dw);
-    // what sweep 2 decides per WAVE (attn_pv_kernel evaluates the same two expressions on the stored values)
-    const bool need_clamp = __any(!(nrm.emax * nrm.inv * 1.0001f + ubias + 0.5f <= urange)) || (((int)ubias) & 1);
-    const bool hi_live = p16 && (need_clamp || __any(!(nrm.emax * nrm.inv * 1.0001f + ubias + 0.5f < 256.f)));
+    // what sweep 2 decides per WAVE: attn_pv_kernel calls the same two functions on the stored values
+    const bool need_clamp = attn_need_clamp(nrm.emax, nrm.inv, ubias, urange);
+    const bool hi_live = p16 && attn_hi_live(need_clamp, nrm.emax, nrm.inv, ubias);
     if (live && (need_clamp || hi_live) && lane == 0) s_flag[1] = 1;
     if (live && half == 0) stat[(long)bh * p.Tpad + q0 + frow] = AttnStat{nrm.ref.nc, nrm.inv, nrm.emax, 0};
     __syncthreads();
@@ -1022,6 +1076,7 @@ __global__ __launch_bounds__(256, FULL ? QD_ATTN_PVFULL_OCC : QD_ATTN_PV_OCC) vo
     using Ring = AttnRing<DT, KT, true>;
     constexpr bool HIK = FULL && P16;                         // this kernel owns hi accumulators
     __shared__ __attribute__((aligned(16))) unsigned char smem[Ring::NST * Ring::STAGE];
+    // (lane coordinates, block -> head / queries, query fragments: written out in all four bodies — change them together)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int frow = lane & 31, half = lane >> 5;
@@ -1031,11 +1086,9 @@ __global__ __launch_bounds__(256, FULL ? QD_ATTN_PVFULL_OCC : QD_ATTN_PV_OCC) vo
     const int q0r = ((lblk - bh * p.gx) * 4 + wave) * 32;
     const bool live = q0r < p.T;
     const int q0 = live ? q0r : 0;
-    const float cs2 = p.prm[0] * 1.4426950408889634f;
-    const float dw = p.prm[3], zpw = p.prm[4], oscale = p.prm[5];
-    const int zv = (int)p.prm[6];
-    const float urange = p.wmax - p.wmin;
-    const float ubias = zpw - p.wmin;
+    const AttnConsts c(p);
+    const float cs2 = c.cs2, dw = c.dw, zpw = c.zpw, oscale = c.oscale, urange = c.urange, ubias = c.ubias;
+    const int zv = c.zv;
     constexpr float MAGIC = QD_MAGIC;
 
     v4i qf[DT];
@@ -1047,10 +1100,9 @@ __global__ __launch_bounds__(256, FULL ? QD_ATTN_PVFULL_OCC : QD_ATTN_PV_OCC) vo
     const int ntile = p.Spad >> 5;
     const int nfull = (p.S & 31) ? ntile - 1 : ntile;
     const Ring ring(p, smem, bh, wave, lane);
-    auto key_ok = [&](int jt, int r) __attribute__((always_inline)) { return jt * 32 + (r & 3) + 8 * (r >> 2) + 4 * half < p.S; };
     const v2f cs2v = {cs2, cs2};
 
-    v16i ol[DT], oh[HIK ? DT : 1];
+    v16i ol[DT], oh[HIK ? DT : 1];                            // (zeroed alike in attn_kernel, attn_lean_body, attn_pv_kernel)
 #pragma unroll
     for (int t = 0; t < DT; ++t)
 #pragma unroll
@@ -1059,8 +1111,8 @@ __global__ __launch_bounds__(256, FULL ? QD_ATTN_PVFULL_OCC : QD_ATTN_PV_OCC) vo
             if (HIK) oh[HIK ? t : 0][r] = 0;
         }
     const int t1 = p.d >> 5, frow1 = p.d & 31;
-    const bool need_clamp = FULL && (__any(!(emax * inv * 1.0001f + ubias + 0.5f <= urange)) || (((int)ubias) & 1));
-    const bool hi_live = HIK && (need_clamp || __any(!(emax * inv * 1.0001f + ubias + 0.5f < 256.f)));
+    const bool need_clamp = FULL && attn_need_clamp(emax, inv, ubias, urange);
+    const bool hi_live = HIK && attn_hi_live(need_clamp, emax, inv, ubias);
     {
         const v2f ncv = {st.nc, st.nc};
         const v2f invv = {inv, inv}, ubv = {ubias, ubias}, magic = {MAGIC, MAGIC}, ubm = {ubias + MAGIC, ubias + MAGIC};
@@ -1071,6 +1123,7 @@ __global__ __launch_bounds__(256, FULL ? QD_ATTN_PVFULL_OCC : QD_ATTN_PV_OCC) vo
         //  the 128 rides in the FMA's constant (even, like MAGIC: ties still go to the even code) and the v_xor disappears)
         const v2f ubm128 = {ubias + MAGIC + 128.f, ubias + MAGIC + 128.f};
         // the probability chain of one 32 x 32 score tile: 16 accumulators of this lane -> four operand words of lo (and hi) bytes
+        // (accumulator -> code bits is attn_lean_body's s2_tile loop, pack and quantise interleaved pairwise: change them together)
         auto chain = [&](const v16i& acc, int jt, auto tail_tag, auto clamp_tag, auto hi_tag, v4i& plo, v4i& phi) __attribute__((always_inline)) {
             constexpr bool tail = decltype(tail_tag)::value, CLAMP = decltype(clamp_tag)::value, HI = decltype(hi_tag)::value;
             constexpr bool BIAS128 = !tail && !CLAMP && !HI;
@@ -1093,17 +1146,10 @@ __global__ __launch_bounds__(256, FULL ? QD_ATTN_PVFULL_OCC : QD_ATTN_PV_OCC) vo
                 ub[r] = __float_as_uint(t2.x);
                 ub[r + 1] = __float_as_uint(t2.y);
                 if (tail) {
-                    if (!key_ok(jt, r)) ub[r] = 0x8080u;
-                    if (!key_ok(jt, r + 1)) ub[r + 1] = 0x8080u;
+                    if (!attn_key_ok(p.S, jt, r, half)) ub[r] = 0x8080u;
+                    if (!attn_key_ok(p.S, jt, r + 1, half)) ub[r + 1] = 0x8080u;
                 }
-                if (sidx & 1) {
-                    const int g = sidx >> 1;
-                    const unsigned a01 = __builtin_amdgcn_perm(ub[4 * g + 1], ub[4 * g], 0x05010400u);
-                    const unsigned a23 = __builtin_amdgcn_perm(ub[4 * g + 3], ub[4 * g + 2], 0x05010400u);
-                    const unsigned lo = __builtin_amdgcn_perm(a23, a01, 0x05040100u);
-                    plo[g] = BIAS128 ? (int)lo : (int)(lo ^ 0x80808080u);
-                    if (HI) phi[g] = (int)(__builtin_amdgcn_perm(a23, a01, 0x07060302u) ^ 0x80808080u);
-                }
+                if (sidx & 1) attn_pack4<HI, BIAS128>(ub, sidx >> 1, plo, phi);
             }
         };
         auto tile = [&](int jt, auto tail_tag, auto clamp_tag, auto hi_tag, auto st_tag, bool met = false) __attribute__((always_inline)) {
@@ -1205,7 +1251,7 @@ __global__ __launch_bounds__(256, FULL ? QD_ATTN_PVFULL_OCC : QD_ATTN_PV_OCC) vo
     }
     if (!live) return;
 
-    // ---- epilogue (attn_lean_kernel's, with the 8-bit constants when the hi bytes were provably all zero) --------------
+    // ---- epilogue: attn_lean_body's code-sum loop (change them together), 8-bit constants when the hi bytes were provably all zero
     int us[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
