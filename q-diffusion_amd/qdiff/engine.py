@@ -449,6 +449,25 @@ def upsample_fold_ok(plan, H, W):
     return bool(plan.pack.tiled and plan.kh * plan.kw > 1 and plan.stride == 1 and H % 2 == 0 and W % 2 == 0)
 
 
+def _pair_launch_differs(plan, xq, B, H, W, Ho, Wo, out_dtype, pad_tl, splitk, upsample2x):
+    """The launch conv_forward is about to make on B samples and the same launch on 2B: do the library's answers (rows and
+    columns of a block, K slices; qd_conv2d_i8_form, nothing runs) differ?  Threads per block do not count: two K-groups and the
+    four-wave block write the same statistics (tests/test_conv_tall_tiles_gpu.py, test_hip_kernels.py)."""
+    if upsample2x or not plan.pack.tiled:
+        return False
+    pad = plan.pad if pad_tl is None else pad_tl
+    probe = torch.empty(1, dtype=out_dtype, device=xq.device)                   # an address of the output's type, never written
+    call = hip.ConvCall(x=xq, w=plan.pack.wq, out=probe, bias=plan.bias, ldx=plan.ldx, ldk=plan.pack.ldk, ldo=plan.Cout, ldr=0,
+                        ld_rowbias=0, B=B, H=H, W=W, Ho=Ho, Wo=Wo, Cout=plan.Cout, kh=plan.kh, kw=plan.kw, stride=plan.stride,
+                        pad_t=pad, pad_l=pad, wbits=plan.pack.wbits, w_tiled=True, segs=plan.segs, splitk=splitk)
+    forms = []
+    for b in (B, 2 * B):
+        call.B = b
+        f = hip.conv2d_i8_form(call)
+        forms.append((f[0], f[1], f[3]))
+    return forms[0] != forms[1]
+
+
 def conv_forward(plan, xq, B, H, W, Ho=None, Wo=None, out=None, rowbias=None, residual=None, acc_out=None,
                  out_dtype=None, pad_tl=None, splitk=None, gn_stats=False, slot=None, upsample2x=False, res_period=0):
     """Run K3/K4 on quantised rows xq [B*H*W][ldx].  Returns out [B*Ho*Wo][Cout] (row-major).
@@ -463,6 +482,20 @@ def conv_forward(plan, xq, B, H, W, Ho=None, Wo=None, out=None, rowbias=None, re
     M = B * Ho * Wo
     if out_dtype is None:
         out_dtype = out.dtype if out is not None else stream_dtype()
+    if (gn_stats and _PAIR_N[0] == B and acc_out is None and out is None and not res_period and xq.is_cuda
+            and _pair_launch_differs(plan, xq, B, H, W, Ho, Wo, out_dtype, pad_tl, splitk, upsample2x)):
+        # Inside the shared stretch of a guidance pair, and the launch on all 2n samples would take another tile or another number
+        # of K slices: the rows would be the same bytes, the GroupNorm statistics would not (each tile sums its 128-row chunk in
+        # its own fp32 order, the pass behind split-K in row order).  This one launch runs as the unshared evaluation runs it,
+        # on both (equal) halves, and the stretch goes on with the first.
+        dup = lambda t, rows: None if t is None else t[:rows].repeat((2,) + (1,) * (t.dim() - 1))
+        full = conv_forward(plan, dup(xq, B * H * W), 2 * B, H, W, Ho, Wo, rowbias=dup(rowbias, B), residual=dup(residual, M),
+                            out_dtype=out_dtype, pad_tl=pad_tl, splitk=splitk, gn_stats=True, upsample2x=upsample2x)
+        half = full[:M]
+        part = getattr(full, "qd_gn_part", None)
+        if part is not None:
+            half.qd_gn_part = part[:B]
+        return half
     if residual is not None and acc_out is None and residual.dtype != out_dtype:
         residual = residual.to(out_dtype)                  # the kernel reads the residual in the output's type
     if out is None and acc_out is None:

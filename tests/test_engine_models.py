@@ -92,6 +92,21 @@ def test_quantised_unet_matches_reference(cuda, name):
     assert all(m.int_ready() for m in mods)
     y = _run(qnn, fx, cuda)
     assert all(m._plan is not None for m in mods), "a QuantModule did not run the integer kernel"
+    _assert_envelope(name, y, fx)
+    if name in TINY + ["cifar_full", "ldm_updown_tiny"]:
+        qnn.set_quant_state(True, False)
+        d, cos, mx = _metrics(_run(qnn, fx, cuda), fx["out_w"])
+        print(f"[{name}] W-only: max|diff|={d:.3e}")
+        assert d <= 1e-3 * mx
+        qnn.set_quant_state(False, False)
+        d, cos, mx = _metrics(_run(qnn, fx, cuda), fx["out_fp"])
+        print(f"[{name}] fp: max|diff|={d:.3e}")
+        assert d <= 1e-3 * mx
+
+
+def _assert_envelope(name, y, fx):
+    """The (weight+act) bounds of the module docstring on y, the engine's fp32 output for the fixture's two `test` samples
+    (shared with tests/test_bench_batch_parity_gpu.py, which holds the same samples evaluated inside a larger batch to them)."""
     d, cos, mx = _metrics(y, fx["out_wa"])
     print(f"\n[{name}] W+A vs reference fp32: max|diff|={d:.3e} ({d / mx:.2e} of range), cosine={cos:.7f}")
     y64 = _oracle64(fx)
@@ -104,15 +119,6 @@ def test_quantised_unet_matches_reference(cuda, name):
     assert d64 <= 1.25 * dself + 1e-3 * mx, f"{name}: engine is {d64 / mx:.3e} of range from the fp64 evaluation, the reference {dself / mx:.3e}"
     assert d <= 1.5 * dself + 1e-3 * mx, f"{name}: {d / mx:.3e} of range vs envelope {dself / mx:.3e}"
     assert cos >= 0.995 and cos64 >= cosself - 1e-3
-    if name in TINY + ["cifar_full", "ldm_updown_tiny"]:
-        qnn.set_quant_state(True, False)
-        d, cos, mx = _metrics(_run(qnn, fx, cuda), fx["out_w"])
-        print(f"[{name}] W-only: max|diff|={d:.3e}")
-        assert d <= 1e-3 * mx
-        qnn.set_quant_state(False, False)
-        d, cos, mx = _metrics(_run(qnn, fx, cuda), fx["out_fp"])
-        print(f"[{name}] fp: max|diff|={d:.3e}")
-        assert d <= 1e-3 * mx
 
 
 @pytest.mark.parametrize("name", TINY + FULL)
