@@ -676,6 +676,30 @@ int qd_attn_h16(const void* q, const void* k, const void* v, int in_dtype, int B
                 int64_t ldo, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Wide single-pass attention (additive in ABI 20; DESIGN.md §4.11 addendum)
+ *
+ *     qd_attn_h16_wide: the same function as qd_attn_h16 — out = softmax(q k^T * scale) v per (b, h) in one fused sweep — for the
+ *         head dims above its range.  Replaces the mid-block attention of the first-stage decoders, reference
+ *         ldm/modules/diffusionmodules/model.py:144-196 (bmm, * c^-0.5, softmax, bmm over one head of 512 channels).
+ *         The parameter list is qd_attn_h16's, with these differences:
+ *         d          a multiple of 8 in [264, 512]; any T >= 1, S >= 1; no mask.  scale > 0.  A block of four waves owns 32
+ *                    queries and splits the head dim in slices of 128 channels, one per wave.
+ *         out        out_dtype QD_F32, QD_F16 or QD_BF16 (the operand rows of a bf16 layer that follows); merged-head rows
+ *                    out[b*T + t][h*d + c], row stride ldo (>= H*d, a multiple of 4 elements, out aligned to 4 elements).
+ *                    Columns >= H*d and rows >= B*T are not touched.
+ *         q, k, v    as for qd_attn_h16: in_dtype QD_F32 / QD_F16 / QD_BF16, element strides (sb, s_token, sh, sd), sd must be 1
+ *                    and every run of 8 channels 16-byte aligned (16-byte aligned bases, the other strides multiples of 16
+ *                    bytes' worth of elements); column ranges of one row tensor are read in place.
+ *         Scores accumulate in fp32 per slice (v_mfma_f32_32x32x16_{f16,bf16}) and the slices' partial scores are added in
+ *         fp32 in a fixed order, so results are run-to-run identical; the softmax runs in fp32 (exp2 with scale*log2 e folded
+ *         in); P is rounded to op_dtype for the P.V product.  Argument checks precede any device work.
+ * ------------------------------------------------------------------------------------------ */
+int qd_attn_h16_wide(const void* q, const void* k, const void* v, int in_dtype, int B, int T, int S, int H, int d,
+                     int64_t qsb, int64_t qst, int64_t qsh, int64_t qsd, int64_t ksb, int64_t kst, int64_t ksh, int64_t ksd,
+                     int64_t vsb, int64_t vst, int64_t vsh, int64_t vsd, float scale, int op_dtype, void* out, int out_dtype,
+                     int64_t ldo, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Weights-only producers (additive in ABI 20): the floating-point glue between the kernels of a
  *     weights-only block written straight as the fp16 / bf16 operand rows [M][ldo] that qd_conv2d_wq_h16 reads.  Input rows
  *     are fp32 or fp16 (x_dtype QD_F32 / QD_F16), 16-byte aligned with a row stride of a multiple of 16 bytes; arithmetic is

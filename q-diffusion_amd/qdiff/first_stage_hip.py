@@ -19,7 +19,9 @@ runs on (csrc/igemm_dma.hip: v_mfma_f32_32x32x16_bf16, LDS-DMA ring) — and eve
 * `Upsample` (model.py:48-63) never materialises the 4x map: the convolution gathers from the half-resolution rows
   (`upsample2x`);
 * the single-head 4096-token mid-block attention (model.py:144-196) takes q | k | v from ONE 1x1 convolution with bf16 output
-  and runs torch's scaled_dot_product_attention on them (plumbing; 1 % of the decoder's arithmetic).
+  and runs torch's scaled_dot_product_attention on them (plumbing; 1 % of the decoder's arithmetic) — or, with
+  `QDIFF_DECODER_ATTN=hip` / HipDecoder(attention="hip"), this package's fused attention kernels on the three column ranges
+  of that output in place: qd_attn_h16 up to 256 channels, qd_attn_h16_wide up to 512 (DECODER_ATTN below).
 
 Weights are rounded to bf16 once (`qd_pack_weights_bf16`, tile order); accumulation, bias, residual adds, GroupNorm
 statistics and swish are fp32.  The result therefore differs from the fp32 reference by bf16 operand rounding only;
@@ -44,6 +46,28 @@ USE_GRAPH = False
 DEFAULT_DTYPE = torch.bfloat16 if os.environ.get("QDIFF_DECODER_DTYPE", "fp16").lower() in ("bf16", "bfloat16") else torch.float16
 
 
+def _parse_attention(v):
+    v = (v or "").strip().lower()
+    if v in ("", "library", "sdpa", "0", "off"):
+        return "library"
+    if v in ("hip", "1", "on"):
+        return "hip"
+    raise ValueError(f"QDIFF_DECODER_ATTN={v!r}: expected library or hip")
+
+
+# Decoder attention: "library" (default) = an AttnBlock's softmax(q k^T c^-0.5) v is torch's scaled_dot_product_attention;
+# "hip" = it is one launch of this package's fused kernel on the q | k | v column ranges of the fused projection, read in place,
+# writing proj_out's operand rows: qd_attn_h16 for C <= 256, qd_attn_h16_wide for 256 < C <= 512; a wider block keeps the
+# library call.  QDIFF_DECODER_ATTN=hip, or set_decoder_attention(); HipDecoder(attention=...) pins one instance.
+DECODER_ATTN = _parse_attention(os.environ.get("QDIFF_DECODER_ATTN"))
+
+
+def set_decoder_attention(mode):
+    """"library" or "hip" (or the strings QDIFF_DECODER_ATTN accepts)."""
+    global DECODER_ATTN
+    DECODER_ATTN = _parse_attention(mode)
+
+
 class _Conv:
     __slots__ = ("wt", "bias", "cin_pad", "cout", "k", "pad", "stamp")
 
@@ -65,7 +89,10 @@ class HipDecoder:
     first use per device and re-built when the module's parameters were re-assigned or modified in place since
     (`load_state_dict` copies in place: the version counter of the parameter moves)."""
 
-    def __init__(self, decoder, dtype=None):
+    def __init__(self, decoder, dtype=None, attention=None):
+        if attention not in (None, "library", "hip"):
+            raise ValueError('HipDecoder: attention must be None (follow DECODER_ATTN), "library" or "hip"')
+        self.attention = attention
         if decoder.give_pre_end or decoder.tanh_out:
             raise hip.HipEngineError("HipDecoder: give_pre_end / tanh_out decoders are not used by the reference's configs")
         self.dec = decoder
@@ -139,6 +166,16 @@ class HipDecoder:
         dev, S, C = x.device, H * W, att.in_channels
         hn = self._norm(att.norm, x, part, B, S, False)
         qkv, _ = self._run_conv(self._qkv(dev, key + ".qkv", att), hn, B, H, W, out_dtype=self.dtype, stats=False)
+        if (self.attention or DECODER_ATTN) == "hip" and C % 8 == 0 and C <= 512:
+            # one head of C channels; q | k | v are column ranges of the [B*S][3C] rows: strides (batch, token, head, channel)
+            st = (S * 3 * C, 3 * C, C, 1)
+            narrow = C <= 256
+            o = torch.empty((B * S, C), dtype=torch.float32 if narrow and self.dtype == torch.bfloat16 else self.dtype, device=dev)
+            (hip.attn_h16 if narrow else hip.attn_h16_wide)(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], B, S, S, 1, C, st, st, st,
+                                                            int(C) ** (-0.5), self.dtype, o)
+            if o.dtype != self.dtype:               # qd_attn_h16 writes fp32 / fp16 rows only: a bf16 decoder rounds them here
+                o = o.to(self.dtype)
+            return self._run_conv(self._conv(dev, key + ".proj", att.proj_out), o, B, H, W, residual=x)
         q, k, v = (qkv[:, i * C:(i + 1) * C].reshape(B, 1, S, C) for i in range(3))
         o = F.scaled_dot_product_attention(q, k, v, scale=int(C) ** (-0.5)).reshape(B * S, C).contiguous()
         return self._run_conv(self._conv(dev, key + ".proj", att.proj_out), o, B, H, W, residual=x)
@@ -150,7 +187,7 @@ class HipDecoder:
         graph (reference: one `Decoder.forward` per batch, model.py:538-572); bit-identical, measured no faster."""
         if not (USE_GRAPH and z.is_cuda) or torch.cuda.is_current_stream_capturing():
             return self._walk(z)
-        key = (z.device, tuple(z.shape), z.dtype, self._stamp(*self.dec.parameters()))
+        key = (z.device, tuple(z.shape), z.dtype, self.attention or DECODER_ATTN, self._stamp(*self.dec.parameters()))
         g = self._graphs.get(key)
         if g is None:
             zs = z.clone()

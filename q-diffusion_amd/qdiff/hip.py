@@ -72,7 +72,7 @@ EXPORTS = ["qd_abi_version", "qd_last_error", "qd_device_ok", "qd_box_probe", "q
            "qd_conv2d_bf16", "qd_pack_weights_bf16_bytes", "qd_pack_weights_bf16", "qd_groupnorm_silu_bf16",
            "qd_pack_weights_h16", "qd_groupnorm_silu_h16", "qd_conv2d_wq_h16", "qd_rows_to_h16",
            "qd_conv2d_wq_h16_splitk_ws_bytes", "qd_wq_h16_config", "qd_conv2d_wq_h16_form",
-           "qd_attn_h16", "qd_layernorm_h16", "qd_geglu_h16", "qd_groupnorm_h16", "qd_groupnorm_mod_h16", "qd_groupnorm_resample_h16"]
+           "qd_attn_h16", "qd_attn_h16_wide", "qd_layernorm_h16", "qd_geglu_h16", "qd_groupnorm_h16", "qd_groupnorm_mod_h16", "qd_groupnorm_resample_h16"]
 
 _lib = None
 
@@ -156,6 +156,8 @@ def load():
     if hasattr(lib, "qd_conv2d_wq_h16_form"):    # (as qd_conv2d_i8_form above)
         lib.qd_conv2d_wq_h16_form.argtypes = [ctypes.POINTER(ConvDesc), i32, vp]
     lib.qd_attn_h16.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32] + [i64] * 12 + [f32, i32, vp, i32, i64, vp]
+    if hasattr(lib, "qd_attn_h16_wide"):         # (as qd_attn_i8_qp above)
+        lib.qd_attn_h16_wide.argtypes = lib.qd_attn_h16.argtypes
     lib.qd_layernorm_h16.argtypes = [vp, i32, i64, i32, i64, f32, vp, vp, vp, i32, i64, vp]
     lib.qd_geglu_h16.argtypes = [vp, i32, i64, i32, i64, vp, i32, i64, vp]
     lib.qd_groupnorm_h16.argtypes = [vp, i32, i64, i64, i32, i64, i32, f32, vp, vp, i32, vp, i32, i64, vp, vp]
@@ -513,6 +515,18 @@ def attn_h16(q, k, v, B, T, S, H, d, q_strides, k_strides, v_strides, scale, op_
     _check(load().qd_attn_h16(_ptr(q, "q"), _ptr(k, "k"), _ptr(v, "v"), _H16[q.dtype], B, T, S, H, d, *q_strides, *k_strides,
                               *v_strides, float(scale), _H16[op_dtype], _ptr(out, "out"), _H16[out.dtype], out.stride(0), _stream()),
            "qd_attn_h16")
+
+
+def attn_h16_wide(q, k, v, B, T, S, H, d, q_strides, k_strides, v_strides, scale, op_dtype, out):
+    """attn_h16 for head dims 264 .. 512 (qd_attn_h16_wide: the head dim split across the waves of a block); out may also be
+    bfloat16 rows."""
+    if op_dtype not in (torch.float16, torch.bfloat16):
+        raise HipEngineError("attn_h16_wide: operands must be float16 or bfloat16")
+    if q.dtype not in _H16 or k.dtype != q.dtype or v.dtype != q.dtype or out.dtype not in _H16:
+        raise HipEngineError(f"attn_h16_wide: unsupported dtypes q {q.dtype} k {k.dtype} v {v.dtype} out {out.dtype}")
+    _check(load().qd_attn_h16_wide(_ptr(q, "q"), _ptr(k, "k"), _ptr(v, "v"), _H16[q.dtype], B, T, S, H, d, *q_strides, *k_strides,
+                                   *v_strides, float(scale), _H16[op_dtype], _ptr(out, "out"), _H16[out.dtype], out.stride(0),
+                                   _stream()), "qd_attn_h16_wide")
 
 
 def _h16_rows_check(what, x, ldx, Cin, out, ldo, Cout):
