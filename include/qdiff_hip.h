@@ -700,6 +700,53 @@ int qd_attn_h16_wide(const void* q, const void* k, const void* v, int in_dtype, 
                      int64_t ldo, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * VQ first stage: nearest-codebook lookup (additive in ABI 20; DESIGN.md §4.11 addendum 2)
+ *
+ *     qd_vq_lookup: per pixel the index of the nearest codebook row and / or the row of a table at that index.  Replaces
+ *         qdiff/arch/first_stage.py `VectorQuantizer.indices` / `get_codebook_entry` — the `self.quantize(h)` of the reference's
+ *         ldm/models/autoencoder.py:274-283 `VQModelInterface.decode` — which build |z|^2 + |e|^2 - 2 z.e as a dense fp32
+ *         [B*S][n_e] matrix and take its argmin; here the matrix is never written.
+ *         z          logical [B][e_dim][S] tensor of z_dtype (QD_F32 / QD_F16 / QD_BF16) addressed by element strides
+ *                    (sb, sc, ss) as in qd_quantize_act: NCHW and channels-last are read in place.  B*S < 2^31.
+ *         codebook   dense [n_e][e_dim] fp32; e_dim in [1, 8], n_e in [1, 2^20].
+ *         table      dense [n_e][t_dim] fp32, t_dim in [1, 8]: the rows to emit (a host folds a per-pixel linear map that follows
+ *                    the gather into it once).  NULL: the codebook itself, t_dim = e_dim.
+ *         indices    int32 [B*S], pixel b*S + s; or NULL.
+ *         out        rows out[(b*S + s)*ldo + c] of out_dtype (QD_F32, or QD_F16 / QD_BF16 with ONE nearest-even rounding of the
+ *                    fp32 table entry); columns [t_dim, ldo) are written as zeros (the K pad of the convolution that reads
+ *                    the rows).  As for qd_rows_to_h16 the rows are 16-byte lanes: out 16-byte aligned, ldo >= t_dim a multiple
+ *                    of 8 elements (of 4 for QD_F32).  Rows at or beyond B*S are not touched.  Or NULL; not both NULL.
+ *         ws         qd_vq_lookup_ws_bytes(B, S, n_e) bytes, 8-byte aligned; may be NULL when that is 0.  Need not be cleared.
+ *         Arithmetic (this defines the function): h_j = |e_j|^2 / 2, the squares added in channel order in fp64 and the half
+ *         rounded ONCE to fp32; the score of code j for pixel p is, in fp32,
+ *             s = h_j;  s = fma(-z_c, e_jc, s)  for c = 0 .. e_dim-1 in that order
+ *         (z widened exactly to fp32).  The per-pixel constant |z|^2 of the squared distance is dropped: it does not move the
+ *         minimiser, and without it the score does not cancel as the expanded form does.  The index is the smallest j whose
+ *         score is not greater than any other (the first minimum, as torch.argmin); comparisons are strict and a NaN score
+ *         never wins, so a pixel holding a NaN yields index 0.  Error of s against the exact |e|^2/2 - z.e: at most
+ *         gamma_n (|e|^2/2 + sum_c |z_c e_jc|), gamma_n = n u / (1 - n u), u = 2^-24, n = e_dim + 2 (e_dim fmas, the rounding of
+ *         h, the fp64 sum).
+ *         Launch form, the one rule (qd_vq_lookup_form): a block owns a tile of 1024 pixels and stages the codebook through
+ *         LDS 512 codes at a time.  tiles = ceil(B*S / 1024).  tiles >= 256: one code slice, one launch, every block walks the
+ *         whole codebook and emits.  Fewer: want = ceil(512 / tiles) slices, at most min(64, ceil(n_e / 128));
+ *         per = ceil(n_e / want) rounded up to a multiple of 128 codes, slices = ceil(n_e / per); with slices >= 2 the grid is
+ *         tiles x slices, slice i scans codes [i*per, (i+1)*per) and writes (score, index) per pixel to ws[i][pixel] (8 bytes),
+ *         and a second launch takes the slices in index order with a strict <, which keeps the first minimum, and emits.  The
+ *         split does not change the function.  No atomics: results are bit-identical from run to run.
+ *         Argument checks precede any device work; a workspace that is missing or too small for the form is refused.
+ *     qd_vq_lookup_ws_bytes: slices * B*S * 8 for the form the rule picks now (0 for one slice, or for a refused shape).
+ *     qd_vq_lookup_form: form2 = {code slices, launches}; a pure host function.
+ *     qd_vq_config: slices -1 = the rule (default); n >= 1 = want n slices whatever the tile count (clamped as above).  For
+ *         tests and measurements; the only state the entry points have.
+ * ------------------------------------------------------------------------------------------ */
+int qd_vq_lookup(const void* z, int z_dtype, int64_t B, int64_t S, int e_dim, int64_t sb, int64_t sc, int64_t ss,
+                 const float* codebook, int n_e, const float* table, int t_dim, int32_t* indices, void* out, int out_dtype,
+                 int64_t ldo, void* ws, int64_t ws_bytes, void* stream);
+int64_t qd_vq_lookup_ws_bytes(int64_t B, int64_t S, int n_e);
+int qd_vq_lookup_form(int64_t B, int64_t S, int n_e, int32_t* form2);
+void qd_vq_config(int slices);
+
+/* ------------------------------------------------------------------------------------------
  * Weights-only producers (additive in ABI 20): the floating-point glue between the kernels of a
  *     weights-only block written straight as the fp16 / bf16 operand rows [M][ldo] that qd_conv2d_wq_h16 reads.  Input rows
  *     are fp32 or fp16 (x_dtype QD_F32 / QD_F16), 16-byte aligned with a row stride of a multiple of 16 bytes; arithmetic is

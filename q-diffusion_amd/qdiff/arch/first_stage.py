@@ -176,7 +176,18 @@ class VectorQuantizer(nn.Module):
         self.n_e, self.e_dim = n_e, e_dim
         self.embedding = nn.Embedding(n_e, e_dim)
 
+    def _hip(self, z):
+        """qdiff.first_stage_hip when QDIFF_DECODER_VQ=hip and qd_vq_lookup serves this call (a GPU tensor, e_dim <= 8, no
+        autograd), else None: the composition below, exactly as without the knob."""
+        if not (torch.is_tensor(z) and z.is_cuda):
+            return None
+        from .. import first_stage_hip as fh
+        return fh if fh.vq_kernel_serves(self, z) else None
+
     def indices(self, z):
+        fh = self._hip(z)
+        if fh is not None:
+            return fh.vq_indices(self, z)
         zf = z.permute(0, 2, 3, 1).reshape(-1, self.e_dim)
         e = self.embedding.weight
         d = torch.sum(zf ** 2, dim=1, keepdim=True) + torch.sum(e ** 2, dim=1) - 2 * torch.einsum('bd,dn->bn', zf, e.t())
@@ -190,6 +201,9 @@ class VectorQuantizer(nn.Module):
 
     def forward(self, z):
         b, c, h, w = z.shape
+        fh = self._hip(z)
+        if fh is not None:                                # one launch: lookup and gather, no index tensor
+            return fh.vq_entries(self, z)
         return self.get_codebook_entry(self.indices(z), (b, h, w, c))
 
 
@@ -300,10 +314,15 @@ def decode_first_stage(first_stage, z, scale_factor=1.0, force_not_quantize=Fals
         z = z.contiguous(memory_format=torch.channels_last)
     kw = dict(force_not_quantize=force_not_quantize) if isinstance(first_stage, VQModelDecoder) else {}
     if engine in ("hip", "hip_fp16", "hip_bf16"):
-        from ..first_stage_hip import hip_decoder
-        quant = z if (not isinstance(first_stage, VQModelDecoder) or force_not_quantize) else first_stage.quantize(z)
+        from ..first_stage_hip import hip_decoder, vq_rows, vq_rows_serve
         dt = {"hip": None, "hip_fp16": torch.float16, "hip_bf16": torch.bfloat16}[engine]
-        x = hip_decoder(first_stage.decoder, dt)(first_stage.post_quant_conv(quant).float())
+        hd = hip_decoder(first_stage.decoder, dt)
+        if isinstance(first_stage, VQModelDecoder) and not force_not_quantize and vq_rows_serve(first_stage, z):
+            # QDIFF_DECODER_VQ=hip: lookup, post_quant_conv (folded into the table) and conv_in's operand rows in one launch
+            x = hd.from_rows(vq_rows(first_stage, z, hd), z.shape[0], z.shape[2], z.shape[3])
+        else:
+            quant = z if (not isinstance(first_stage, VQModelDecoder) or force_not_quantize) else first_stage.quantize(z)
+            x = hd(first_stage.post_quant_conv(quant).float())
     elif engine is not None:
         raise ValueError(f"decode_first_stage: unknown engine {engine!r}")
     elif autocast_dtype is not None and z.is_cuda:

@@ -68,6 +68,86 @@ def set_decoder_attention(mode):
     DECODER_ATTN = _parse_attention(mode)
 
 
+def _parse_vq(v):
+    v = (v or "").strip().lower()
+    if v in ("", "library", "0", "off"):
+        return "library"
+    if v in ("hip", "1", "on"):
+        return "hip"
+    raise ValueError(f"QDIFF_DECODER_VQ={v!r}: expected library or hip")
+
+
+# Codebook lookup of the VQ first stage: "library" (default) = VectorQuantizer builds the [pixels][n_e] distance matrix and takes
+# torch.argmin; "hip" = one qd_vq_lookup call that never writes the matrix (VectorQuantizer.indices / forward on GPU tensors), and
+# in decode_first_stage(engine="hip*") that call gathers from the codebook folded through post_quant_conv straight into conv_in's
+# operand rows (vq_rows below).  QDIFF_DECODER_VQ=hip, or set_decoder_vq().
+DECODER_VQ = _parse_vq(os.environ.get("QDIFF_DECODER_VQ"))
+
+
+def set_decoder_vq(mode):
+    """"library" or "hip" (or the strings QDIFF_DECODER_VQ accepts)."""
+    global DECODER_VQ
+    DECODER_VQ = _parse_vq(mode)
+
+
+def vq_kernel_serves(vq, z):
+    """The knob is on and qd_vq_lookup takes this call: a 4-d fp32 / fp16 / bf16 GPU tensor, at most 8 channels, a codebook of
+    at most 2^20 fp32 rows, nothing for autograd to record.  Otherwise the caller keeps its composition."""
+    w = vq.embedding.weight
+    return (DECODER_VQ == "hip" and torch.is_tensor(z) and z.is_cuda and z.dim() == 4 and z.dtype in (torch.float32, torch.float16, torch.bfloat16)
+            and z.shape[1] == vq.e_dim and 1 <= vq.e_dim <= 8 and w.shape[0] <= 1 << 20 and w.dtype == torch.float32 and w.device == z.device
+            and z.numel() > 0 and not (torch.is_grad_enabled() and (z.requires_grad or w.requires_grad)))
+
+
+def vq_indices(vq, z):
+    """VectorQuantizer.indices on the kernel: int64 [b*h*w]"""
+    idx = torch.empty(z.shape[0] * z.shape[2] * z.shape[3], dtype=torch.int32, device=z.device)
+    hip.vq_lookup(z, vq.embedding.weight.detach().contiguous(), indices=idx)
+    return idx.long()
+
+
+def vq_entries(vq, z):
+    """VectorQuantizer.forward on the kernel: the nearest codebook rows as fp32 [b, c, h, w] (dense NCHW, as the composition)"""
+    b, c, h, w = z.shape
+    ldo = (c + 3) // 4 * 4
+    rows = torch.empty((b * h * w, ldo), dtype=torch.float32, device=z.device)
+    hip.vq_lookup(z, vq.embedding.weight.detach().contiguous(), out=rows)
+    return rows[:, :c].view(b, h, w, c).permute(0, 3, 1, 2).contiguous()
+
+
+def vq_folded_table(first_stage):
+    """T = E W^T + b, fp32 [n_e][z_channels] on the codebook's device: post_quant_conv is 1x1, a per-pixel linear map, so it
+    commutes with the gather and is applied to the codebook ONCE.  Cached on the module; re-made when one of the three
+    parameters was re-assigned or modified in place (HipDecoder._stamp)."""
+    e, pq = first_stage.quantize.embedding.weight, first_stage.post_quant_conv
+    stamp = HipDecoder._stamp(e, pq.weight, pq.bias)
+    hit = first_stage.__dict__.get("_hip_vq_table")
+    if hit is None or hit[0] != stamp:
+        w = pq.weight.detach().float().reshape(pq.weight.shape[0], -1)
+        t = e.detach().float() @ w.t()
+        if pq.bias is not None:
+            t = t + pq.bias.detach().float()
+        hit = first_stage.__dict__["_hip_vq_table"] = (stamp, t.contiguous())
+    return hit[1]
+
+
+def vq_rows(first_stage, z, hd):
+    """conv_in's operand rows [b*h*w][cin_pad] of HipDecoder `hd` for the latent z, in ONE launch: nearest code, row of the folded
+    table, rounding to the operand type, zero K pad.  No index tensor, no gathered latent, no post_quant_conv launch."""
+    b, _, h, w = z.shape
+    rows = torch.empty((b * h * w, hd.conv_in_width(z.device)), dtype=hd.dtype, device=z.device)
+    hip.vq_lookup(z, first_stage.quantize.embedding.weight.detach().contiguous(), table=vq_folded_table(first_stage), out=rows)
+    return rows
+
+
+def vq_rows_serve(first_stage, z):
+    """decode_first_stage's test for the fused head: the lookup itself, a plain 1x1 post_quant_conv of at most 8 outputs"""
+    pq = first_stage.post_quant_conv
+    return (vq_kernel_serves(first_stage.quantize, z) and isinstance(pq, torch.nn.Conv2d) and pq.kernel_size == (1, 1) and pq.groups == 1
+            and pq.out_channels <= 8 and pq.weight.device == z.device
+            and not (torch.is_grad_enabled() and pq.weight.requires_grad))
+
+
 class _Conv:
     __slots__ = ("wt", "bias", "cin_pad", "cout", "k", "pad", "stamp")
 
@@ -214,10 +294,30 @@ class HipDecoder:
         from .arch.first_stage import largest_activation_bytes
         if B * largest_activation_bytes(d, H, W) >= 1 << 32:      # fp32 bytes of the largest tensor of the walk (the last up-sampling level)
             raise HipBatchTooLarge("HipDecoder: batch too large for 32-bit row offsets; decode in chunks (decode_first_stage does)")
-        cin = self._conv(dev, "conv_in", d.conv_in)
-        x0 = torch.zeros((B * H * W, cin.cin_pad), dtype=self.dtype, device=dev)
+        x0 = torch.zeros((B * H * W, self.conv_in_width(dev)), dtype=self.dtype, device=dev)
         x0[:, :zc] = z.permute(0, 2, 3, 1).reshape(B * H * W, zc)
-        h, part = self._run_conv(cin, x0, B, H, W)
+        return self._walk_rows(x0, B, H, W)
+
+    def conv_in_width(self, dev):
+        """columns of conv_in's operand rows: z_channels padded to the K granule, the pad columns zero"""
+        return self._conv(dev, "conv_in", self.dec.conv_in).cin_pad
+
+    @torch.no_grad()
+    def from_rows(self, x0, B, H, W):
+        """The decode from READY operand rows of conv_in: x0 [B*H*W][conv_in_width] in the operand type, channels-last pixel
+        order, pad columns zero (what `_walk` builds from an fp32 latent; qd_vq_lookup writes them directly) -> fp32
+        [B, out_ch, H', W']."""
+        if x0.dtype != self.dtype or x0.dim() != 2 or tuple(x0.shape) != (B * H * W, self.conv_in_width(x0.device)) or not x0.is_contiguous():
+            raise hip.HipEngineError(f"HipDecoder.from_rows: expected dense {self.dtype} rows [{B * H * W}][{self.conv_in_width(x0.device)}], "
+                                     f"got {x0.dtype} {tuple(x0.shape)}")
+        from .arch.first_stage import largest_activation_bytes
+        if B * largest_activation_bytes(self.dec, H, W) >= 1 << 32:
+            raise HipBatchTooLarge("HipDecoder: batch too large for 32-bit row offsets; decode in chunks (decode_first_stage does)")
+        return self._walk_rows(x0, B, H, W)
+
+    def _walk_rows(self, x0, B, H, W):
+        d, dev = self.dec, x0.device
+        h, part = self._run_conv(self._conv(dev, "conv_in", d.conv_in), x0, B, H, W)
         h, part = self._resblock("mid.block_1", d.mid.block_1, h, part, B, H, W)
         a1 = d.mid.attn_1
         if all(hasattr(a1, n) for n in ("q", "k", "v", "proj_out", "norm")):      # AttnBlock (attn_type "vanilla")

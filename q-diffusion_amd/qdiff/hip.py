@@ -72,7 +72,7 @@ EXPORTS = ["qd_abi_version", "qd_last_error", "qd_device_ok", "qd_box_probe", "q
            "qd_conv2d_bf16", "qd_pack_weights_bf16_bytes", "qd_pack_weights_bf16", "qd_groupnorm_silu_bf16",
            "qd_pack_weights_h16", "qd_groupnorm_silu_h16", "qd_conv2d_wq_h16", "qd_rows_to_h16",
            "qd_conv2d_wq_h16_splitk_ws_bytes", "qd_wq_h16_config", "qd_conv2d_wq_h16_form",
-           "qd_attn_h16", "qd_attn_h16_wide", "qd_layernorm_h16", "qd_geglu_h16", "qd_groupnorm_h16", "qd_groupnorm_mod_h16", "qd_groupnorm_resample_h16"]
+           "qd_attn_h16", "qd_attn_h16_wide", "qd_vq_lookup", "qd_vq_lookup_ws_bytes", "qd_vq_lookup_form", "qd_vq_config", "qd_layernorm_h16", "qd_geglu_h16", "qd_groupnorm_h16", "qd_groupnorm_mod_h16", "qd_groupnorm_resample_h16"]
 
 _lib = None
 
@@ -158,6 +158,13 @@ def load():
     lib.qd_attn_h16.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32] + [i64] * 12 + [f32, i32, vp, i32, i64, vp]
     if hasattr(lib, "qd_attn_h16_wide"):         # (as qd_attn_i8_qp above)
         lib.qd_attn_h16_wide.argtypes = lib.qd_attn_h16.argtypes
+    if hasattr(lib, "qd_vq_lookup"):             # (likewise)
+        lib.qd_vq_lookup.argtypes = [vp, i32, i64, i64, i32, i64, i64, i64, vp, i32, vp, i32, vp, vp, i32, i64, vp, i64, vp]
+        lib.qd_vq_lookup_ws_bytes.restype = i64
+        lib.qd_vq_lookup_ws_bytes.argtypes = [i64, i64, i32]
+        lib.qd_vq_lookup_form.argtypes = [i64, i64, i32, vp]
+        lib.qd_vq_config.argtypes = [i32]
+        lib.qd_vq_config.restype = None
     lib.qd_layernorm_h16.argtypes = [vp, i32, i64, i32, i64, f32, vp, vp, vp, i32, i64, vp]
     lib.qd_geglu_h16.argtypes = [vp, i32, i64, i32, i64, vp, i32, i64, vp]
     lib.qd_groupnorm_h16.argtypes = [vp, i32, i64, i64, i32, i64, i32, f32, vp, vp, i32, vp, i32, i64, vp, vp]
@@ -527,6 +534,53 @@ def attn_h16_wide(q, k, v, B, T, S, H, d, q_strides, k_strides, v_strides, scale
     _check(load().qd_attn_h16_wide(_ptr(q, "q"), _ptr(k, "k"), _ptr(v, "v"), _H16[q.dtype], B, T, S, H, d, *q_strides, *k_strides,
                                    *v_strides, float(scale), _H16[op_dtype], _ptr(out, "out"), _H16[out.dtype], out.stride(0),
                                    _stream()), "qd_attn_h16_wide")
+
+
+_VQ_WS = {}              # (device, stream) -> scratch of the sliced codebook lookup (grows; old buffers stay alive for captured graphs)
+
+
+def _vq_scratch(device, nbytes):
+    bufs = _VQ_WS.setdefault((device, _stream()), [])
+    if not bufs or bufs[-1].numel() < nbytes:
+        bufs.append(torch.empty(max(nbytes, 4 << 20), dtype=torch.uint8, device=device))
+    return bufs[-1]
+
+
+def vq_lookup_form(B, S, n_e):
+    """(code slices, launches) of the qd_vq_lookup call for B x S pixels and n_e codes now (qd_vq_lookup_form; pure host)."""
+    form = (ctypes.c_int32 * 2)()
+    _check(load().qd_vq_lookup_form(B, S, n_e, ctypes.cast(form, ctypes.c_void_p)), "qd_vq_lookup_form")
+    return form[0], form[1]
+
+
+def vq_lookup(z, codebook, table=None, indices=None, out=None, ws=None):
+    """Nearest codebook row per pixel of z [B, e_dim, H, W] (fp32 / fp16 / bf16; NCHW or channels-last, read in place) without
+    the [pixels, n_e] distance matrix (qd_vq_lookup).  codebook [n_e, e_dim] and table [n_e, t_dim] (None: the codebook) are
+    dense fp32.  indices: int32 [B*H*W] or None; out: rows [B*H*W, ldo] (ldo = out.stride(0)) of fp32 / fp16 / bf16 or None —
+    table[index] in the first t_dim columns, zeros up to ldo.  ws: a scratch tensor of the caller's (tests); None: the
+    stream's own."""
+    if z.dim() != 4 or z.dtype not in _H16:
+        raise HipEngineError(f"vq_lookup: z must be a 4-d fp32 / fp16 / bf16 tensor, got {tuple(z.shape)} {z.dtype}")
+    B, E, H, W = z.shape
+    if H > 1 and z.stride(2) != W * z.stride(3):         # the two pixel axes must collapse into one stride
+        z = z.contiguous()
+    for name, t in (("codebook", codebook), ("table", table)):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous()):
+            raise HipEngineError(f"vq_lookup: {name} must be a dense 2-d float32 tensor")
+    if codebook.shape[1] != E or (table is not None and table.shape[0] != codebook.shape[0]):
+        raise HipEngineError(f"vq_lookup: codebook {tuple(codebook.shape)} does not match z's {E} channels (or the table's rows)")
+    if indices is not None and (indices.dtype != torch.int32 or not indices.is_contiguous() or indices.numel() < B * H * W):
+        raise HipEngineError("vq_lookup: indices must be a dense int32 tensor of B*H*W elements")
+    if out is not None and (out.dtype not in _H16 or out.dim() != 2 or not out.is_contiguous() or out.shape[0] < B * H * W):
+        raise HipEngineError("vq_lookup: out must be dense fp32 / fp16 / bf16 rows [B*H*W, ldo] (every column of a row is written)")
+    lib, S, n_e = load(), H * W, codebook.shape[0]
+    need = int(lib.qd_vq_lookup_ws_bytes(B, S, n_e))
+    if ws is None and need:
+        ws = _vq_scratch(z.device, need)
+    _check(lib.qd_vq_lookup(_ptr(z, "z"), _H16[z.dtype], B, S, E, z.stride(0), z.stride(1), z.stride(3), _ptr(codebook, "codebook"), n_e,
+                            _ptr(table, "table"), table.shape[1] if table is not None else E, _ptr(indices, "indices"), _ptr(out, "out"),
+                            _H16[out.dtype] if out is not None else F32, out.shape[1] if out is not None else 0,
+                            _ptr(ws, "ws"), ws.numel() * ws.element_size() if ws is not None else 0, _stream()), "qd_vq_lookup")
 
 
 def _h16_rows_check(what, x, ldx, Cin, out, ldo, Cout):
