@@ -726,6 +726,14 @@ int qd_attn_h16_wide(const void* q, const void* k, const void* v, int in_dtype, 
  *         never wins, so a pixel holding a NaN yields index 0.  Error of s against the exact |e|^2/2 - z.e: at most
  *         gamma_n (|e|^2/2 + sum_c |z_c e_jc|), gamma_n = n u / (1 - n u), u = 2^-24, n = e_dim + 2 (e_dim fmas, the rounding of
  *         h, the fp64 sum).
+ *         Values that are no numbers (these are values, not addresses: nothing faults).  A codebook row holding a NaN or an
+ *         infinity never wins a finite pixel: its h is +inf or NaN and every fma adds +-inf or NaN to it, so its score is
+ *         +inf or NaN and loses every strict comparison; the other rows score as if it were a far finite row.  A pixel
+ *         holding an infinity yields an index in [0, n_e): the first row whose score is -inf (-z_c e_jc = -inf with nothing
+ *         opposing it), 0 if every row scores NaN.  Such a pixel changes no other pixel's result, the three that share its
+ *         lane included.
+ *         An axis of extent 1 has no stride: S = 1 never reads ss, B = 1 never reads sb, e_dim = 1 never reads sc.  A caller
+ *         that collapses [H][W] into S passes the stride of the axis that is longer than 1.
  *         Launch form, the one rule (qd_vq_lookup_form): a block owns a tile of 1024 pixels and stages the codebook through
  *         LDS 512 codes at a time.  tiles = ceil(B*S / 1024).  tiles >= 256: one code slice, one launch, every block walks the
  *         whole codebook and emits.  Fewer: want = ceil(512 / tiles) slices, at most min(64, ceil(n_e / 128));

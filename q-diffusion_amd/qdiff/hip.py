@@ -562,8 +562,9 @@ def vq_lookup(z, codebook, table=None, indices=None, out=None, ws=None):
     if z.dim() != 4 or z.dtype not in _H16:
         raise HipEngineError(f"vq_lookup: z must be a 4-d fp32 / fp16 / bf16 tensor, got {tuple(z.shape)} {z.dtype}")
     B, E, H, W = z.shape
-    if H > 1 and z.stride(2) != W * z.stride(3):         # the two pixel axes must collapse into one stride
+    if H > 1 and W > 1 and z.stride(2) != W * z.stride(3):       # the two pixel axes must collapse into one stride
         z = z.contiguous()
+    ss = z.stride(3) if W > 1 else z.stride(2)           # an axis of one element keeps whatever stride its view had: never read it
     for name, t in (("codebook", codebook), ("table", table)):
         if t is not None and (t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous()):
             raise HipEngineError(f"vq_lookup: {name} must be a dense 2-d float32 tensor")
@@ -577,7 +578,7 @@ def vq_lookup(z, codebook, table=None, indices=None, out=None, ws=None):
     need = int(lib.qd_vq_lookup_ws_bytes(B, S, n_e))
     if ws is None and need:
         ws = _vq_scratch(z.device, need)
-    _check(lib.qd_vq_lookup(_ptr(z, "z"), _H16[z.dtype], B, S, E, z.stride(0), z.stride(1), z.stride(3), _ptr(codebook, "codebook"), n_e,
+    _check(lib.qd_vq_lookup(_ptr(z, "z"), _H16[z.dtype], B, S, E, z.stride(0), z.stride(1), ss, _ptr(codebook, "codebook"), n_e,
                             _ptr(table, "table"), table.shape[1] if table is not None else E, _ptr(indices, "indices"), _ptr(out, "out"),
                             _H16[out.dtype] if out is not None else F32, out.shape[1] if out is not None else 0,
                             _ptr(ws, "ws"), ws.numel() * ws.element_size() if ws is not None else 0, _stream()), "qd_vq_lookup")

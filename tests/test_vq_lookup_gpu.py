@@ -11,12 +11,9 @@ import torch
 from golden_util import load_fixture
 from test_first_stage import _build
 from test_first_stage_hip import DECODER_TOL, ENGINE
+from vq_lookup_cases import BF16, F16, F32, FORCED, MAX_SLICES, MIN_SLICE, STAGE, _assert_nearest, _margins, _run
 
 pytestmark = pytest.mark.gpu
-
-TILE, STAGE, MIN_SLICE, MAX_SLICES = 1024, 512, 128, 64          # include/qdiff_hip.h, the launch form of qd_vq_lookup
-FORCED = [-1, 1, 2, 1 << 20]                                     # the rule, one slice, two, the most the rule allows
-F32, F16, BF16 = torch.float32, torch.float16, torch.bfloat16
 
 
 @pytest.fixture
@@ -25,52 +22,6 @@ def lib():
     lib = hip.load()
     yield lib
     lib.qd_vq_config(-1)
-
-
-def _margins(z, cb):
-    """fp64 on the CPU: (argmin, per-pixel tolerance function of the kernel's index, mask of pixels whose runner-up is farther
-    than the tolerance at the minimiser, NaN-pixel mask) for z [B, E, H, W] (already in the kernel's input type)"""
-    zr, e = z.permute(0, 2, 3, 1).reshape(-1, z.shape[1]).double().cpu(), cb.double().cpu()
-    d = sum((zr[:, c:c + 1] - e[None, :, c]) ** 2 for c in range(e.shape[1]))
-    m = 0.5 * (e ** 2).sum(1)[None] + zr.abs() @ e.abs().t()
-    n = e.shape[1] + 3
-    gamma = n * 2.0 ** -24 / (1 - n * 2.0 ** -24)
-    return d, m, gamma, torch.isnan(zr).any(1)
-
-
-def _assert_nearest(z, cb, idx):
-    d, m, gamma, nan = _margins(z, cb)
-    idx = idx.cpu().long()
-    assert ((idx >= 0) & (idx < cb.shape[0])).all() and (idx[nan] == 0).all()
-    ok = ~nan
-    d, m, idx = d[ok], m[ok], idx[ok]
-    j0 = d.argmin(1)
-    rows = torch.arange(d.shape[0])
-    tol = 4 * gamma * torch.maximum(m[rows, idx], m[rows, j0])
-    excess = d[rows, idx] - d[rows, j0]
-    print(f"worst excess / tol {(excess / tol.clamp_min(1e-300)).max().item() if len(rows) else 0:.3f}")
-    assert (excess <= tol).all()
-    if d.shape[1] > 1:                                           # determined pixels: the index IS the fp64 argmin
-        second = d.topk(2, dim=1, largest=False).values[:, 1]
-        det = second - d[rows, j0] > tol
-        assert torch.equal(idx[det], j0[det]) and det.any()
-
-
-def _run(lib, cuda, z, cb, table, out_dtype, ldo, slices):
-    """one call with `slices` forced, poisoned workspace, sentinel row: (indices, out rows) after the byte-level checks"""
-    from qdiff import hip
-    P, T = z.shape[0] * z.shape[2] * z.shape[3], (cb if table is None else table).shape[1]
-    lib.qd_vq_config(slices)
-    ws = torch.full((max(int(lib.qd_vq_lookup_ws_bytes(z.shape[0], z.shape[2] * z.shape[3], cb.shape[0])), 8),), 255, dtype=torch.uint8, device=cuda)
-    buf = torch.full((P + 1, ldo), -1234.0, dtype=out_dtype, device=cuda)
-    idx = torch.full((P + 1,), -7, dtype=torch.int32, device=cuda)
-    hip.vq_lookup(z, cb, table=table, indices=idx, out=buf[:P], ws=ws)
-    torch.cuda.synchronize()
-    assert (buf[P] == -1234.0).all() and idx[P].item() == -7    # the row past B*S is not touched
-    want = (cb if table is None else table)[idx[:P].long()]
-    assert torch.equal(buf[:P, :T], want.to(out_dtype))          # bit for bit in fp32, ONE nearest-even rounding otherwise
-    assert (buf[:P, T:] == 0).all()
-    return idx[:P].clone()
 
 
 def _z(cuda, B, E, H, W, layout, dtype, g):
