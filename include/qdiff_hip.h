@@ -337,6 +337,22 @@ int qd_groupnorm_mod_silu_quant(const void* x, int x_dtype, int64_t B, int64_t S
                                 int8_t* out, int64_t ldo, float* yout, int64_t ldy,
                                 void* ws, const float* part_in, int nchunk_in, int64_t part_ld,
                                 const float* mod, int64_t mod_ld, void* stream);
+/* The first norm of an `updown` residual block on the W+A route (additive in ABI 20): GroupNorm (+ SiLU) of
+ * the fp32 channels-last map x [B*H*W][ldx], `h_upd`, and the act quantiser of `in_layers[-1]` in ONE apply launch, which also
+ * writes `x_upd(x)`, the fp32 skip rows conv2's epilogue adds, from the same loads (qdiff/quant_block.py:84-90).  Statistics
+ * over the full-resolution input; ws / part_in / nchunk_in / part_ld as for qd_groupnorm_silu_quant with S = H * W.
+ *   resample = 1: the 2x2 average (Downsample(channels, False) = AvgPool2d(2, 2)), H and W even.  Each output is
+ *       ((y00 + y01) + (y10 + y11)) * 0.25f of the four fp32 post-SiLU values, the order of qd_groupnorm_resample_h16,
+ *       quantised once: out [B * H/2 * W/2][ldo].  xr (optional) [B * H/2 * W/2][ldr]: the same combination of the raw input.
+ *   resample = 2: nearest 2x.  Quantising commutes with replication, so out is the SMALL map [B * H * W][ldo] (the
+ *       convolution replicates it: qd_conv_desc.upsample2x); xr (optional) [B * 2H * 2W][ldr] holds x replicated, bit for bit.
+ * C a multiple of 16 and of groups; x / xr rows 16-byte aligned (ldx, ldr multiples of 4), ldo a multiple of 16; columns
+ * [C, ldo) of out and [C, ldr) of xr are not written.  Any other resample is refused.  fp32 input only.                   */
+int qd_groupnorm_resample_silu_quant(const float* x, int64_t B, int H, int W, int C, int64_t ldx, int groups, float eps,
+                                     const float* gamma, const float* beta, int apply_silu, int resample,
+                                     const float* qparams, int qmin, int qmax, int off, int8_t* out, int64_t ldo,
+                                     float* xr, int64_t ldr, void* ws, const float* part_in, int nchunk_in, int64_t part_ld,
+                                     void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * K9a LayerNorm -> quantise (up to 3 consumers).  Replaces nn.LayerNorm (attention.py:229-231)

@@ -6,7 +6,7 @@
 // atomics) and one apply pass that reads the activation once and writes one byte per element.
 // GroupNorm has ONE statistics driver (gn_stats: partial sums, gn_finalize_kernel<64 | 256>, optional modulation) behind its
 // three kinds of entry, which differ in the apply pass alone: int8 codes (gn_apply_kernel, gn_apply_rows_kernel,
-// gn_apply_rows_h8_kernel), and fp16 / bf16 rows (gn_apply_h16_kernel; gn_apply_resample_h16_kernel for the resampling residual
+// gn_apply_rows_h8_kernel; gn_apply_resample_q8_kernel for the resampling residual blocks), and fp16 / bf16 rows (gn_apply_h16_kernel; gn_apply_resample_h16_kernel for the resampling residual
 // blocks) for the first-stage decoder and the weights-only blocks.
 #include "common.h"
 
@@ -1063,6 +1063,84 @@ __global__ __launch_bounds__(256) void gn_apply_resample_h16_kernel(const T* __r
     }
 }
 
+// The integer counterpart of gn_apply_resample_h16_kernel: the apply pass of an `updown` residual block on the W+A route
+// (qd_groupnorm_resample_silu_quant).  Thread = (pixel, 16-channel chunk): four 16-byte loads per pixel, ONE 16-byte store of
+// codes.  The per-element arithmetic up to the average is gn_apply_rows_kernel's, expression for expression; the quantiser is
+// qd_pack4_t.  Pad columns [C, ldo) are not written (as every int8 apply pass).  One thread per chunk, 64-thread blocks: the
+// maps are small (Churches: 8 x 8 .. 32 x 32), a launch is a few hundred waves, and one-wave blocks spread them over all CUs.
+//   MODE 1  2x2 average: pixel = one OUTPUT pixel of the [B][H/2][W/2] map.  The sixteen loads of its window are issued back to
+//           back; the four post-SiLU values are combined as ((y00 + y01) + (y10 + y11)) * 0.25f (the order of the 16-bit
+//           kernel) and quantised once.  xr: the same combination of the RAW input, x_upd(x), from the same loads.
+//   MODE 2  nearest 2x: pixel = one INPUT pixel; its codes go once to the SMALL map (the convolution's upsample2x gather
+//           replicates them), its raw chunk to the four rows (2h + dy, 2w + dx) of xr [B][2H][2W].
+template <int MODE>
+__global__ __launch_bounds__(64) void gn_apply_resample_q8_kernel(const float* __restrict__ x, long total, int H, int W, int C, long ldx,
+                                                                  const float* __restrict__ ab, int apply_silu,
+                                                                  const float* __restrict__ qp, float qmin, float qmax, int off,
+                                                                  int8_t* __restrict__ out, long ldo, float* __restrict__ xr, long ldr) {
+    static_assert(MODE == 1 || MODE == 2, "1 = 2x2 average, 2 = nearest 2x");
+    constexpr int NP = MODE == 1 ? 4 : 1;          // input pixels per thread
+    const long gid = (long)blockIdx.x * 64 + threadIdx.x;
+    if (gid >= total) return;
+    const int nch = C >> 4;
+    const int Wr = MODE == 1 ? W >> 1 : W, Hr = MODE == 1 ? H >> 1 : H;      // the map the thread index runs over
+    const long row = gid / nch;
+    const int c = (int)(gid - row * nch) * 16;
+    const long t = row / Wr;                       // b * Hr + h
+    const int w = (int)(row - t * Wr);
+    const long b = t / Hr;
+    const int h = (int)(t - b * Hr);
+    const long in0 = MODE == 1 ? (b * H + 2 * h) * W + 2 * w : row;
+    float4 xv[NP][4];
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) xv[p][k] = *reinterpret_cast<const float4*>(x + (in0 + (p >> 1) * (long)W + (p & 1)) * ldx + c + 4 * k);
+    const QP q = qd_load_qp(qp);
+    const QB qb = qd_bytes_setup(q, qmin, qmax, off);
+    const float* abp = ab + (b * C + c) * 2;
+    v4i codes;
+    // the quantiser's fast / exact choice and the SiLU switch are tested once per 16-byte group, never per element (common.h)
+    auto chunk = [&](auto ft) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float4 ab0 = *reinterpret_cast<const float4*>(abp + 8 * k);
+            const float4 ab1 = *reinterpret_cast<const float4*>(abp + 8 * k + 4);
+            const float a4[4] = {ab0.x, ab0.z, ab1.x, ab1.z}, s4[4] = {ab0.y, ab0.w, ab1.y, ab1.w};
+            float y[NP][4];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const float v[4] = {xv[p][k].x, xv[p][k].y, xv[p][k].z, xv[p][k].w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) y[p][j] = v[j] * a4[j] + s4[j];
+            }
+            if (apply_silu) {
+#pragma unroll
+                for (int p = 0; p < NP; ++p)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) y[p][j] = y[p][j] * (1.0f / (1.0f + expf(-y[p][j])));
+            }
+            if constexpr (MODE == 1) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) y[0][j] = ((y[0][j] + y[1][j]) + (y[2][j] + y[3][j])) * 0.25f;
+                if (xr)
+                    *reinterpret_cast<float4*>(xr + row * ldr + c + 4 * k) =
+                        make_float4(((xv[0][k].x + xv[1][k].x) + (xv[2][k].x + xv[3][k].x)) * 0.25f, ((xv[0][k].y + xv[1][k].y) + (xv[2][k].y + xv[3][k].y)) * 0.25f,
+                                    ((xv[0][k].z + xv[1][k].z) + (xv[2][k].z + xv[3][k].z)) * 0.25f, ((xv[0][k].w + xv[1][k].w) + (xv[2][k].w + xv[3][k].w)) * 0.25f);
+            } else if (xr) {
+                float* o = xr + ((t * 2) * (2L * W) + 2 * w) * ldr + c + 4 * k;
+                *reinterpret_cast<float4*>(o) = xv[0][k];
+                *reinterpret_cast<float4*>(o + ldr) = xv[0][k];
+                *reinterpret_cast<float4*>(o + 2L * W * ldr) = xv[0][k];
+                *reinterpret_cast<float4*>(o + (2L * W + 1) * ldr) = xv[0][k];
+            }
+            codes[k] = (int)qd_pack4_t<decltype(ft)::value>(y[0][0], y[0][1], y[0][2], y[0][3], q, qb);
+        }
+    };
+    QD_FAST_DISPATCH(q.fast, chunk);
+    *reinterpret_cast<v4i*>(out + row * ldo + c) = codes;
+}
+
 // the argument checks every GroupNorm -> operand rows entry shares (qd_groupnorm_h16's)
 inline int gn_h16_args(const char* who, const void* x, int x_dtype, int64_t B, int64_t S, int C, int64_t ldx, int groups, const void* out,
                        int out_dtype, int64_t ldo, const void* ws) {
@@ -1178,5 +1256,39 @@ extern "C" int qd_groupnorm_resample_h16(const void* x, int x_dtype, int64_t B, 
     else
         h16_launch(gn_apply_resample_h16_kernel<float, 2>, gn_apply_resample_h16_kernel<__half, 2>, x_dtype, x, total, st, H, W, C, (long)ldx, ab, apply_silu, o, (long)ldo, fh);
     QD_LAUNCH_CHECK("qd_groupnorm_resample_h16");
+    return 0;
+}
+
+// GroupNorm . SiLU, h_upd and the act quantiser of `in_layers[-1]` of an `updown` residual block on the W+A route, with x_upd(x)
+// from the same loads (reference quant_block.py:84-90).  Statistics: gn_stats as qd_groupnorm_silu_quant runs it (64-thread
+// finalise, part_in).  resample 1: out [B * H/2 * W/2][ldo], xr [B * H/2 * W/2][ldr]; 2: out [B * H * W][ldo] (the small map),
+// xr [B * 2H * 2W][ldr].
+extern "C" int qd_groupnorm_resample_silu_quant(const float* x, int64_t B, int H, int W, int C, int64_t ldx, int groups, float eps,
+                                                const float* gamma, const float* beta, int apply_silu, int resample,
+                                                const float* qparams, int qmin, int qmax, int off, int8_t* out, int64_t ldo,
+                                                float* xr, int64_t ldr, void* ws, const float* part_in, int nchunk_in,
+                                                int64_t part_ld, void* stream) {
+    const char* who = "qd_groupnorm_resample_silu_quant";
+    QD_REQUIRE(x && out && ws && qparams, "%s: null pointer", who);
+    QD_REQUIRE(H > 0 && W > 0 && B > 0 && B < 65536, "%s: empty map or batch too large", who);
+    QD_REQUIRE(resample == 1 || resample == 2, "%s: resample=%d must be 1 (2x2 average) or 2 (nearest 2x)", who, resample);
+    QD_REQUIRE(resample != 1 || (H % 2 == 0 && W % 2 == 0), "%s: the 2x2 average needs even H, W (got %d x %d)", who, H, W);
+    QD_REQUIRE(C > 0 && groups > 0 && C % groups == 0 && C % 16 == 0, "%s: C=%d must be a multiple of 16 and of groups=%d", who, C, groups);
+    QD_REQUIRE(ldx >= C && ldx % 4 == 0 && qd_aligned(x, 16), "%s: input rows must be 16-byte aligned", who);
+    QD_REQUIRE(ldo >= C && ldo % 16 == 0 && qd_aligned(out, 16), "%s: code rows must be 16-byte aligned (ldo %% 16 == 0)", who);
+    QD_REQUIRE(!xr || (ldr >= C && ldr % 4 == 0 && qd_aligned(xr, 16)), "%s: skip rows must be 16-byte aligned", who);
+    QD_REQUIRE(!part_in || (nchunk_in > 0 && (part_ld == 0 || part_ld >= C)), "%s: part_in needs nchunk_in > 0 and part_ld >= C", who);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const long S = (long)H * W;
+    const float* ab = gn_stats(x, QD_F32, B, S, C, ldx, groups, eps, gamma, beta, ws, part_in, nchunk_in, part_ld, false, nullptr, 0, st);
+    const long total = (resample == 1 ? (long)B * (H / 2) * (W / 2) : (long)B * S) * (C / 16);     // threads: output / input pixels
+    const dim3 grid((unsigned)((total + 63) / 64));
+    if (resample == 1)
+        hipLaunchKernelGGL(gn_apply_resample_q8_kernel<1>, grid, dim3(64), 0, st, x, total, H, W, C, (long)ldx, ab, apply_silu, qparams,
+                           (float)qmin, (float)qmax, off, out, (long)ldo, xr, (long)ldr);
+    else
+        hipLaunchKernelGGL(gn_apply_resample_q8_kernel<2>, grid, dim3(64), 0, st, x, total, H, W, C, (long)ldx, ab, apply_silu, qparams,
+                           (float)qmin, (float)qmax, off, out, (long)ldo, xr, (long)ldr);
+    QD_LAUNCH_CHECK(who);
     return 0;
 }

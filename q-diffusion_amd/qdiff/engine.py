@@ -1103,6 +1103,40 @@ def groupnorm_silu_quant(x_rows, B, S, C, gn, silu, plan=None, want_float=False,
     return out, y
 
 
+# Resampling residual blocks of the integer path: False (default) = an `updown` QuantResBlock resamples
+# between its first norm and first convolution in torch (quant_block._res_forward_int: F.avg_pool2d on fp32 rows and a
+# quantize_rows launch, or the expanded int8 rows and F.interpolate); True = one qd_groupnorm_resample_silu_quant apply launch
+# writes conv1's int8 rows and the resampled fp32 skip rows.  QDIFF_FUSE_UPDOWN=1, or engine.set_fused_updown().
+FUSE_UPDOWN = _parse_flag(os.environ.get("QDIFF_FUSE_UPDOWN"), "QDIFF_FUSE_UPDOWN")
+
+# qd_groupnorm_resample_silu_quant launches by kind of block (tests read it); never ticks while the knob is off
+UPDOWN_FUSED = {"down": 0, "up": 0}
+
+
+def set_fused_updown(on=True):
+    """True / False (or the strings QDIFF_FUSE_UPDOWN accepts)."""
+    _set_flag("FUSE_UPDOWN", on, "fused resampling residual blocks")
+
+
+def groupnorm_resample_quant(x_rows, B, H, W, C, gn, plan, resample, part=None):
+    """GroupNorm . SiLU of the channels-last fp32 map x_rows [B*H*W][>= C], resampled (1: 2x2 average, 2: nearest 2x) and
+    quantised for `plan`, with the resampled raw map from the same pass.  Returns (int8 rows [.][plan.ldx], fp32 rows [.][C]):
+    resample 1 both at H/2 x W/2; resample 2 the int8 rows at H x W (conv_forward(upsample2x=True) or the caller replicates
+    them) and the fp32 rows at 2H x 2W.  part: as for groupnorm_silu_quant."""
+    if len(plan.segs) != 1 or plan.pack.segs[0]["clen"] != C:
+        raise hip.HipEngineError("groupnorm producer feeds single-segment consumers of the same width only")
+    x_rows = _h16_input_rows(x_rows)
+    dev = x_rows.device
+    Mq = B * (H // 2) * (W // 2) if resample == 1 else B * H * W
+    out = torch.empty((Mq, plan.ldx), dtype=torch.int8, device=dev)
+    xr = torch.empty((Mq if resample == 1 else 4 * Mq, C), dtype=torch.float32, device=dev)
+    hip.groupnorm_resample_silu_quant(x_rows, B, H, W, C, x_rows.stride(0), gn.num_groups, gn.eps, gn.weight, gn.bias, True, resample,
+                                      plan.qparams[0], plan.grids[0], out, plan.ldx, _workspace(hip.groupnorm_ws_bytes(B, C, H * W), dev),
+                                      xr=xr, ldr=C, part=_part_view(part, B, H * W, C))
+    UPDOWN_FUSED["down" if resample == 1 else "up"] += 1
+    return out, xr
+
+
 def layernorm_quant(x_rows, M, C, ln, plans):
     """LayerNorm + one quantised copy per consumer plan (to_q / to_k / to_v have distinct deltas)."""
     outs = [torch.empty((M, p.ldx), dtype=torch.int8, device=x_rows.device) for p in plans]

@@ -64,7 +64,8 @@ EPI_GEGLU_H16 = 4          # qd_conv2d_wq_h16 only: value * gelu(gate) -> operan
 EXPORTS = ["qd_abi_version", "qd_last_error", "qd_device_ok", "qd_box_probe", "qd_make_qparams", "qd_quantize_act", "qd_pack_weights", "qd_pack_weights_t4",
            "qd_pack_weights_t8",
            "qd_conv2d_i8", "qd_conv_config", "qd_conv2d_i8_group", "qd_conv2d_i8_splitk_ws_bytes", "qd_conv2d_i8_form",
-           "qd_conv2d_i8_acc", "qd_groupnorm_ws_bytes", "qd_groupnorm_silu_quant", "qd_groupnorm_mod_silu_quant", "qd_layernorm_quant",
+           "qd_conv2d_i8_acc", "qd_groupnorm_ws_bytes", "qd_groupnorm_silu_quant", "qd_groupnorm_mod_silu_quant", "qd_groupnorm_resample_silu_quant",
+           "qd_layernorm_quant",
            "qd_geglu_quant", "qd_quantize_heads", "qd_attn_i8", "qd_attn_i8_qp", "qd_attn_i8_form", "qd_attn_keyterm", "qd_attn_uses_keyterm", "qd_attn_config", "qd_attn_ws_bytes", "qd_bmm_qk_i8", "qd_bmm_pv_i8", "qd_temb_mlp", "qd_temb_mlp_wq_h16",
            "qd_fakequant_blocks", "qd_fakequant_fwd", "qd_fakequant_bwd",
            "qd_adaround_blocks", "qd_adaround_fwd", "qd_adaround_bwd",
@@ -108,6 +109,9 @@ def load():
                                             i64, vp, i64, vp, vp, i32, i64, ctypes.POINTER(RawQuant), vp]
     lib.qd_groupnorm_mod_silu_quant.argtypes = [vp, i32, i64, i64, i32, i64, i32, f32, vp, vp, i32, vp, i32, i32, i32, vp,
                                                 i64, vp, i64, vp, vp, i32, i64, vp, i64, vp]
+    if hasattr(lib, "qd_groupnorm_resample_silu_quant"):      # (as qd_attn_i8_qp below)
+        lib.qd_groupnorm_resample_silu_quant.argtypes = [vp, i64, i32, i32, i32, i64, i32, f32, vp, vp, i32, i32, vp, i32, i32, i32,
+                                                         vp, i64, vp, i64, vp, vp, i32, i64, vp]
     lib.qd_layernorm_quant.argtypes = [vp, i32, i64, i32, i64, f32, vp, vp, i32, ctypes.POINTER(vp),
                                        ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32),
                                        ctypes.POINTER(vp), i64, vp]
@@ -719,6 +723,33 @@ def groupnorm_silu_quant(x, B, S, C, ldx, groups, eps, gamma, beta, silu, qparam
                                           _ptr(yout), ldy, _ptr(ws), _ptr(part), part.shape[1] if part is not None else 0,
                                           part_ld(part) if part is not None else 0,
                                           ctypes.byref(rq) if rq is not None else None, _stream()), "qd_groupnorm_silu_quant")
+
+
+def groupnorm_resample_silu_quant(x, B, H, W, C, ldx, groups, eps, gamma, beta, silu, resample, qparams, grid, out, ldo, ws,
+                                  xr=None, ldr=0, part=None):
+    """fp32 channels-last rows [B*H*W][ldx] -> GroupNorm (+ SiLU) -> resampled -> int8 rows of `grid`, and with xr the resampled
+    raw input as fp32 rows (qd_groupnorm_resample_silu_quant).  resample 1: the 2x2 average, out / xr rows [B*H/2*W/2] (even
+    H, W); 2: nearest 2x, out the SMALL map [B*H*W] (the convolution replicates it), xr rows [B*2H*2W].  part: as for
+    groupnorm_silu_quant.  ws: groupnorm_ws_bytes(B, C, H * W) bytes."""
+    who = "groupnorm_resample_silu_quant"
+    if x.dtype != torch.float32 or out.dtype != torch.int8 or (xr is not None and xr.dtype != torch.float32):
+        raise HipEngineError(f"{who}: fp32 rows -> int8 rows (+ fp32 skip rows) only (got {x.dtype} -> {out.dtype})")
+    if resample not in (1, 2):
+        raise HipEngineError(f"{who}: resample={resample} must be 1 (2x2 average) or 2 (nearest 2x)")
+    if resample == 1 and (H % 2 or W % 2):
+        raise HipEngineError(f"{who}: the 2x2 average needs even H, W (got {H} x {W})")
+    if C % 16 or C % groups:
+        raise HipEngineError(f"{who}: C={C} must be a multiple of 16 and of groups={groups}")
+    if ldx < C or ldx % 4 or x.data_ptr() % 16 or (xr is not None and (ldr < C or ldr % 4 or xr.data_ptr() % 16)):
+        raise HipEngineError(f"{who}: fp32 rows must be 16-byte aligned (row strides {ldx}, {ldr})")
+    if ldo < C or ldo % 16 or out.data_ptr() % 16:
+        raise HipEngineError(f"{who}: code rows must be 16-byte aligned with ldo % 16 == 0 and ldo >= {C} (ldo {ldo})")
+    _check(load().qd_groupnorm_resample_silu_quant(_ptr(x, "x"), B, H, W, C, ldx, groups, float(eps), _ptr(gamma), _ptr(beta),
+                                                   1 if silu else 0, resample, _ptr(_qp(qparams)), grid.qmin, grid.qmax, grid.off,
+                                                   _ptr(out, "out"), ldo, _ptr(xr), ldr, _ptr(ws, "ws"), _ptr(part),
+                                                   part.shape[1] if part is not None else 0,
+                                                   part_ld(part) if part is not None else 0, _stream()),
+           "qd_groupnorm_resample_silu_quant")
 
 
 def layernorm_quant(x, M, C, ldx, eps, gamma, beta, qparams_list, grids, outs, ldo):

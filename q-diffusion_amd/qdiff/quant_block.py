@@ -888,13 +888,37 @@ def _res_skip_plan(p, split, C):
     return plan if engine.raw_quant_segs(plan, C) is not None else None
 
 
+def _rep2x(xq, B, H, W):
+    """Rows [B*H*W][ld] of an H x W map replicated nearest-2x: rows [B*2H*2W][ld]."""
+    return xq.view(B, H, 1, W, 1, -1).expand(B, H, 2, W, 2, xq.shape[1]).reshape(B * 4 * H * W, xq.shape[1])
+
+
+def _res_updown_fused(p, x):
+    """This call of an `updown` block takes the one-launch producer (engine.FUSE_UPDOWN, qd_groupnorm_resample_silu_quant): an
+    fp32 stream and an fp32 map (even for the 2x2 average) of C % 16 == 0 channels, conv1 reading them as one segment through
+    initialised quantisers (the first call initialises them from the torch composition), the identity skip, and no forward /
+    pre-forward hook below the block: the route bypasses h_upd and x_upd, and a hooked model must keep seeing every module
+    call."""
+    if not engine.FUSE_UPDOWN or p.mode not in (1, 2) or p.skip is not None:
+        return False
+    C, H, W = x.shape[1:]
+    conv1 = p.conv1
+    if (engine.stream_dtype() != torch.float32 or x.dtype != torch.float32 or C % 16 or (p.mode == 1 and (H % 2 or W % 2))
+            or conv1.split != 0 or not all(q.inited for q in conv1._act_quantizers())
+            or not _no_hooks(*list(p.block.modules())[1:])):
+        return False
+    plan = conv1.conv_plan()
+    return len(plan.segs) == 1 and plan.pack.segs[0]["clen"] == C
+
+
 def _res_forward_int(p, x, emb, split, out_slot=None):
     """Reference :83-111 on the integer engine.  Plain blocks: GN.SiLU -> int8 (one pass; the skip connection's rows in
     the same pass), conv1 with the embedding as a row bias and the next norm's statistics in its epilogue, GN.SiLU ->
     int8, conv2 with the residual in its epilogue.  `updown` blocks (:84-90) resample between the first norm and the
     first convolution: nearest-2x commutes with the quantiser, so the SMALL map is quantised and its int8 rows are
     replicated; the 2x2 average does not, so the norm writes fp32 rows, torch averages them (F.avg_pool2d, as the
-    reference) and the small map is quantised.  `use_scale_shift_norm` blocks (:99-103) hand the two halves of the
+    reference) and the small map is quantised; with engine.FUSE_UPDOWN (_res_updown_fused) both resamplings, the quantiser and
+    x_upd(x) are one apply launch instead.  `use_scale_shift_norm` blocks (:99-103) hand the two halves of the
     embedding projection to the second norm as a per-sample modulation (qd_groupnorm_mod_silu_quant) instead of
     adding the projection to h."""
     B, C, H, W = x.shape
@@ -902,7 +926,18 @@ def _res_forward_int(p, x, emb, split, out_slot=None):
     rows = _nhwc_rows(x)
     blk, conv1, conv2 = p.block, p.conv1, p.conv2
     skp = _res_skip_plan(p, split, C)
-    if p.mode == 1:
+    fused, fold = _res_updown_fused(p, x), False
+    if fused:
+        # engine.FUSE_UPDOWN: norm . SiLU, h_upd, conv1's quantiser and x_upd(x) (the residual of conv2) in one apply launch
+        xq, rows = engine.groupnorm_resample_quant(rows, B, H, W, C, p.norm1, conv1.conv_plan(), p.mode,
+                                                   part=getattr(rows, "qd_gn_part", None))
+        H, W = (H // 2, W // 2) if p.mode == 1 else (2 * H, 2 * W)
+        S = H * W
+        if p.mode == 2:
+            fold = engine.upsample_fold_ok(conv1.conv_plan(), H, W)      # the replication rides in conv1's im2col gather
+            if not fold:
+                xq = _rep2x(xq, B, H // 2, W // 2)
+    elif p.mode == 1:
         y = engine.groupnorm_silu_quant(rows, B, S, C, p.norm1, True, want_float=True,
                                         part=getattr(rows, "qd_gn_part", None))[1]
         hp = blk.h_upd(_rows_to_nchw(y, B, H, W))
@@ -917,8 +952,8 @@ def _res_forward_int(p, x, emb, split, out_slot=None):
         xq, skq = _gn_silu_to(conv1, rows, B, S, C, p.norm1, raw_plan=skp)
     else:
         xq = _gn_silu_to(conv1, rows, B, S, C, p.norm1)
-    if p.mode == 2:
-        xq = xq.view(B, H, 1, W, 1, -1).expand(B, H, 2, W, 2, xq.shape[1]).reshape(B * 4 * S, xq.shape[1])
+    if p.mode == 2 and not fused:
+        xq = _rep2x(xq, B, H, W)
         x = blk.x_upd(x)
         H, W = 2 * H, 2 * W
         S = H * W
@@ -928,12 +963,12 @@ def _res_forward_int(p, x, emb, split, out_slot=None):
     if e is None:
         e = p.emb_rows(emb if p.emb_act is None else p.emb_act(emb)).float().contiguous()   # SiLU + integer linear -> [B, Cout] (2 Cout: scale | shift)
     if p.scale_shift:
-        h = conv1.forward_codes(xq, B, H, W, gn_stats=True)
+        h = conv1.forward_codes(xq, B, H, W, gn_stats=True, upsample2x=fold)
         if e.stride(1) != 1:
             e = e.contiguous()
         hq = _gn_silu_to(conv2, h, B, S, blk.out_channels, p.norm2, mod=e)
     else:
-        h = conv1.forward_codes(xq, B, H, W, rowbias=e, gn_stats=True)
+        h = conv1.forward_codes(xq, B, H, W, rowbias=e, gn_stats=True, upsample2x=fold)
         hq = _gn_silu_to(conv2, h, B, S, blk.out_channels, p.norm2)
     if p.skip is None:
         res = rows

@@ -502,7 +502,9 @@ class QuantModel(nn.Module):
         try:
             if graphs:
                 if tok >= 0:
-                    key = signature(x, timesteps, context) + (engine.STREAM_DTYPE, None if entry is None else entry["slot"], pair)
+                    # (engine.FUSE_UPDOWN selects other launches: an off / on A/B keeps both graphs, as the weights-only knobs do)
+                    key = signature(x, timesteps, context) + (engine.STREAM_DTYPE, None if entry is None else entry["slot"], pair,
+                                                              engine.FUSE_UPDOWN)
                 else:
                     key = signature(x, timesteps, context) + self._wonly_graph_key()
                 g = self._graphs.get(key)
