@@ -565,6 +565,44 @@ int qd_mse_search(const float* x, int64_t rows, int64_t cols, int64_t ldx, int p
                   int32_t* index, float* scores, void* ws, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Calibration: fused EMA range tracking and no-grad fake-quantisation of an activation tensor.
+ *     qd_range_track replaces, for a quantiser with running_stat set, UniformAffineQuantizer.act_momentum_update (reference
+ *     qdiff/quant_layer.py:91-110, called from :77-78) and the simulation that follows it (:82-88): two whole-tensor reductions,
+ *     the scalar chain and six elementwise launches become two launches (range partials; finalise and apply).
+ *     Geometry: that of qd_mse_search with per_row = 0 — `rows` rows of `cols` consecutive floats, row r at x + r * ldx
+ *     (ldx >= cols when rows > 1; 4-byte aligned: the x[:, :split] / x[:, split:] halves of a split layer are read in place,
+ *     bytes between the rows are never read).  Counts and indices are 64-bit: there is NO 2^31 limit.  fp32 only.
+ *     m, om: the host passes float32(0.95) and float32(1 - 0.95), the subtraction done in double.  mode: QD_RANGE_*.
+ *     range_in: {x_min, x_max} before the call (two floats; must not overlap state_out).  zero_point_in: read in the symmetric
+ *     mode only (may be null otherwise).  State, operation by operation in fp32 (no contraction, IEEE division), as ATen
+ *     evaluates the composition on the device — it divides a tensor by a host scalar as a product with its fp32 reciprocal:
+ *       mn' = x_min * m + min(x) * om             mx' = x_max * m + max(x) * om
+ *       symmetric:    delta = max(|mn'|, |mx'|) * (1.0f / n_levels)
+ *       always_zero:  delta = mx' * (1.0f / (n_levels - 1))
+ *       affine:       delta = (mx' - mn') * (1.0f / (n_levels - 1))
+ *       delta = max(delta, 1e-8f)  (a NaN stays NaN)
+ *       zp    = rint(-mn' / delta)   affine only; always_zero uses 0; symmetric uses zero_point_in[0], unchanged
+ *       y     = (clamp(rint(x / delta) + zp, qmin, qmax) - zp) * delta, a NaN kept by the clamp as torch.clamp keeps it
+ *     A NaN anywhere in x makes min(x) and max(x) NaN, as in ATen; which of +0 / -0 wins a tie is not pinned.
+ *     state_out: four floats {x_min', x_max', delta, zero_point}.  y: dense [rows * cols], 16-byte aligned; null = the state
+ *     alone (one block finalises, nothing is quantised).  ws: qd_range_track_ws_bytes(rows, cols) bytes, 16-byte aligned: one
+ *     16-byte {min, max, nan} record per block of the first launch, at most 2048 blocks.
+ *     No atomics and no block waits on another; results are bit-identical from run to run.
+ *     qd_fakequant_rows: the apply launch alone on the same geometry, delta / zero_point device scalars — the no-grad forward
+ *     of an initialised quantiser that is not tracking (:82-88; the capture runs of save_inp_oup_data).  Unlike
+ *     qd_fakequant_fwd it reads strided rows in place and keeps a NaN.
+ *     Refused with a message before any launch: a null pointer, an empty tensor, ldx < cols with more than one row,
+ *     n_levels < 2, an unknown mode, a misaligned x, y or ws.
+ * ------------------------------------------------------------------------------------------ */
+enum { QD_RANGE_AFFINE = 0, QD_RANGE_ALWAYS_ZERO = 1, QD_RANGE_SYMMETRIC = 2 };
+int64_t qd_range_track_ws_bytes(int64_t rows, int64_t cols);
+int qd_range_track(const float* x, int64_t rows, int64_t cols, int64_t ldx, float m, float om, int mode, int n_levels, int qmin,
+                   int qmax, const float* range_in, const float* zero_point_in, float* state_out, float* y, void* ws,
+                   void* stream);
+int qd_fakequant_rows(const float* x, int64_t rows, int64_t cols, int64_t ldx, const float* delta, const float* zero_point,
+                      int qmin, int qmax, float* y, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * First-stage decoder: the convolutions of the KL-f8 / VQ-f4 `Decoder`
  *     (ldm/modules/diffusionmodules/model.py:465-572 `Decoder.forward`: conv_in, ResnetBlock :80-141, AttnBlock :144-196
  *     q/k/v/proj_out, Upsample :48-63 nearest-2x + conv, conv_out; called from ldm/models/autoencoder.py:330-333 `decode`

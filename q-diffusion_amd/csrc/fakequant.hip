@@ -27,16 +27,10 @@ __global__ __launch_bounds__(256) void fakequant_fwd_kernel(const float* __restr
         const float4 v = *reinterpret_cast<const float4*>(x + i0);
         float in[4] = {v.x, v.y, v.z, v.w}, out[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const float r = rintf(in[j] / d) + zp;
-            out[j] = (fminf(fmaxf(r, lo), hi) - zp) * d;
-        }
+        for (int j = 0; j < 4; ++j) out[j] = qd_fakequant_one<false>(in[j], d, zp, lo, hi);
         *reinterpret_cast<float4*>(y + i0) = make_float4(out[0], out[1], out[2], out[3]);
     } else {
-        for (long i = i0; i < n; ++i) {
-            const float r = rintf(x[i] / d) + zp;
-            y[i] = (fminf(fmaxf(r, lo), hi) - zp) * d;
-        }
+        for (long i = i0; i < n; ++i) y[i] = qd_fakequant_one<false>(x[i], d, zp, lo, hi);
     }
 }
 

@@ -654,6 +654,22 @@ def mse_init_device_ok(t):
     return t.is_cuda
 
 
+# Fused range tracking and no-grad fake-quantisation: False (default) = UniformAffineQuantizer.forward runs
+# act_momentum_update and the simulation as ATen operators; True = without autograd an initialised quantiser with a scalar
+# delta hands an fp32 device tensor whose rows are consecutive in memory to qd_range_track (running_stat: EMA range, delta,
+# zero point and y in two launches) or qd_fakequant_rows (one launch).  The device check is mse_init_device_ok.
+# QDIFF_FUSED_RANGE_TRACK=1, or engine.set_fused_range_track().
+FUSED_RANGE_TRACK = _parse_flag(os.environ.get("QDIFF_FUSED_RANGE_TRACK"), "QDIFF_FUSED_RANGE_TRACK")
+
+# [qd_range_track calls, qd_fakequant_rows calls] (tests read it)
+RANGE_TRACK_CALLS = [0, 0]
+
+
+def set_fused_range_track(on):
+    """True / False (or the strings QDIFF_FUSED_RANGE_TRACK accepts)."""
+    _set_flag("FUSED_RANGE_TRACK", on, "fused range tracking")
+
+
 def wonly_device_ok(t):
     """The weights-only kernel runs on GPU tensors only; anything else keeps the library path."""
     return t.is_cuda

@@ -70,6 +70,7 @@ EXPORTS = ["qd_abi_version", "qd_last_error", "qd_device_ok", "qd_box_probe", "q
            "qd_fakequant_blocks", "qd_fakequant_fwd", "qd_fakequant_bwd",
            "qd_adaround_blocks", "qd_adaround_fwd", "qd_adaround_bwd",
            "qd_mse_search_form", "qd_mse_search_ws_bytes", "qd_mse_search",
+           "qd_range_track_ws_bytes", "qd_range_track", "qd_fakequant_rows",
            "qd_conv2d_bf16", "qd_pack_weights_bf16_bytes", "qd_pack_weights_bf16", "qd_groupnorm_silu_bf16",
            "qd_pack_weights_h16", "qd_groupnorm_silu_h16", "qd_conv2d_wq_h16", "qd_rows_to_h16",
            "qd_conv2d_wq_h16_splitk_ws_bytes", "qd_wq_h16_config", "qd_conv2d_wq_h16_form",
@@ -144,6 +145,11 @@ def load():
     lib.qd_mse_search_ws_bytes.restype = ctypes.c_int64
     lib.qd_mse_search_ws_bytes.argtypes = [i64, i64, i32, i32]
     lib.qd_mse_search.argtypes = [vp, i64, i64, i64, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "qd_range_track"):           # (as qd_attn_i8_qp above)
+        lib.qd_range_track_ws_bytes.restype = i64
+        lib.qd_range_track_ws_bytes.argtypes = [i64, i64]
+        lib.qd_range_track.argtypes = [vp, i64, i64, i64, f32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+        lib.qd_fakequant_rows.argtypes = [vp, i64, i64, i64, vp, vp, i32, i32, vp, vp]
     lib.qd_conv2d_bf16.argtypes = [ctypes.POINTER(ConvDesc), vp]
     lib.qd_pack_weights_bf16_bytes.restype = ctypes.c_int64
     lib.qd_pack_weights_bf16_bytes.argtypes = [i32, i32, i32]
@@ -970,6 +976,61 @@ def mse_search(x, per_row, n_bits, n_levels, always_zero, want_scores=False):
     from . import engine
     engine.MSE_INIT_SEARCHES[0] += 1
     return out[0], out[1], out[2], out[3], index, scores
+
+
+RANGE_AFFINE, RANGE_ALWAYS_ZERO, RANGE_SYMMETRIC = 0, 1, 2
+
+
+def _rows_together(x):
+    """adaround_rows(x) for an entry that treats all rows as one tensor: dense rows are one long row."""
+    rows, cols, ldx = adaround_rows(x)
+    return (1, rows * cols, rows * cols) if ldx == cols else (rows, cols, ldx)
+
+
+def _device_scalar(v, like, name):
+    """A 1-element fp32 device tensor of a quantiser's scalar: a tensor is viewed, a host number is filled in."""
+    if torch.is_tensor(v):
+        if v.numel() != 1 or v.device != like.device:
+            raise HipEngineError(f"{name} must be one element on {like.device} (got {tuple(v.shape)} on {v.device})")
+        return v.detach().reshape(1).float()
+    return torch.full((1,), float(v), dtype=torch.float32, device=like.device)
+
+
+def range_track(x, x_min, x_max, mode, n_levels, qmin, qmax, zero_point=None, momentum=0.95, want_y=True):
+    """UniformAffineQuantizer.act_momentum_update followed by the fake-quantisation of x, as one qd_range_track call (two
+    launches) over fp32 rows read in place (adaround_rows(x): a dense tensor or a channel slice).  x_min / x_max: the 0-dim
+    range before the call; zero_point: read in the symmetric mode only.  Returns (state, y): a fresh float[4] device tensor
+    {x_min, x_max, delta, zero_point} and the dense fp32 y of x's shape (None unless want_y: the state alone).  Never
+    synchronises."""
+    rows, cols, ldx = _rows_together(x)
+    lib = load()
+    dev = x.device
+    if x_min.data_ptr() + 4 == x_max.data_ptr():           # the two leading floats of the state an earlier call returned
+        range_in = x_min
+    else:
+        range_in = torch.stack((x_min.detach(), x_max.detach()))
+    state = torch.empty(4, dtype=torch.float32, device=dev)
+    y = torch.empty(x.shape, dtype=torch.float32, device=dev) if want_y else None
+    ws = torch.empty(int(lib.qd_range_track_ws_bytes(rows, cols)) // 4, dtype=torch.float32, device=dev)
+    zp = _device_scalar(0 if zero_point is None else zero_point, x, "zero_point") if mode == RANGE_SYMMETRIC else None
+    _check(lib.qd_range_track(_ptr(x, "x"), rows, cols, ldx, float(momentum), 1 - float(momentum), int(mode), int(n_levels), int(qmin),
+                              int(qmax), _ptr(range_in, "range"), _ptr(zp), _ptr(state), _ptr(y), _ptr(ws), _stream()), "qd_range_track")
+    from . import engine
+    engine.RANGE_TRACK_CALLS[0] += 1
+    return state, y
+
+
+def fakequant_rows(x, delta, zero_point, qmin, qmax):
+    """y = (clamp(rint(x / delta) + zp, qmin, qmax) - zp) * delta without autograd, one launch over fp32 rows read in place
+    (adaround_rows(x)); delta: a 1-element device tensor, zero_point: one or a host number.  A NaN stays a NaN."""
+    rows, cols, ldx = _rows_together(x)
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    _check(load().qd_fakequant_rows(_ptr(x, "x"), rows, cols, ldx, _ptr(_device_scalar(delta, x, "delta")),
+                                    _ptr(_device_scalar(zero_point, x, "zero_point")), int(qmin), int(qmax), _ptr(y), _stream()),
+           "qd_fakequant_rows")
+    from . import engine
+    engine.RANGE_TRACK_CALLS[1] += 1
+    return y
 
 
 def box_probe(device, kind, blocks, iters):

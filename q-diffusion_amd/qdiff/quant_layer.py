@@ -140,10 +140,45 @@ class UniformAffineQuantizer(nn.Module):
         self.zero_point = zero_point
         self.inited = True
 
+    def _nograd_route(self, x):
+        """True when the no-grad HIP route serves this call (engine.FUSED_RANGE_TRACK; csrc/range_track.hip):
+        the knob, no autograd through the quantiser, an initialised quantiser with one fp32 delta (and at most one zero point)
+        on x's device, x fp32 on a device the kernel runs on with rows consecutive in memory (a dense tensor, a channel slice
+        as B rows).  Anything else keeps the composition."""
+        d, z = self.delta, self.zero_point
+        return (engine.FUSED_RANGE_TRACK and self.inited and torch.is_tensor(x) and x.dtype == torch.float32
+                and engine.mse_init_device_ok(x) and torch.is_tensor(d) and d.numel() == 1 and d.dtype == torch.float32
+                and d.device == x.device and not (torch.is_tensor(z) and (z.numel() != 1 or z.device != x.device))
+                and not (torch.is_grad_enabled() and (x.requires_grad or d.requires_grad))
+                and hip.adaround_rows(x) is not None)
+
+    def track_range(self, x, want_y=False):
+        """EMA range tracking of a running_stat quantiser: ONE hip.range_track call on the route (the range, delta, the zero
+        point and, with want_y, the fake-quantised x from two launches), act_momentum_update (and y = None) off it.  On the
+        route x_min / x_max / delta / zero_point are 0-dim views of one fresh state tensor: the attribute types and the
+        state-generation bumps of act_momentum_update."""
+        ranged = all(torch.is_tensor(t) and t.dim() == 0 and t.dtype == torch.float32 and t.device == x.device
+                     for t in (getattr(self, "x_min", None), getattr(self, "x_max", None)))
+        if not (self.leaf_param and ranged and self._nograd_route(x)):
+            self.act_momentum_update(x)
+            return None
+        mode = hip.RANGE_SYMMETRIC if self.sym else hip.RANGE_ALWAYS_ZERO if self.always_zero else hip.RANGE_AFFINE
+        state, y = hip.range_track(x.detach(), self.x_min, self.x_max, mode, self.n_levels, *self.code_range(),
+                                   zero_point=self.zero_point, want_y=want_y)
+        self.x_min, self.x_max = state[0], state[1]
+        if not self.sym:
+            self.zero_point = 0 if self.always_zero else state[3]
+        self.delta = nn.Parameter(state[2])
+        return y
+
     def forward(self, x: torch.Tensor):
         self.ensure_init(x)
         if self.running_stat:
-            self.act_momentum_update(x)
+            y = self.track_range(x, want_y=True)
+            if y is not None:
+                return y
+        elif self._nograd_route(x):
+            return hip.fakequant_rows(x.detach(), self.delta, self.zero_point, *self.code_range())
         lo, hi = self.code_range()
         if (FUSED_FAKEQUANT and x.is_cuda and torch.is_grad_enabled() and x.dtype == torch.float32 and torch.is_tensor(self.delta)
                 and self.delta.numel() == 1 and self.delta.dtype == torch.float32 and (x.requires_grad or self.delta.requires_grad)):
@@ -537,7 +572,7 @@ class QuantModule(nn.Module):
         for q, xs in zip(self._act_quantizers(), self._input_slices(x)):
             q.ensure_init(xs)
             if q.running_stat:
-                q.act_momentum_update(xs)
+                q.track_range(xs)
 
     def _forward_int(self, x, out_slot=None):
         self._init_act_quantizers(x)
