@@ -603,6 +603,39 @@ int qd_fakequant_rows(const float* x, int64_t rows, int64_t cols, int64_t ldx, c
                       int qmin, int qmax, float* y, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Calibration: fused reconstruction term and its gradient (additive in ABI 20).
+ *     qd_recon_loss replaces, per iteration of the reconstruction loop, the gather of the target rows `cache[idx]`, the term
+ *     itself — QD_RECON_MSE: lp_loss with p = 2, (pred - tgt).abs().pow(2).sum(1).mean() (reference qdiff/quant_layer.py:26-33);
+ *     QD_RECON_FISHER_DIAG: ((pred - tgt).pow(2) * grad.pow(2)).sum(1).mean() (qdiff/block_recon.py:192-215) — and autograd's
+ *     walk back through it: one streaming launch and a one-block finalise.  fp32 only.
+ *     Geometry: pred is a logical [B][C][S] tensor (S = the product of the spatial extents; the sum runs over C, the mean over
+ *     B * S), each sample dense channel-major (pred_cl = 0: c * S + s) or channels-last (pred_cl = 1: s * C + c), sample b at
+ *     pred + b * ldp (ldp >= C * S when B > 1).  tgt_cache / grad_cache: `cache_rows` rows of the same logical [C][S] shape,
+ *     dense in the order cache_cl names, row r at cache + r * ldc (ldc >= C * S when cache_rows > 1); grad_cache is read in
+ *     FISHER_DIAG only (may be null otherwise) and shares the geometry.  idx: B int64 on the device; sample b is compared with
+ *     row idx[b], read in place.  An index outside [0, cache_rows) is never dereferenced: that sample's target reads as NaN.
+ *     Outputs: loss[0]; gpred, dense [B][C * S] in pred's order: dloss/dpred for an upstream gradient of 1.  Counts and
+ *     indices are 64-bit.  4-byte alignment suffices (idx: 8); 16-byte accesses are used where the sample bases allow.
+ *     Arithmetic, operation by operation in fp32 (no contraction), with inv = 1.0f / float(B * S) and d = pred - tgt:
+ *       MSE            term = |d| * |d|                gpred = (inv * (2 * |d|)) * sgn(d),  sgn(0) = sgn(NaN) = 0
+ *       FISHER_DIAG    term = (d * d) * (g * g)        gpred = (inv * (g * g)) * (2 * d)
+ *       loss = (sum of the terms) * inv; a lane adds 16 terms pairwise and chains its work items, lanes, waves, blocks (at most
+ *       2048 partials) and the finalise add as fixed binary trees.  No atomics: results are bit-identical from run to run.
+ *     pred_cl == cache_cl (or C = 1 or S = 1): a flat pass.  Otherwise 64 x 64 tiles, the cache side transposed through LDS, both
+ *     sides read along their own fast axis.  ws: qd_recon_loss_ws_bytes(B, C, S) bytes (0 for an empty shape), 4-byte aligned.
+ *     qd_recon_loss_scale: gpred[i] *= gout[0] over n floats, for an upstream gradient that is not 1; when the DEVICE scalar
+ *     gout[0] is exactly 1 the launch touches no byte of gpred — the host never has to read gout.
+ *     Refused with a message before any launch: a null pointer, an empty shape, a stride shorter than a sample, an unknown
+ *     mode, FISHER_DIAG without grad_cache, a misaligned pointer.
+ * ------------------------------------------------------------------------------------------ */
+enum { QD_RECON_MSE = 0, QD_RECON_FISHER_DIAG = 1 };
+int64_t qd_recon_loss_ws_bytes(int64_t B, int64_t C, int64_t S);
+int qd_recon_loss(const float* pred, int64_t ldp, int pred_cl, const float* tgt_cache, const float* grad_cache,
+                  int64_t cache_rows, int64_t ldc, int cache_cl, const int64_t* idx, int64_t B, int64_t C, int64_t S, int mode,
+                  float* loss, float* gpred, void* ws, void* stream);
+int qd_recon_loss_scale(float* gpred, int64_t n, const float* gout, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * First-stage decoder: the convolutions of the KL-f8 / VQ-f4 `Decoder`
  *     (ldm/modules/diffusionmodules/model.py:465-572 `Decoder.forward`: conv_in, ResnetBlock :80-141, AttnBlock :144-196
  *     q/k/v/proj_out, Upsample :48-63 nearest-2x + conv, conv_out; called from ldm/models/autoencoder.py:330-333 `decode`

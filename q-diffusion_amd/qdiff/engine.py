@@ -670,6 +670,27 @@ def set_fused_range_track(on):
     _set_flag("FUSED_RANGE_TRACK", on, "fused range tracking")
 
 
+# Fused reconstruction term: False (default) = the calibration loop gathers the target rows and differentiates
+# the ATen composition of the reconstruction term; True = for 'mse' with p == 2 and for 'fisher_diag', an fp32 device output
+# that requires grad and a resident cache, both dense NCHW or channels-last, go to qd_recon_loss: the target is read in place
+# through the batch indices, the loss and d loss / d pred come out of one pass.  Engages inside simulation(), as FUSED_ADAROUND.
+# QDIFF_FUSED_RECON_LOSS=1, or engine.set_fused_recon_loss().
+FUSED_RECON_LOSS = _parse_flag(os.environ.get("QDIFF_FUSED_RECON_LOSS"), "QDIFF_FUSED_RECON_LOSS")
+
+# qd_recon_loss calls (tests read it)
+RECON_LOSS_CALLS = [0]
+
+
+def set_fused_recon_loss(on):
+    """True / False (or the strings QDIFF_FUSED_RECON_LOSS accepts)."""
+    _set_flag("FUSED_RECON_LOSS", on, "fused reconstruction loss")
+
+
+def recon_loss_device_ok(t):
+    """The fused reconstruction term runs on GPU tensors only; anything else keeps the composition."""
+    return t.is_cuda
+
+
 def wonly_device_ok(t):
     """The weights-only kernel runs on GPU tensors only; anything else keeps the library path."""
     return t.is_cuda

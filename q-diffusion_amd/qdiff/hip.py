@@ -71,6 +71,7 @@ EXPORTS = ["qd_abi_version", "qd_last_error", "qd_device_ok", "qd_box_probe", "q
            "qd_adaround_blocks", "qd_adaround_fwd", "qd_adaround_bwd",
            "qd_mse_search_form", "qd_mse_search_ws_bytes", "qd_mse_search",
            "qd_range_track_ws_bytes", "qd_range_track", "qd_fakequant_rows",
+           "qd_recon_loss_ws_bytes", "qd_recon_loss", "qd_recon_loss_scale",
            "qd_conv2d_bf16", "qd_pack_weights_bf16_bytes", "qd_pack_weights_bf16", "qd_groupnorm_silu_bf16",
            "qd_pack_weights_h16", "qd_groupnorm_silu_h16", "qd_conv2d_wq_h16", "qd_rows_to_h16",
            "qd_conv2d_wq_h16_splitk_ws_bytes", "qd_wq_h16_config", "qd_conv2d_wq_h16_form",
@@ -150,6 +151,11 @@ def load():
         lib.qd_range_track_ws_bytes.argtypes = [i64, i64]
         lib.qd_range_track.argtypes = [vp, i64, i64, i64, f32, f32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
         lib.qd_fakequant_rows.argtypes = [vp, i64, i64, i64, vp, vp, i32, i32, vp, vp]
+    if hasattr(lib, "qd_recon_loss"):            # (likewise)
+        lib.qd_recon_loss_ws_bytes.restype = i64
+        lib.qd_recon_loss_ws_bytes.argtypes = [i64, i64, i64]
+        lib.qd_recon_loss.argtypes = [vp, i64, i32, vp, vp, i64, i64, i32, vp, i64, i64, i64, i32, vp, vp, vp, vp]
+        lib.qd_recon_loss_scale.argtypes = [vp, i64, vp, vp]
     lib.qd_conv2d_bf16.argtypes = [ctypes.POINTER(ConvDesc), vp]
     lib.qd_pack_weights_bf16_bytes.restype = ctypes.c_int64
     lib.qd_pack_weights_bf16_bytes.argtypes = [i32, i32, i32]
@@ -1031,6 +1037,65 @@ def fakequant_rows(x, delta, zero_point, qmin, qmax):
     from . import engine
     engine.RANGE_TRACK_CALLS[1] += 1
     return y
+
+
+RECON_MSE, RECON_FISHER_DIAG = 0, 1
+
+
+def recon_orders(t):
+    """The dense orders of the samples t[b] of a [B, C, *spatial] tensor: a subset of {0 (channel-major, NCHW), 1 (channels-last)}
+    — both when C or the spatial extent is 1, none when the samples are not dense or overlap."""
+    if t.dim() < 2 or t.numel() == 0 or (t.shape[0] > 1 and t.stride(0) < t[0].numel()):
+        return set()
+    return {o for o, v in ((0, t[0]), (1, t[0].movedim(0, -1))) if v.is_contiguous()}
+
+
+def recon_loss(pred, tgt_cache, idx, mode, grad_cache=None):
+    """(loss, gpred) of the reconstruction term between pred [B, C, *spatial] and the rows tgt_cache[idx], one qd_recon_loss call
+    (two launches).  mode: RECON_MSE (lp_loss with p = 2) or RECON_FISHER_DIAG (grad_cache[idx] weighs the squares).  The caches
+    are read in place through the int64 device tensor idx; pred's samples and the cache rows are each dense NCHW or channels-last,
+    in any combination.  loss: a 0-dim fp32 tensor; gpred: d loss / d pred in pred's order.  Never synchronises."""
+    caches = [tgt_cache] + ([grad_cache] if mode == RECON_FISHER_DIAG else [])
+    if mode not in (RECON_MSE, RECON_FISHER_DIAG) or (mode == RECON_FISHER_DIAG and grad_cache is None):
+        raise HipEngineError(f"recon_loss: mode {mode!r} is not RECON_MSE or RECON_FISHER_DIAG with a grad_cache")
+    for name, t in [("pred", pred)] + [("cache", c) for c in caches]:
+        if t.dtype != torch.float32 or t.device != pred.device:
+            raise HipEngineError(f"recon_loss: {name} must be fp32 on {pred.device} (got {t.dtype} on {t.device})")
+    po, co = recon_orders(pred), recon_orders(tgt_cache)
+    if not po or not co or any(c.shape != tgt_cache.shape or c.stride() != tgt_cache.stride() for c in caches):
+        raise HipEngineError(f"recon_loss: pred and the cache rows must be dense NCHW or channels-last, the caches alike "
+                             f"(shapes {[tuple(t.shape) for t in [pred] + caches]}, strides {[t.stride() for t in [pred] + caches]})")
+    if tgt_cache.shape[1:] != pred.shape[1:]:
+        raise HipEngineError(f"recon_loss: cache rows of shape {tuple(tgt_cache.shape[1:])} for samples of {tuple(pred.shape[1:])}")
+    B, C = pred.shape[:2]
+    if idx.dtype != torch.int64 or idx.device != pred.device or idx.shape != (B,) or not idx.is_contiguous():
+        raise HipEngineError(f"recon_loss: idx must be {B} consecutive int64 on {pred.device} (got {idx.dtype} {tuple(idx.shape)} on {idx.device})")
+    S = pred[0].numel() // C
+    both = po & co
+    pcl, ccl = (min(both),) * 2 if both else (min(po), min(co))      # a shared order: the flat pass
+    lib = load()
+    dev = pred.device
+    gpred = torch.empty(pred.shape, dtype=torch.float32, device=dev) if not pcl else \
+        torch.empty((B,) + tuple(pred.shape[2:]) + (C,), dtype=torch.float32, device=dev).movedim(-1, 1)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    ws = torch.empty(int(lib.qd_recon_loss_ws_bytes(B, C, S)) // 4, dtype=torch.float32, device=dev)
+    _check(lib.qd_recon_loss(_ptr(pred, "pred"), pred.stride(0), pcl, _ptr(tgt_cache, "tgt_cache"),
+                             _ptr(grad_cache, "grad_cache") if mode == RECON_FISHER_DIAG else None, tgt_cache.shape[0],
+                             tgt_cache.stride(0), ccl, _ptr(idx, "idx"), B, C, S, int(mode), _ptr(loss), _ptr(gpred), _ptr(ws),
+                             _stream()), "qd_recon_loss")
+    from . import engine
+    engine.RECON_LOSS_CALLS[0] += 1
+    return loss, gpred
+
+
+def recon_loss_scale(gpred, gout):
+    """gpred *= gout in place (gpred: what recon_loss returned; gout: a 1-element fp32 device tensor).  One launch that leaves
+    gpred alone when gout is exactly 1; the host never reads gout."""
+    if gout.numel() != 1 or gout.dtype != torch.float32 or gout.device != gpred.device:
+        raise HipEngineError(f"recon_loss_scale: gout must be one fp32 element on {gpred.device} (got {gout.dtype} {tuple(gout.shape)} on {gout.device})")
+    _check(load().qd_recon_loss_scale(_ptr(gpred, "gpred"), gpred.numel(), _ptr(gout.detach().reshape(1), "gout"), _stream()),
+           "qd_recon_loss_scale")
+    return gpred
 
 
 def box_probe(device, kind, blocks, iters):
